@@ -9,7 +9,7 @@ One step = project 4096 uint8 probe faces (p - mean).W + search the gallery + (N
 two all-gathers and the merge.  Inputs are resident in HBM before timing.  Data are
 synthetic (eigenface.synth): planted probes, so the step's result is also checked.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--backend nccl|gloo]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--backend nccl|gloo] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,12 @@ With WORLD_SIZE unset and --gpus N > 1 the script is its own launcher: the paren
 (which makes no GPU call) starts N rank processes of this file with RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, waits for all of them and exits
 non-zero if any rank fails.  Under torchrun, --gpus must equal WORLD_SIZE.
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps,
+the outputs of the last step to DIR/idx.npy + DIR/best.npy with --dump-outputs, one JSON
+line (metric, value, unit, ms_per_step, ...).  --full adds every other measurement and
+check to that line: result checks, rooflines, the side legs of the other scan arithmetic
+and merge, CPU baselines, the C2 / C5 records, the fits, the image / JPEG / Haar timings.
 """
 from __future__ import annotations
 
@@ -1019,8 +1025,20 @@ def main():
                     help="self-launch (N > 1 without torchrun): stop every rank after this many seconds (0: none)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed repeats of the K steps; value = the median repeat (BASELINE.md)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of the K steps; value = the median repeat (BASELINE.md).  Default: 1, so "
+                         "that --steps is the number of timed steps; 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run everything else the benchmark measures or checks: the "
+                         "planted-match / rank-agreement / host-buffer checks, kernel rooflines, the other scan "
+                         "arithmetic and the other merge as side legs, the CPU baselines, the C2 and C5 records, "
+                         "the fits, the image, JPEG and Haar timings (each can be skipped with its --no-* option, "
+                         "which has no effect without --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned to the caller, the packed keys "
+                         "decoded, as DIR/idx.npy (matched gallery row per probe, float64) and DIR/best.npy (its "
+                         "squared L2 distance or cosine score, float32); the inputs are seeded, so two builds "
+                         "can be compared output for output")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--metric", default="l2", choices=["l2", "cosine"])
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work")
@@ -1050,6 +1068,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:  # be the launcher: no torch / GPU call in this process
@@ -1123,7 +1143,7 @@ def main():
         # R repeats of exactly K timed steps, each bracketed by barrier + synchronize; the
         # reported step time is the median repeat (max over ranks within each repeat)
         reps = []
-        eng.timing(True)
+        eng.timing(args.full)  # per-kernel hipEvents feed the rooflines: --full only
         eng.timing_reset()
         for _ in range(max(1, args.repeats)):
             torch.cuda.synchronize(dev)
@@ -1150,16 +1170,23 @@ def main():
     reps, (s_ms, s_n), (p_ms, p_n) = timed(step)
     el = float(np.median(reps))
 
-    idx, best = decode_keys(keys.cpu().numpy(), args.metric)
-    match = float((idx == targets).mean())
+    match = None
+    if args.full or (args.dump_outputs and rank == 0):
+        idx, best = decode_keys(keys.cpu().numpy(), args.metric)
+        if args.dump_outputs and rank == 0:  # the last timed step's result, as its caller receives it
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "idx.npy"), idx.astype(np.float64))
+            np.save(os.path.join(args.dump_outputs, "best.npy"), best.astype(np.float32))
+        if args.full:
+            match = float((idx == targets).mean())
     exchange_ms = None
-    if world > 1:  # the step's collectives alone (upper bound of their share; max over ranks)
+    if world > 1 and args.full:  # the step's collectives alone (upper bound of their share; max over ranks)
         t = torch.tensor([shard.exchange_ms(bsz, k, dev)], dtype=torch.float64,
                          device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         exchange_ms = float(t.item())
     other_merge = None
-    if world > 1:  # the other exchange on the same step: exact record merge <-> one all-reduce(MIN)
+    if world > 1 and args.full:  # the other exchange on the same step: exact record merge <-> one all-reduce(MIN)
         main_keys = keys.clone()
         shard.merge = "min" if args.merge == "exact" else "exact"
         reps_o, _, _ = timed(step)
@@ -1172,7 +1199,7 @@ def main():
         shard.merge = args.merge
         keys.copy_(main_keys)
     ranks_agree = None
-    if world > 1:  # every rank must hold the same merged keys
+    if world > 1 and args.full:  # every rank must hold the same merged keys
         h = torch.tensor([int(np.bitwise_xor.reduce(keys.cpu().numpy() * np.int64(0x9E3779B1)))
                           & 0x7FFFFFFFFFFFFFFF], dtype=torch.int64,
                          device=dev if args.backend == "nccl" else "cpu")
@@ -1182,7 +1209,7 @@ def main():
         ranks_agree = bool(lo_t.item() == hi_t.item())
 
     host_rate = host_same = None
-    if world == 1:  # PCIe-inclusive rate (never `value`)
+    if world == 1 and args.full:  # PCIe-inclusive rate (never `value`)
         eng.use_own_stream()
         eng.recognize_keys(P, args.metric)
         t = time.perf_counter()
@@ -1192,7 +1219,7 @@ def main():
         host_same = bool(np.array_equal(hk, keys.cpu().numpy()))
 
     split_leg = None
-    if world == 1 and not args.no_split:
+    if world == 1 and args.full and not args.no_split:
         # the other scan precision on the same step: split-bf16 when the headline is fp32
         # (and vice versa); its keys must equal the headline's bit for bit
         eng.set_stream(stream.cuda_stream)
@@ -1209,12 +1236,12 @@ def main():
                      "keys_identical": bool(torch.equal(keys2, keys))}
 
     fit_sharded = None
-    if world > 1 and not args.no_fit:  # every rank: the sample-sharded fit is collective
+    if world > 1 and args.full and not args.no_fit:  # every rank: the sample-sharded fit is collective
         eng.set_stream(stream.cuda_stream)
         fit_sharded = fit_bench_sharded(eng, rank, world, args.backend, dev, n=args.fit_n, side=args.fit_side)
 
     tol = None
-    if world == 1 and precision == "bf16":
+    if world == 1 and args.full and precision == "bf16":
         # the bf16 projection's tolerance vs fp32 — max relative feature
         # error and the argmin agreement rate of the two projections on the same step
         eng.set_stream(stream.cuda_stream)
@@ -1236,6 +1263,7 @@ def main():
         ms_step = el / args.steps * 1e3
         value = bsz * args.steps / el
         search_avg_ms = s_ms / max(s_n, 1)
+        full1 = args.full and world == 1
 
         def roof(split, avg_ms):
             return scan_roofline(split, avg_ms, bsz, hi - lo, k, args.split_opt)
@@ -1245,7 +1273,7 @@ def main():
                 return args.config
             return args.config + ("hi" if args.split_opt == 3 and k > 128 else "s3")
 
-        traffic, traffic_src = pmc_traffic(traffic_key(split_main)) if world == 1 else (None, None)
+        traffic, traffic_src = pmc_traffic(traffic_key(split_main)) if full1 else (None, None)
         rec = {
             "metric": "faces/sec recognized (projection+NN) @1M-gallery k=128" if args.config == "c3"
                       else f"faces/sec recognized (projection+NN) @{n_total}-gallery k={k}",
@@ -1273,16 +1301,20 @@ def main():
                 "rows_per_rank": hi - lo,
                 "backend": args.backend if world > 1 else None,
             },
-            "roofline": dict(roof(split_main, search_avg_ms), traffic=traffic, traffic_source=traffic_src,
-                             launches=s_n),
-            "project_avg_ms": round(p_ms / max(p_n, 1), 4),
-            "exchange_ms_per_step": round(exchange_ms, 4) if exchange_ms is not None else None,
-            "exchange_share_of_step": round(exchange_ms / ms_step, 4) if exchange_ms is not None else None,
-            "merge": args.merge if world > 1 else None,
-            "other_merge": other_merge,
-            "host_buffer_faces_per_s": round(host_rate, 1) if host_rate else None,
-            "check": {"planted_match": match, "ranks_agree": ranks_agree, "host_buffer_keys_identical": host_same},
         }
+        if args.full:
+            rec.update({
+                "roofline": dict(roof(split_main, search_avg_ms), traffic=traffic, traffic_source=traffic_src,
+                                 launches=s_n),
+                "project_avg_ms": round(p_ms / max(p_n, 1), 4),
+                "exchange_ms_per_step": round(exchange_ms, 4) if exchange_ms is not None else None,
+                "exchange_share_of_step": round(exchange_ms / ms_step, 4) if exchange_ms is not None else None,
+                "merge": args.merge if world > 1 else None,
+                "other_merge": other_merge,
+                "host_buffer_faces_per_s": round(host_rate, 1) if host_rate else None,
+                "check": {"planted_match": match, "ranks_agree": ranks_agree,
+                          "host_buffer_keys_identical": host_same},
+            })
         if tol:
             rec["bf16_projection_tolerance"] = tol
         if split_leg:
@@ -1297,23 +1329,23 @@ def main():
                                  **dict(zip(("traffic", "traffic_source"),
                                             pmc_traffic(traffic_key(not split_main))))),
             }
-        if world == 1 and not args.no_cpu:
+        if full1 and not args.no_cpu:
             rec["cpu_baseline"] = cpu_baseline(P, mean, W, G, targets, args.cpu_budget)
             rec["cpu_baseline"]["reference_pattern"] = reference_pattern(P, mean, W, G.astype(np.float64), 16,
                                                                          args.cpu_budget)
-        else:
+        elif args.full:
             rec["cpu_baseline"] = None
-        if world == 1 and args.config == "c3" and not args.no_c2:
+        if full1 and args.config == "c3" and not args.no_c2:
             rec["c2"] = c2_bench(eng, not args.no_cpu)
-        if world == 1 and args.config == "c3" and not args.no_c5:
+        if full1 and args.config == "c3" and not args.no_c5:
             rec["c5"] = c5_bench(eng, dev, not args.no_cpu, args.steps, args.warmup, args.repeats,
                                  min(args.cpu_budget, 8.0), args.c5_opt)
-        if world == 1 and not args.no_fit:
+        if full1 and not args.no_fit:
             rec["fit"] = {"c3": fit_bench_c3(eng, not args.no_cpu, n=args.fit_n, side=args.fit_side),
                           "c2": fit_bench(eng, not args.no_cpu)}
         if fit_sharded is not None:
             rec["fit"] = {"c4": fit_sharded}
-        if world == 1 and not args.no_image:
+        if full1 and not args.no_image:
             eng.use_own_stream()
             eng.timing(True)
             rec.update(image_bench(eng, not args.no_cpu))

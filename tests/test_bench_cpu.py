@@ -31,11 +31,22 @@ def test_gpus_must_be_positive():
     assert r.returncode == 2
 
 
+def test_full_and_dump_outputs_are_options():
+    """--full and --dump-outputs DIR parse: the run gets as far as the WORLD_SIZE check
+    (before any GPU call) instead of stopping at an unrecognised argument."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
+                        "--dump-outputs", "unused"], capture_output=True, text=True, timeout=120,
+                       env=_env(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"))
+    assert r.returncode == 2 and "disagrees with WORLD_SIZE=2" in r.stderr
+    assert "unrecognized arguments" not in r.stderr
+
+
 def test_self_launch_sets_rank_env_and_propagates_failure():
-    """Here every rank finds no GPU and exits 2: the parent must report it (not 0), and
-    each rank must have seen its own RANK / LOCAL_RANK and the common WORLD_SIZE."""
+    """Here every rank finds no GPU (on a machine that has some they are hidden from the
+    ranks) and exits 2: the parent must report it (not 0), and each rank must have seen its
+    own RANK / LOCAL_RANK and the common WORLD_SIZE."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "3", "--launch-timeout", "200"], capture_output=True,
-                       text=True, timeout=300, env=_env())
+                       text=True, timeout=300, env=_env(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1"))
     assert r.returncode == 2, r.stderr[-2000:]
     assert "no GPU visible" in r.stderr
 

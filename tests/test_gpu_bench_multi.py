@@ -32,7 +32,7 @@ def _json_line(stdout):
 
 @pytest.mark.parametrize("metric", ["l2", "cosine"])
 def test_bench_two_ranks_one_gpu(metric):
-    r = _run(["--gpus", "2", "--backend", "gloo", "--gallery", "200000", "--metric", metric, "--no-cpu",
+    r = _run(["--gpus", "2", "--backend", "gloo", "--full", "--gallery", "200000", "--metric", metric, "--no-cpu",
               "--no-fit", "--no-image", "--no-c2", "--no-split", "--steps", "3", "--warmup", "1", "--repeats", "2",
               "--launch-timeout", "240"])
     assert r.returncode == 0, r.stderr[-3000:]
@@ -59,8 +59,8 @@ def test_bench_more_ranks_one_gpu(ranks, gallery):
     """Rehearsal of the driver's N = 4 run (and an uneven 3-way split: shards of 66667 /
     66668 rows, the probe slices 1366 / 1365) on the one card: every rank's keys agree and
     every planted probe finds its row across the shard boundaries."""
-    r = _run(["--gpus", str(ranks), "--backend", "gloo", "--gallery", str(gallery), "--no-cpu", "--no-fit",
-              "--no-image", "--no-c2", "--no-split", "--steps", "2", "--warmup", "1", "--repeats", "1",
+    r = _run(["--gpus", str(ranks), "--backend", "gloo", "--full", "--gallery", str(gallery), "--no-cpu",
+              "--no-fit", "--no-image", "--no-c2", "--no-split", "--steps", "2", "--warmup", "1", "--repeats", "1",
               "--launch-timeout", "240"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)
@@ -68,6 +68,41 @@ def test_bench_more_ranks_one_gpu(ranks, gallery):
     assert rec["check"]["planted_match"] == 1.0
     assert rec["check"]["ranks_agree"] is True
     assert rec["config"]["rows_per_rank"] in (gallery // ranks, -(-gallery // ranks))
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the run times exactly --steps steps once and prints the headline alone;
+    --dump-outputs writes the last step's matches as float arrays — every planted probe's own
+    gallery row and its squared distance — the same bytes from run to run."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k != "WORLD_SIZE"}
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--gallery", "100000",
+                               "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=ROOT)
+             for d in ("a", "b")]  # the same run twice, side by side
+    outs = []
+    try:
+        for p, d in zip(procs, ("a", "b")):
+            stdout, stderr = p.communicate(timeout=120)
+            assert p.returncode == 0, stderr[-3000:]
+            outs.append((np.load(tmp_path / d / "idx.npy"), np.load(tmp_path / d / "best.npy")))
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
+    rec = _json_line(stdout)
+    assert rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["warmup"] == 1
+    assert len(rec["repeats_ms_per_step"]) == 1 and rec["ms_per_step"] == rec["repeats_ms_per_step"][0]
+    assert rec["unit"] == "faces/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["value"] == pytest.approx(4096 / rec["ms_per_step"] * 1e3, rel=1e-3)
+    for key in ("roofline", "check", "cpu_baseline", "scan_split_bf16", "c2", "c5", "fit", "ingest", "haar"):
+        assert key not in rec
+    (idx, best), (idx2, best2) = outs
+    assert idx.dtype == np.float64 and best.dtype == np.float32 and idx.shape == best.shape == (4096,)
+    np.testing.assert_array_equal(idx, np.random.default_rng(2024).integers(0, 100_000, 4096))
+    assert np.isfinite(best).all() and (best >= 0).all()
+    assert idx.tobytes() == idx2.tobytes() and best.tobytes() == best2.tobytes()
 
 
 def test_bench_rejects_gpus_world_mismatch():

@@ -91,8 +91,8 @@ def test_bench_sharded_fit_two_ranks_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--gallery", "100000", "--no-cpu", "--no-image", "--no-c2", "--no-split", "--steps", "2",
-                        "--warmup", "1", "--repeats", "1", "--fit-n", "30000", "--fit-side", "64",
+                        "--full", "--gallery", "100000", "--no-cpu", "--no-image", "--no-c2", "--no-split",
+                        "--steps", "2", "--warmup", "1", "--repeats", "1", "--fit-n", "30000", "--fit-side", "64",
                         "--launch-timeout", "240"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -6,7 +6,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 timeout -k 10 300 python -u -m pytest tests/test_gpu_project.py -x -v --timeout 200 --timeout-method thread -p no:cacheprovider > $O/pytest.txt 2>&1 || { echo "pytest rc=$?"; tail -30 $O/pytest.txt; exit 1; }
 tail -1 $O/pytest.txt
-B="bench.py --config c5 --steps 5 --warmup 2 --no-cpu --no-fit --no-split --no-image"
+B="bench.py --full --config c5 --steps 5 --warmup 2 --no-cpu --no-fit --no-split --no-image"
 for v in wk128 wk64 wide; do
   case $v in wk128) E="EF_PROJ_WK=128";; wk64) E="EF_PROJ_WK=64";; wide) E="EF_PROJ_FRAG=0";; esac
   env EF_LIB_VARIANT=diag $E timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$v -o run -- python $B > $O/t_$v.txt 2>&1 || { echo "trace rc=$?"; tail $O/t_$v.txt; exit 1; }

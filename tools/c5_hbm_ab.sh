@@ -7,10 +7,10 @@ export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 9
 O=gpurun_out/$1; shift
 mkdir -p $O
-B="bench.py --config c5 --steps 3 --warmup 1 --repeats 1 --no-cpu --no-fit --no-image --no-split"
+B="bench.py --full --config c5 --steps 3 --warmup 1 --repeats 1 --no-cpu --no-fit --no-image --no-split"
 for v in base "$@"; do
   if [ "$v" = base ]; then unset EF_LIB_VARIANT; else export EF_LIB_VARIANT=$v; fi
-  timeout -k 10 240 python bench.py --config c5 --no-cpu --no-fit --no-image --no-c2 --no-split --steps 10 \
+  timeout -k 10 240 python bench.py --full --config c5 --no-cpu --no-fit --no-image --no-c2 --no-split --steps 10 \
     --repeats 3 > $O/$v.json 2> $O/$v.err || exit $?
   timeout -s KILL 180 rocprofv3 --kernel-include-regex search_wide16 --pmc FETCH_SIZE --output-format csv \
     -d $O/f_$v -o run -- python $B > $O/f_$v.txt 2>&1 || exit $?

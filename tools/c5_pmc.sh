@@ -11,9 +11,9 @@ mkdir -p $O
 # SPLIT=3 (default): the single-bf16 screen (pmc_summary_c5hi.json); SPLIT=1: the split-bf16 scan
 SPLIT=${SPLIT:-3}
 CFG=$([ "$SPLIT" = 3 ] && echo c5hi || echo c5s3)
-B="bench.py --config c5 --split-opt $SPLIT --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image"
+B="bench.py --full --config c5 --split-opt $SPLIT --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image"
 R="search_wide16"
-timeout -k 10 300 python bench.py --config c5 --split-opt $SPLIT --steps 5 --warmup 2 --no-cpu --no-fit > $O/bench.txt 2>&1 || exit $?
+timeout -k 10 300 python bench.py --full --config c5 --split-opt $SPLIT --steps 5 --warmup 2 --no-cpu --no-fit > $O/bench.txt 2>&1 || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python $B > $O/t.txt 2>&1 || exit $?
 timeout -s KILL 180 rocprofv3 --kernel-include-regex "$R" --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python $B > $O/pf.txt 2>&1 || exit $?
 timeout -s KILL 180 rocprofv3 --kernel-include-regex "$R" --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python $B > $O/pw.txt 2>&1 || exit $?

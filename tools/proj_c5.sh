@@ -9,7 +9,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_project.py -x -q --timeout 
 rc=$?
 tail -3 $O/pytest.txt
 [ $rc -ne 0 ] && exit $rc
-B="bench.py --config c5 --steps 3 --warmup 1 --no-cpu --no-fit"
+B="bench.py --full --config c5 --steps 3 --warmup 1 --no-cpu --no-fit"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pc -o run -- python $B > $O/t.txt 2>&1 || exit $?
 cp /tmp/pc/run_kernel_stats.csv $O/kernel_stats.csv
 grep -E "project_bf16|search_wide" $O/kernel_stats.csv | cut -c1-160

@@ -30,17 +30,17 @@ pmc3() {  # tag, kernel regex, config, bench args...
     $O/${t}_sq/run_counter_collection.csv $O/${t}_trace/run_kernel_stats.csv $O/pmc_summary_$cfg.json $cfg > $O/${t}_summary.txt
 }
 if [ "$PART" = all ] || [ "$PART" = bench ]; then
-  step bench 900 python bench.py || exit $?
+  step bench 900 python bench.py --full || exit $?
 fi
 if [ "$PART" = all ] || [ "$PART" = c3 ]; then
-  pmc3 c3 "search_kernel<128, 0, false, false, 0>" c3 bench.py --steps 5 --warmup 2 --no-cpu --no-fit --no-c2 --no-c5 --no-image || exit $?
+  pmc3 c3 "search_kernel<128, 0, false, false, 0>" c3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-fit --no-c2 --no-c5 --no-image || exit $?
 fi
 if [ "$PART" = all ] || [ "$PART" = c5 ]; then
-  pmc3 c5hi "search_wide16" c5hi bench.py --config c5 --split-opt 3 --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image || exit $?
-  pmc3 c5proj "project_bf16_frag" c5proj bench.py --config c5 --split-opt 3 --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image || exit $?
+  pmc3 c5hi "search_wide16" c5hi bench.py --full --config c5 --split-opt 3 --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image || exit $?
+  pmc3 c5proj "project_bf16_frag" c5proj bench.py --full --config c5 --split-opt 3 --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image || exit $?
 fi
 if [ "$PART" = all ] || [ "$PART" = c5fp32 ]; then
-  pmc3 c5 "search_wide_kernel<512" c5 bench.py --config c5 --search fp32 --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image || exit $?
+  pmc3 c5 "search_wide_kernel<512" c5 bench.py --full --config c5 --search fp32 --steps 3 --warmup 1 --no-cpu --no-fit --no-split --no-image || exit $?
 fi
 if [ "$PART" = all ] || [ "$PART" = image ]; then
   R="tm_corr|haar_cascade"

@@ -9,7 +9,7 @@ O=gpurun_out/${1:-r06/proj}
 mkdir -p $O
 timeout -k 10 300 python -u -m pytest tests/test_gpu_project.py -x -v --timeout 200 --timeout-method thread -p no:cacheprovider > $O/pytest.txt 2>&1 || { echo "pytest rc=$?"; tail -30 $O/pytest.txt; exit 1; }
 tail -2 $O/pytest.txt
-B="bench.py --config c5 --steps 5 --warmup 2 --no-cpu --no-fit --no-split --no-image"
+B="bench.py --full --config c5 --steps 5 --warmup 2 --no-cpu --no-fit --no-split --no-image"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_frag -o run -- python $B > $O/t_frag.txt 2>&1 || { echo "trace rc=$?"; tail $O/t_frag.txt; exit 1; }
 EF_LIB_VARIANT=diag EF_PROJ_FRAG=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_wide -o run -- python $B > $O/t_wide.txt 2>&1 || { echo "trace rc=$?"; tail $O/t_wide.txt; exit 1; }
 grep -hE "project_bf16|search_wide16|project_reduce" $O/trace_frag/run_kernel_stats.csv $O/trace_wide/run_kernel_stats.csv | cut -d, -f1-6

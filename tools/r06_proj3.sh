@@ -7,7 +7,7 @@ O=gpurun_out/${1:-r06/proj3}
 mkdir -p $O
 timeout -k 10 300 python -u -m pytest tests/test_gpu_project.py -x -q --timeout 200 --timeout-method thread -p no:cacheprovider > $O/pytest.txt 2>&1 || { echo "pytest rc=$?"; tail -30 $O/pytest.txt; exit 1; }
 tail -1 $O/pytest.txt
-B="bench.py --config c5 --steps 5 --warmup 2 --no-cpu --no-fit --no-split --no-image"
+B="bench.py --full --config c5 --steps 5 --warmup 2 --no-cpu --no-fit --no-split --no-image"
 for v in ml1 ml0 ml1b ml0b; do
   case $v in ml1*) E=1;; ml0*) E=0;; esac
   EF_LIB_VARIANT=diag EF_PROJ_MEAN_LDS=$E timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$v -o run -- python $B > $O/t_$v.txt 2>&1 || { echo "trace rc=$?"; tail $O/t_$v.txt; exit 1; }

@@ -9,7 +9,7 @@ O=gpurun_out/${1:-r06/proj384}
 mkdir -p $O
 for v in new old new2 old2; do
   case $v in old*) export EF_LIB_VARIANT=old;; *) unset EF_LIB_VARIANT;; esac
-  timeout -k 10 400 python bench.py --steps 2 --warmup 1 --repeats 1 --no-cpu --no-c2 --no-c5 --no-image > $O/b_$v.json 2> $O/b_$v.err || { echo "bench rc=$?"; tail $O/b_$v.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 2 --warmup 1 --repeats 1 --no-cpu --no-c2 --no-c5 --no-image > $O/b_$v.json 2> $O/b_$v.err || { echo "bench rc=$?"; tail $O/b_$v.err; exit 1; }
   python - $O/b_$v.json $v >> $O/ab.txt <<'PY'
 import json, sys
 f = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])["fit"]["c3"]

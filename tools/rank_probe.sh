@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 9
 O=gpurun_out/${1:-rprobe}
 mkdir -p $O
-B="bench.py --gallery 125000 --steps 20 --warmup 3 --no-cpu --no-fit --no-image"
+B="bench.py --full --gallery 125000 --steps 20 --warmup 3 --no-cpu --no-fit --no-image"
 for w in 256 512 1024; do
   EF_SEARCH_WGS=$w timeout -k 10 300 python $B > $O/wgs$w.json 2> $O/wgs$w.err || exit $?
 done

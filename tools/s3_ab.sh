@@ -7,7 +7,7 @@ O=gpurun_out/$1
 mkdir -p $O
 timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread -p no:cacheprovider \
   tests/test_gpu_search_split.py > $O/pytest.out 2>&1 || exit $?
-B="bench.py --no-cpu --no-fit --no-image --no-c2"
+B="bench.py --full --no-cpu --no-fit --no-image --no-c2"
 timeout -k 10 300 python $B --split-opt 1 > $O/bench1.out 2> $O/bench1.err || exit $?
 timeout -k 10 300 python $B --split-opt 2 > $O/bench2.out 2> $O/bench2.err || exit $?
 timeout -k 10 300 python $B --split-opt 1 > $O/bench1b.out 2> $O/bench1b.err || exit $?

@@ -9,7 +9,7 @@ for rep in 1 2; do
   for v in base "$@"; do
     if [ "$v" = base ]; then unset EF_LIB_VARIANT; else export EF_LIB_VARIANT=$v; fi
     timeout -k 10 200 python -u tools/tm_micro.py > $O/$v.$rep.micro.txt 2>&1 || exit $?
-    timeout -k 10 300 python bench.py --no-cpu --no-fit --no-c2 --no-c5 --no-split --steps 3 --repeats 1 > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
+    timeout -k 10 300 python bench.py --full --no-cpu --no-fit --no-c2 --no-c5 --no-split --steps 3 --repeats 1 > $O/$v.$rep.json 2> $O/$v.$rep.err || exit $?
     python - "$O" "$v" "$rep" >> $O/summary.txt <<'PY'
 import json, sys
 o, v, rep = sys.argv[1:4]
