@@ -287,9 +287,7 @@ __global__ __launch_bounds__(512, 1) void syrk_i8_kernel(const uint8_t* __restri
   constexpr int STG = (YT + TJ) * YK;       // bytes per stage (A panel, then B panel)
   static_assert(NP % 8 == 0, "pieces must split evenly over the 8 waves");
   __shared__ __attribute__((aligned(16))) uint8_t smem[NB * STG];
-  const int total = gridDim.x;  // multiple of 8; trailing blocks are idle padding
-  // blocks b and b+8 share an XCD: XCD x runs list entries [x*total/8, (x+1)*total/8)
-  const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
+  const int lin = xcd_lin();  // XCD-contiguous list entries; trailing blocks are idle padding
   if (lin >= nitems) return;
   const int ks = lin / ntiles;
   const int2 tt = order[lin - ks * ntiles];
@@ -464,15 +462,14 @@ __global__ __launch_bounds__(512, 1) void syrk16_i8_kernel(const uint8_t* __rest
   constexpr int STG = (YT + TJ) * YK;
   constexpr int DUMMY = NP % 8 ? 1024 : 0;
   __shared__ __attribute__((aligned(16))) uint8_t smem[NB * STG + DUMMY];  // + a dummy DMA target
-  const int total = gridDim.x;
-  const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
+  const int lin = xcd_lin();
   if (lin >= nitems) return;
   int64_t i0, j0, sb, nst;
   int ks = 0;
   int64_t oz_row0 = 0;  // OZ: the item's first output row
   if constexpr (OZ) {
     const int64_t odim = kps;
-    const int per = total >> 3, x = lin / per, r = lin - x * per;
+    const int per = (int)gridDim.x >> 3, x = lin / per, r = lin - x * per;
     int p, mt;
     sb = st_begin;
     nst = st_end - st_begin;

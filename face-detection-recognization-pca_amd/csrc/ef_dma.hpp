@@ -73,4 +73,12 @@ __device__ __forceinline__ void glds16_halves(const void* gsrc, unsigned m0a, un
 }
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// XCD-contiguous linear work index: blocks b and b + 8 share an XCD, so XCD x runs items
+// [x * total / 8, (x + 1) * total / 8) and items that share an operand meet in its L2.
+// The host launches a multiple of 8 blocks.
+__device__ __forceinline__ int xcd_lin() {
+  const int total = gridDim.x;
+  return (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
+}
+
 }  // namespace ef

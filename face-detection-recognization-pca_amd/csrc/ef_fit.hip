@@ -300,7 +300,7 @@ int subspace_wide(ef_ctx* c, Bufs& B, const double* C, int64_t dim, int kk, int 
     int hinfo = -1;
     const bool fused = chol_inv_supported(m);  // blocked Cholesky + L^-1 (ef_chol_blk.hip)
     if (fused) {
-#ifdef EF_CHOL_REG  // A/B build (tools/r05_chol.sh): round 4's register-resident kernel
+#ifdef EF_CHOL_REG  // A/B build (profiles/r05/README.md): round 4's register-resident kernel
       if (chol_inv_reg_supported(m))
         EF_HIP(c, launch_chol_inv_reg(s, G, m, m, 1e-13, Li, cinfo), "cholesky + L^-1");
       else

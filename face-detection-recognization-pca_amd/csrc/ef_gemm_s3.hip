@@ -48,9 +48,8 @@ __global__ __launch_bounds__(512, 1) void gemm_s3_kernel(const float* __restrict
   const int qd = lane >> 4, r16 = lane & 15;
   const int pg = wave & 3, rh = wave >> 2;
   // XCD-aware: the workgroups of one K range share an XCD (its slice of Bt3 stays in L2)
-  const int total = gridDim.x;  // host guarantees total % 8 == 0
-  const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
-  const int mtiles = total / splits;
+  const int lin = xcd_lin();
+  const int mtiles = (int)gridDim.x / splits;
   const int split = lin / mtiles, mt = lin - split * mtiles;
   const int64_t kslices = K / GBK;
   const int64_t s0 = kslices * split / splits, s1 = kslices * (split + 1) / splits;

@@ -114,10 +114,9 @@ __global__ __launch_bounds__(512, 1) void proj_i8_kernel(const uint8_t* __restri
   constexpr int BPW = TN / 128;                 // B pieces per wave per stage (A: 2)
   constexpr int PSTAGE = (PM + TN) * PK;        // bytes per stage: A panel, then B panel
   __shared__ __attribute__((aligned(16))) uint8_t smem[PNB * PSTAGE];
-  const int total = gridDim.x;  // multiple of 8; trailing blocks are idle padding
-  // blocks b and b+8 share an XCD: XCD x runs items [x*total/8, (x+1)*total/8), row-block
-  // major, so the N-tiles of a row block run together and share its X rows in L2
-  const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
+  // XCD-contiguous items (trailing blocks are idle padding), row-block major, so the N-tiles
+  // of a row block run together and share its X rows in L2
+  const int lin = xcd_lin();
   if (lin >= nblocks) return;
   const int mt = lin / ntn, nt = lin - (lin / ntn) * ntn;
   const int64_t m0 = (int64_t)mt * PM, n0 = (int64_t)nt * TN;

@@ -43,16 +43,12 @@
 // (tests/test_gpu_search_split.py; at the full C3 size, tests/test_gpu_c3_full.py).
 #include "ef_search_common.hpp"
 
-#include <climits>
 #include <cstdlib>
 #include <cmath>
 
 namespace ef {
 
 constexpr int TG = 64;  // gallery rows per LDS tile (two 32-row MFMA blocks)
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // round-to-nearest-even fp32 -> bf16 bits (finite inputs) and back
 __device__ __forceinline__ unsigned bf16_bits(float x) {
@@ -69,19 +65,12 @@ __device__ __forceinline__ void split8(const float* x, bf16x8& hi, bf16x8& lo) {
     lo[j] = (short)bf16_bits(x[j] - bf16_value(h));
   }
 }
-__device__ __forceinline__ bf16x8 as_bf16x8(const float4& v) {
-  bf16x8 r;
-  __builtin_memcpy(&r, &v, 16);
-  return r;
-}
 
 // Workgroup = 8 waves x 32 probes = 256 probes (the gallery is swept Bpad/256 times).
 // Each wave keeps its 32 probes as one B block (KP/2 VGPRs, pre-scaled) and runs the
 // tile's two 32-row blocks as two independent accumulator chains; the arg-best epilogue
 // is a branch-free top-2 in row order on registers.  <= 128 VGPRs -> 4 waves per SIMD.
-// ABL (diagnostic builds only, results invalid): bit 1 skips the epilogue, bit 4 skips
-// the per-tile wait + barrier.
-template <int KP, int METRIC, bool COLLECT, bool S3 = false, int ABL = 0>
+template <int KP, int METRIC, bool COLLECT, bool S3 = false>
 __global__ __launch_bounds__(512, 4) void search_kernel(
     const float* __restrict__ qpad, const float* __restrict__ G, const float* __restrict__ aux, int64_t n,
     int n_ptiles, int tiles_per_chunk, int64_t bpad, SearchWs ws) {
@@ -121,17 +110,13 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   const int c32 = lane & 31;
   const int lrow = lane / CPR, lc = lane % CPR;  // this lane's (row, chunk) inside a piece
 
-  const int64_t tiles_total = (n + TG - 1) / TG;
-  const int64_t t0 = (int64_t)gc * tiles_per_chunk;
-  const int64_t t1 = t0 + tiles_per_chunk < tiles_total ? t0 + tiles_per_chunk : tiles_total;
+  int64_t t0, t1;
+  chunk_range<TG>(n, gc, tiles_per_chunk, t0, t1);
   const int64_t s0 = (int64_t)pt * 256 + wave * 32 + c32;  // this lane's probe slot
 
   if (t0 >= t1) {  // empty chunk: publish "no candidate" so the reducer can skip it
     if constexpr (!COLLECT) {
-      if (h == 0) {
-        ws.part_key[(int64_t)gc * bpad + s0] = LLONG_MAX;
-        ws.part_b2[(int64_t)gc * bpad + s0] = __builtin_inff();
-      }
+      if (h == 0) top2_store_empty(ws, (int64_t)gc * bpad, s0);
     }
     return;
   }
@@ -243,10 +228,7 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
       }
     }
   }
-  float thr = -__builtin_inff();
-  if constexpr (COLLECT) {
-    if (s0 < n_amb) thr = ws.thr[s0];
-  }
+  const float thr = collect_threshold<COLLECT>(ws, s0, n_amb);
   // Consume every probe register here, so hipcc places its waits for these loads before
   // the loop; otherwise its (loop-merged) wait state puts vmcnt(0) inside the tile loop,
   // which would also drain the asm LDS-DMA of the next tile.
@@ -270,12 +252,7 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   auto consume = [&](const f32x16& v, int rowbase) {
     if constexpr (COLLECT) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (v[r] <= thr) {
-          const int pos = atomicAdd(&ws.cand_cnt[s0], 1);
-          if (pos < kCandMax) ws.cand[s0 * kCandMax + pos] = rowbase + (r & 3) + 8 * (r >> 2) + 4 * h;
-        }
-      }
+      for (int r = 0; r < 16; ++r) collect_hit(ws, s0, thr, v[r], rowbase, (r & 3) + 8 * (r >> 2) + 4 * h);
     } else {
       // Screen: a block whose minimum is not below the lane's runner-up changes neither
       // b1, b2 nor i1 (the update below would keep all three), so when no lane of the wave
@@ -387,16 +364,10 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
         if (row + 32 >= n) acc1[r] = INF;
       }
     }
-    if constexpr (ABL & 1) {
-      asm volatile("" ::"v"(acc0), "v"(acc1));
-    } else {
-      consume(acc0, tbase);  // rows of block 0 precede block 1 (row-order tie rule)
-      consume(acc1, tbase + 32);
-    }
-    if constexpr (!(ABL & 4)) {
-      dma_wait_all();
-      __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
-    }
+    consume(acc0, tbase);  // rows of block 0 precede block 1 (row-order tie rule)
+    consume(acc1, tbase + 32);
+    dma_wait_all();
+    __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
   }
 
   if constexpr (!COLLECT) {
@@ -404,29 +375,16 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
     const float ob1 = __shfl_xor(b1, 32);
     const int oi1 = __shfl_xor(i1, 32);
     const float ob2 = __shfl_xor(b2, 32);
-    const bool other = ob1 < b1 || (ob1 == b1 && oi1 < i1);
-    const float lose = other ? b1 : ob1;
-    b2 = fminf(fminf(b2, ob2), lose);
-    if (other) { b1 = ob1; i1 = oi1; }
-    if (h == 0) {
-      const int64_t o = (int64_t)gc * bpad;
-      ws.part_key[o + s0] = i1 == INT_MAX ? LLONG_MAX : pack_key(b1, (unsigned)i1);
-      ws.part_b2[o + s0] = b2;
-    }
+    top2_merge(b1, b2, i1, ob1, ob2, oi1);
+    if (h == 0) top2_store(ws, (int64_t)gc * bpad, s0, b1, b2, i1);
   }
   };  // body
   if constexpr (COLLECT) {
-    // collect pass: n_ptiles carries the collect plan's chunk count; the grid strides over
-    // the (chunk, queued probe tile) items, so a handful of queued probes still spread over
-    // the whole grid instead of one workgroup per main-pass chunk
-    const int n_amb = *ws.amb_count;
-    const int items = ((n_amb + 256 - 1) / 256) * n_ptiles;
-    for (int item = blockIdx.x; item < items; item += gridDim.x) body(item % n_ptiles, item / n_ptiles, n_amb);
+    collect_items<kSearchProbeTile>(ws, n_ptiles, body);  // n_ptiles carries the collect plan's chunk count
   } else {
-    // XCD-aware mapping: blocks b and b+8 share an XCD; give each XCD a contiguous run of
-    // (chunk, probe-tile) pairs so the probe tiles of one chunk are co-resident on it.
-    const int total = gridDim.x;  // host guarantees total % 8 == 0
-    const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
+    // each XCD gets a contiguous run of (chunk, probe-tile) pairs, so the probe tiles of
+    // one chunk are co-resident on it
+    const int lin = xcd_lin();
     const int gc = lin / n_ptiles;
     body(gc, lin - gc * n_ptiles, 0);
   }
@@ -458,9 +416,8 @@ __global__ __launch_bounds__(512, 4) void search16_kernel(
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qd = lane >> 4, r16 = lane & 15;
-  const int64_t tiles_total = (n + TG - 1) / TG;
-  const int64_t t0 = (int64_t)gc * tiles_per_chunk;
-  const int64_t t1 = t0 + tiles_per_chunk < tiles_total ? t0 + tiles_per_chunk : tiles_total;
+  int64_t t0, t1;
+  chunk_range<TG>(n, gc, tiles_per_chunk, t0, t1);
   int64_t sl0[2];
   sl0[0] = (int64_t)pt * 256 + wave * 32 + r16;
   sl0[1] = sl0[0] + 16;
@@ -469,10 +426,7 @@ __global__ __launch_bounds__(512, 4) void search16_kernel(
     if constexpr (!COLLECT) {
       if (qd == 0) {
 #pragma unroll
-        for (int pb = 0; pb < 2; ++pb) {
-          ws.part_key[(int64_t)gc * bpad + sl0[pb]] = LLONG_MAX;
-          ws.part_b2[(int64_t)gc * bpad + sl0[pb]] = __builtin_inff();
-        }
+        for (int pb = 0; pb < 2; ++pb) top2_store_empty(ws, (int64_t)gc * bpad, sl0[pb]);
       }
     }
     return;
@@ -550,12 +504,7 @@ __global__ __launch_bounds__(512, 4) void search16_kernel(
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (v[rb][r] <= thr[pb]) {
-            const int pos = atomicAdd(&ws.cand_cnt[sl0[pb]], 1);
-            if (pos < kCandMax) ws.cand[sl0[pb] * kCandMax + pos] = tbase + 16 * rb + 4 * qd + r;
-          }
-        }
+        for (int r = 0; r < 4; ++r) collect_hit(ws, sl0[pb], thr[pb], v[rb][r], tbase, 16 * rb + 4 * qd + r);
     } else {
       float mn = v[0][0];
 #pragma unroll
@@ -659,29 +608,16 @@ __global__ __launch_bounds__(512, 4) void search16_kernel(
         const float ob1 = __shfl_xor(b1[pb], off);
         const int oi1 = __shfl_xor(i1[pb], off);
         const float ob2 = __shfl_xor(b2[pb], off);
-        const bool other = ob1 < b1[pb] || (ob1 == b1[pb] && oi1 < i1[pb]);
-        const float lose = other ? b1[pb] : ob1;
-        b2[pb] = fminf(fminf(b2[pb], ob2), lose);
-        if (other) { b1[pb] = ob1; i1[pb] = oi1; }
+        top2_merge(b1[pb], b2[pb], i1[pb], ob1, ob2, oi1);
       }
-      if (qd == 0) {
-        const int64_t o = (int64_t)gc * bpad + sl0[pb];
-        ws.part_key[o] = i1[pb] == INT_MAX ? LLONG_MAX : pack_key(b1[pb], (unsigned)i1[pb]);
-        ws.part_b2[o] = b2[pb];
-      }
+      if (qd == 0) top2_store(ws, (int64_t)gc * bpad, sl0[pb], b1[pb], b2[pb], i1[pb]);
     }
   }
   };  // body
   if constexpr (COLLECT) {
-    // collect pass: n_ptiles carries the collect plan's chunk count; the grid strides over
-    // the (chunk, queued probe tile) items, so a handful of queued probes still spread over
-    // the whole grid instead of one workgroup per main-pass chunk
-    const int n_amb = *ws.amb_count;
-    const int items = ((n_amb + 256 - 1) / 256) * n_ptiles;
-    for (int item = blockIdx.x; item < items; item += gridDim.x) body(item % n_ptiles, item / n_ptiles, n_amb);
+    collect_items<kSearchProbeTile>(ws, n_ptiles, body);  // n_ptiles carries the collect plan's chunk count
   } else {
-    const int total = gridDim.x;  // host guarantees total % 8 == 0
-    const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
+    const int lin = xcd_lin();
     const int gc = lin / n_ptiles;
     body(gc, lin - gc * n_ptiles, 0);
   }
@@ -944,17 +880,16 @@ SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3) {
   // at C5 = 8 MiB > 4 MiB L2: 27x the gallery bytes measured).  Deal blocks of 8 probe
   // tiles x cblk chunks to each XCD instead: 2 MiB of probes stay L2-resident and each
   // chunk is read by n_ptiles / 8 XCDs.
-  // The split-bf16 wide kernel's probe tiles are 256 x KP x 4 B (512 KiB at KP = 512): 4
-  // of them per XCD keep 2 MiB of probes L2-resident.
   // collect plan: ~512 chunks (a few queued probes then spread over the whole chip; with
   // every probe tile queued the grid strides over all items, a main pass's work)
   pl.c_tpc = (int)std::max<int64_t>(1, (tiles + 511) / 512);
   pl.c_chunks = (int)((tiles + pl.c_tpc - 1) / pl.c_tpc);
   pl.c_grid = w3 ? 256 : 512;
-#ifndef EF_WIDE3_PB  // probe tiles per XCD block of the split-bf16 wide scan (variant builds: experiments)
-#define EF_WIDE3_PB 8
-#endif
-  const int pb = w3 ? EF_WIDE3_PB : 8;
+  // probe tiles per XCD block.  The split-bf16 wide kernels' probe tiles are 256 x KP x 4 B
+  // (512 KiB at KP = 512), so 8 of them fill an XCD's L2; with the serpentine k order of
+  // search_wide16_kernel that still fetches least from HBM (profiles/r04/c5_hbm_ab.txt), and
+  // 16, 4 and 2 measured slower (profiles/r04/c5_screen_pb16_ab.txt)
+  constexpr int pb = 8;
   pl.pblk = pl.n_ptiles;
   pl.cblk = 1;
   if (wide && pl.n_ptiles % pb == 0 && pl.n_ptiles > pb) {
@@ -1043,21 +978,8 @@ static hipError_t search_t(hipStream_t s, const SearchPlan& pl, const float* qpa
     const hipError_t e = launch_search_wide(s, kp, M, false, 0, pl, qpad, G, aux, n, bpad, ws);
     if (e != hipSuccess) return e;
   } else {
-#ifdef EF_DIAGNOSTICS
-  static const int abl = [] { const char* e = getenv("EF_SEARCH_ABL"); return e ? atoi(e) : 0; }();
-#else
-  constexpr int abl = 0;
-#endif
-  if (KP == 128 && M == EF_METRIC_L2 && abl > 0) {  // diagnostic build only: ablations (timing, wrong results)
-#ifdef EF_DIAGNOSTICS
-    auto k = abl == 1 ? search_kernel<KP, M, false, false, 1>
-                      : abl == 4 ? search_kernel<KP, M, false, false, 4> : search_kernel<KP, M, false, false, 5>;
-    hipLaunchKernelGGL(k, grid, block, 0, s, qpad, G, aux, n, pl.n_ptiles, pl.tiles_per_chunk, bpad, ws);
-#endif
-  } else {
     hipLaunchKernelGGL((search_kernel<KP, M, false>), grid, block, 0, s, qpad, G, aux, n, pl.n_ptiles,
                        pl.tiles_per_chunk, bpad, ws);
-  }
   }
   if (timed_main) timer_end(c, tev);
   hipError_t e = hipGetLastError();

@@ -1,5 +1,10 @@
-// Device helpers shared by the search kernels (ef_search.hip, ef_search_wide.hip).
+// Device and host helpers shared by the search kernels (ef_search.hip, ef_search_wide.hip,
+// and the diagnostic-only ef_search_screen.hip): the arg-best contract (top-2 merge, tie
+// rule, per-chunk partial records, COLLECT), the XCD block deal, and the wide kernels'
+// common chunk / DMA geometry.
 #pragma once
+
+#include <climits>
 
 #include "ef_dma.hpp"
 #include "ef_internal.hpp"
@@ -7,6 +12,29 @@
 namespace ef {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+
+// min / max of three floats as one v_min3_f32 / v_max3_f32, without the compiler's IEEE-mode
+// canonicalisation of each input (scores are finite or +-inf, never NaN)
+__device__ __forceinline__ float min3_raw(float a, float b, float c) {
+  float r;
+  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+__device__ __forceinline__ float max3_raw(float a, float b, float c) {
+  float r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+// 16 bytes (a float4 from LDS, a register quad) as a bf16x8 MFMA operand
+template <typename T>
+__device__ __forceinline__ bf16x8 as_bf16x8(const T& v) {
+  static_assert(sizeof(T) == 16, "one 16-byte fragment");
+  bf16x8 r;
+  __builtin_memcpy(&r, &v, 16);
+  return r;
+}
 
 __device__ __forceinline__ long long pack_key(float v, unsigned idx) {
   if (v == 0.0f) v = 0.0f;  // canonical +0 so that -0 and +0 tie on index
@@ -17,6 +45,128 @@ __device__ __forceinline__ long long pack_key(float v, unsigned idx) {
 __device__ __forceinline__ float key_value(long long key) {
   const int s = (int)(key >> 32);
   return __int_as_float(s >= 0 ? s : (s ^ 0x7FFFFFFF));
+}
+
+// ---- the arg-best contract ------------------------------------------------------------
+// A running record is (b1 best score, b2 runner-up score, i1 row of the best; i1 = INT_MAX
+// while empty).  Merge another record of the same probe over disjoint rows into it: the
+// lower score wins, equal scores go to the lower row (np.argmin / np.argmax order).
+__device__ __forceinline__ void top2_merge(float& b1, float& b2, int& i1, float ob1, float ob2, int oi1) {
+  const bool other = ob1 < b1 || (ob1 == b1 && oi1 < i1);
+  const float lose = other ? b1 : ob1;
+  b2 = fminf(fminf(b2, ob2), lose);
+  // selects, not `if (other) { b1 = ob1; i1 = oi1; }`: through the references that form
+  // becomes exec-masked branches (+23 instructions in search_kernel's epilogue, 3 more
+  // spilled VGPRs in search_kernel<128, cosine>)
+  b1 = other ? ob1 : b1;
+  i1 = other ? oi1 : i1;
+}
+// Publish a chunk's record for one probe at chunk_base + slot, chunk_base = chunk * bpad
+// (reduce_kernel takes the min key over chunks and the min runner-up); an empty chunk
+// publishes no candidate.  Base and slot are separate arguments, added once per store as the
+// kernels always wrote it: with the sum passed in, the compiler shares the two helpers'
+// stores and the kernels' prologues and epilogues change.
+__device__ __forceinline__ void top2_store(const SearchWs& ws, int64_t chunk_base, int64_t slot, float b1, float b2,
+                                           int i1) {
+  ws.part_key[chunk_base + slot] = i1 == INT_MAX ? LLONG_MAX : pack_key(b1, (unsigned)i1);
+  ws.part_b2[chunk_base + slot] = b2;
+}
+__device__ __forceinline__ void top2_store_empty(const SearchWs& ws, int64_t chunk_base, int64_t slot) {
+  ws.part_key[chunk_base + slot] = LLONG_MAX;
+  ws.part_b2[chunk_base + slot] = __builtin_inff();
+}
+// COLLECT pass: queue row row_base + row_off for the fp64 resolution of queued probe `slot`
+// when its fp32 score is within the slot's threshold (resolve_kernel re-scans the gallery
+// past kCandMax).  The row comes in two parts so that it is formed only on a hit: passed as
+// one value, the 16 rows of an unrolled block are computed ahead of the compares and cost up
+// to 10 VGPRs (search_kernel<64, .., COLLECT>: 96 -> 106).
+__device__ __forceinline__ void collect_hit(const SearchWs& ws, int64_t slot, float thr, float score, int row_base,
+                                            int row_off) {
+  if (score <= thr) {
+    const int pos = atomicAdd(&ws.cand_cnt[slot], 1);
+    if (pos < kCandMax) ws.cand[slot * kCandMax + pos] = row_base + row_off;
+  }
+}
+// the slot's COLLECT threshold (main pass, or a slot past the queue: nothing qualifies)
+template <bool COLLECT>
+__device__ __forceinline__ float collect_threshold(const SearchWs& ws, int64_t slot, int n_amb) {
+  float thr = -__builtin_inff();
+  if constexpr (COLLECT) {
+    if (slot < n_amb) thr = ws.thr[slot];
+  }
+  return thr;
+}
+
+// ---- work items -----------------------------------------------------------------------
+// Tiles [t0, t1) of gallery chunk gc (ROWS rows per tile); t0 >= t1 for an empty chunk.
+template <int ROWS>
+__device__ __forceinline__ void chunk_range(int64_t n, int gc, int tiles_per_chunk, int64_t& t0, int64_t& t1) {
+  const int64_t tiles_total = (n + ROWS - 1) / ROWS;
+  t0 = (int64_t)gc * tiles_per_chunk;
+  t1 = t0 + tiles_per_chunk < tiles_total ? t0 + tiles_per_chunk : tiles_total;
+}
+// Collect pass: n_chunks is the collect plan's chunk count; the grid strides over the
+// (chunk, queued probe tile) items, so a handful of queued probes still spread over the
+// whole grid instead of one workgroup per main-pass chunk.  body(chunk, probe tile, n_amb).
+template <int PROBE_TILE, typename Body>
+__device__ __forceinline__ void collect_items(const SearchWs& ws, int n_chunks, const Body& body) {
+  const int n_amb = *ws.amb_count;
+  const int items = ((n_amb + PROBE_TILE - 1) / PROBE_TILE) * n_chunks;
+  for (int item = blockIdx.x; item < items; item += gridDim.x) body(item % n_chunks, item / n_chunks, n_amb);
+}
+// Wide kernels' main pass: (chunk, probe tile) blocks of cblk x pblk, one block per XCD run
+// of xcd_lin() (see search_plan); block_deal_ok is the host's check that this is a bijection.
+__device__ __forceinline__ void xcd_block_deal(int lin, int n_ptiles, int pblk, int cblk, int& gc, int& pt) {
+  const int bsz = cblk * pblk;
+  const int blk = lin / bsz, r = lin - blk * bsz;
+  const int nbp = n_ptiles / pblk;
+  gc = (blk / nbp) * cblk + r / pblk;
+  pt = (blk % nbp) * pblk + r % pblk;
+}
+inline bool block_deal_ok(const SearchPlan& pl, int probe_tile, int64_t bpad) {
+  const int items = pl.nchunks * pl.n_ptiles;
+  return pl.n_ptiles % pl.pblk == 0 && pl.nchunks % pl.cblk == 0 && items % 8 == 0 &&
+         (items / 8) % (pl.cblk * pl.pblk) == 0 && bpad % probe_tile == 0;
+}
+
+// ---- wide kernels: DMA geometry of a 32-k slice -----------------------------------------
+// A slice row is 128 B = eight 16-B chunks; a slice is pieces of 1 KiB (8 rows); wave w
+// issues pieces 4w .. 4w + 3 of the gallery slice and of the probe slice.  Lane l of piece
+// j carries row 8j + (l >> 3), physical chunk l & 7, which holds logical chunk
+// (l & 7) ^ ((row >> 1) & SWZ) = (l & 7) ^ ((4 jj + (l >> 4)) & SWZ).  The per-lane byte
+// offsets are fixed for the whole sweep (SGPR-base DMA: the slice's base address is
+// wave-uniform), so a slice's DMAs cost no per-lane address arithmetic.  COLLECT: the probe
+// rows are those of the queued slots.
+// Also written out, with SWZ = 5, in search_wide16_kernel (ef_search_wide.hip; the reason is
+// given there): keep the two in step.
+template <int SWZ, int PROBE_TILE, bool COLLECT>
+__device__ __forceinline__ void wide_dma_offsets(const SearchWs& ws, int pt, int wave, int lane, int n_amb,
+                                                 int row_bytes, unsigned (&goff)[4], unsigned (&qoff)[4]) {
+  const int prow = lane >> 3;
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+    const int slot = pt * PROBE_TILE + (wave * 4 + jj) * 8 + prow;
+    int qrow = slot;
+    if constexpr (COLLECT) qrow = slot < n_amb ? ws.amb_list[slot] : 0;
+    const unsigned lch16 = (unsigned)(((lane & 7) ^ ((4 * jj + (lane >> 4)) & SWZ)) * 16);
+    goff[jj] = (unsigned)((wave * 4 + jj) * 8 + prow) * row_bytes + lch16;
+    qoff[jj] = (unsigned)qrow * row_bytes + lch16;
+  }
+}
+// rows of tile t that exist (ROWS except in the tail tile)
+template <int ROWS>
+__device__ __forceinline__ int tile_rows(int64_t n, int64_t t) {
+  return (int)((n - t * ROWS) < ROWS ? (n - t * ROWS) : ROWS);
+}
+// Tail tile: a gallery piece's rows past the end re-read the last row (masked later).
+// go = row * row_bytes + byte offset inside the row; nrem = tile_rows().
+template <int ROWS>
+__device__ __forceinline__ unsigned wide_tail_clamp(unsigned go, int nrem, int row_bytes) {
+  if (nrem < ROWS) {
+    const unsigned row = go / row_bytes;
+    go = (row < (unsigned)nrem ? row : (unsigned)(nrem - 1)) * row_bytes + go % row_bytes;
+  }
+  return go;
 }
 
 
@@ -70,10 +220,13 @@ constexpr int kWide3ProbeTile = 256;  // split-bf16 wide kernel: probes per work
 hipError_t launch_search_wide(hipStream_t s, int kp, int metric, bool collect, int s3, const SearchPlan& pl,
                               const float* qpad, const float* G, const float* aux, int64_t n, int64_t bpad,
                               const SearchWs& ws);
-// the single-bf16 screen's main pass with the gallery operand in VGPRs (ef_search_screen.hip;
-// kh = k / 2 in {128, 256}); screen_vg_enabled: the product default (diagnostic A/B knob)
+#ifdef EF_DIAGNOSTICS
+// Diagnostic builds only (ef_search_screen.hip is not part of the product library): the
+// single-bf16 screen's main pass with the gallery operand in VGPRs (kh = k / 2 in
+// {128, 256}); screen_vg_enabled: the EF_SCREEN_VG=1 A/B knob
 bool screen_vg_enabled();
 hipError_t launch_search_screen(hipStream_t s, int kh, int metric, const SearchPlan& pl, const float* q1,
                                 const float* G1, const float* aux, int64_t n, int64_t bpad, const SearchWs& ws);
+#endif
 
 }  // namespace ef

@@ -26,16 +26,20 @@
 //     VMEM in the loop, so it never waits for all of them.
 // The per-slice barrier stays (the probe ring's slots are recycled), but nothing waits for
 // a DMA issued less than two slices earlier.
+//
+// Diagnostic builds only (make diag): measured slower than search_wide16_kernel (see the
+// note above screen_vg_enabled), so the product library does not contain it.
+#ifndef EF_DIAGNOSTICS
+#error "ef_search_screen.hip belongs to the diagnostic build only (make diag)"
+#endif
 #include "ef_search_common.hpp"
 
-#include <climits>
+#include <cstdlib>
 
 namespace ef {
 
 namespace {
 
-typedef short bf16x8s __attribute__((ext_vector_type(8)));
-typedef float f32x4s __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
 
 constexpr int SR = kWide3RowTile;    // gallery rows per tile
@@ -44,22 +48,6 @@ constexpr int SBK = 32;              // floats (64 bf16) per slice row
 constexpr int SSL = SP * SBK;        // floats per probe slice (32 KiB)
 constexpr int RING = 4;              // probe slices in LDS
 constexpr int AUXW = 64;             // aux floats per wave and slot (32 rows, lanes 32-63 duplicate)
-
-__device__ __forceinline__ float min3f(float a, float b, float c) {
-  float r;
-  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ bf16x8s as_bf16(const u32x4s& v) {
-  bf16x8s r;
-  __builtin_memcpy(&r, &v, 16);
-  return r;
-}
-__device__ __forceinline__ bf16x8s as_bf16(const float4& v) {
-  bf16x8s r;
-  __builtin_memcpy(&r, &v, 16);
-  return r;
-}
 
 // 16 B at sbase + voff and at + 64 into two VGPR quads (vmcnt += 2)
 __device__ __forceinline__ void gload32(u32x4s& lo, u32x4s& hi, unsigned voff, unsigned long long sbase) {
@@ -90,29 +78,21 @@ __global__ __launch_bounds__(512, 1) void search_screen_kernel(const float* __re
   __shared__ __attribute__((aligned(16))) float smem[RING * SSL + RING * 8 * AUXW];
 
   // the XCD deal of search_wide16_kernel's main pass
-  const int total = gridDim.x;  // host guarantees total % 8 == 0
-  const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
-  const int bsz = cblk * pblk;
-  const int blk = lin / bsz, rr = lin - blk * bsz;
-  const int nbp = n_ptiles / pblk;
-  const int gc = (blk / nbp) * cblk + rr / pblk, pt = (blk % nbp) * pblk + rr % pblk;
+  int gc, pt;
+  xcd_block_deal(xcd_lin(), n_ptiles, pblk, cblk, gc, pt);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qd = lane >> 4, r16 = lane & 15;
 
-  const int64_t tiles_total = (n + SR - 1) / SR;
-  const int64_t t0 = (int64_t)gc * tiles_per_chunk;
-  const int64_t t1 = t0 + tiles_per_chunk < tiles_total ? t0 + tiles_per_chunk : tiles_total;
+  int64_t t0, t1;
+  chunk_range<SR>(n, gc, tiles_per_chunk, t0, t1);
   const int64_t prow0 = (int64_t)pt * SP;  // this workgroup's first probe slot
 
   const float INF = __builtin_inff();
   if (t0 >= t1) {
-    if (tid < SP) {
-      ws.part_key[(int64_t)gc * bpad + prow0 + tid] = LLONG_MAX;
-      ws.part_b2[(int64_t)gc * bpad + prow0 + tid] = INF;
-    }
+    if (tid < SP) top2_store_empty(ws, (int64_t)gc * bpad, prow0 + tid);
     return;
   }
   const int n_it = (int)((t1 - t0) * NS);  // host checks the 32-bit range
@@ -163,10 +143,10 @@ __global__ __launch_bounds__(512, 1) void search_screen_kernel(const float* __re
 
   // 8 values of probe block pb (rows rowbase + 16 rb + 4 qd + r, increasing with (rb, r):
   // first minimum in lane) into the running (best, index, runner-up)
-  auto consume = [&](const f32x4s& v0, const f32x4s& v1, int rowbase, int pb) {
-    float mn = min3f(v0[0], v0[1], v0[2]);
-    mn = min3f(mn, v0[3], v1[0]);
-    mn = min3f(mn, v1[1], v1[2]);
+  auto consume = [&](const f32x4& v0, const f32x4& v1, int rowbase, int pb) {
+    float mn = min3_raw(v0[0], v0[1], v0[2]);
+    mn = min3_raw(mn, v0[3], v1[0]);
+    mn = min3_raw(mn, v1[1], v1[2]);
     mn = fminf(mn, v1[3]);
     if (!__any(mn < b2[pb])) return;  // exact skip: no value here can change the top-2
     float m1 = INF, m2 = INF;
@@ -185,7 +165,7 @@ __global__ __launch_bounds__(512, 1) void search_screen_kernel(const float* __re
     b1[pb] = lt ? m1 : b1[pb];
   };
 
-  f32x4s acc[2][16];
+  f32x4 acc[2][16];
   const int sw = ((r16 >> 1) & 3) << 1;  // s(row) of every probe this lane reads
   const int ph = (qd ^ sw) * 4, pl = ((4 + qd) ^ sw) * 4;
 
@@ -202,22 +182,22 @@ __global__ __launch_bounds__(512, 1) void search_screen_kernel(const float* __re
       // L2: start from -|g|^2 / 2 and accumulate q.g (-2 acc = |g|^2 - 2 q.g); cosine: 0
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
-        f32x4s a = {0.f, 0.f, 0.f, 0.f};
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
         if constexpr (METRIC == EF_METRIC_L2) {
           const float4 x = *reinterpret_cast<const float4*>(sAux + 16 * rb + 4 * qd);
-          a = f32x4s{-0.5f * x.x, -0.5f * x.y, -0.5f * x.z, -0.5f * x.w};
+          a = f32x4{-0.5f * x.x, -0.5f * x.y, -0.5f * x.z, -0.5f * x.w};
         }
 #pragma unroll
         for (int pb = 0; pb < 16; ++pb) acc[rb][pb] = a;
       }
     }
     const float* sq = smem + slot * SSL + r16 * SBK;
-    const bf16x8s a00 = as_bf16(cur.g[0]), a01 = as_bf16(cur.g[1]);
-    const bf16x8s a10 = as_bf16(cur.g[2]), a11 = as_bf16(cur.g[3]);
+    const bf16x8 a00 = as_bf16x8(cur.g[0]), a01 = as_bf16x8(cur.g[1]);
+    const bf16x8 a10 = as_bf16x8(cur.g[2]), a11 = as_bf16x8(cur.g[3]);
 #pragma unroll
     for (int pb = 0; pb < 16; ++pb) {
-      const bf16x8s bh = as_bf16(*reinterpret_cast<const float4*>(sq + 16 * pb * SBK + ph));
-      const bf16x8s bl = as_bf16(*reinterpret_cast<const float4*>(sq + 16 * pb * SBK + pl));
+      const bf16x8 bh = as_bf16x8(*reinterpret_cast<const float4*>(sq + 16 * pb * SBK + ph));
+      const bf16x8 bl = as_bf16x8(*reinterpret_cast<const float4*>(sq + 16 * pb * SBK + pl));
       acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a00, bh, acc[0][pb], 0, 0, 0);
       acc[1][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a10, bh, acc[1][pb], 0, 0, 0);
       acc[0][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a01, bl, acc[0][pb], 0, 0, 0);
@@ -280,10 +260,7 @@ __global__ __launch_bounds__(512, 1) void search_screen_kernel(const float* __re
       const float ob1 = __shfl_xor(b1[pb], off);
       const int oi1 = __shfl_xor(i1[pb], off);
       const float ob2 = __shfl_xor(b2[pb], off);
-      const bool other = ob1 < b1[pb] || (ob1 == b1[pb] && oi1 < i1[pb]);
-      const float lose = other ? b1[pb] : ob1;
-      b2[pb] = fminf(fminf(b2[pb], ob2), lose);
-      if (other) { b1[pb] = ob1; i1[pb] = oi1; }
+      top2_merge(b1[pb], b2[pb], i1[pb], ob1, ob2, oi1);
     }
   }
   float* xb = smem;  // [8 waves][256 probes] x (b1, b2, i1)
@@ -302,16 +279,9 @@ __global__ __launch_bounds__(512, 1) void search_screen_kernel(const float* __re
     int I1 = __float_as_int(xb[tid * 3 + 2]);
     for (int w = 1; w < 8; ++w) {
       const int o = (w * SP + tid) * 3;
-      const float ob1 = xb[o], ob2 = xb[o + 1];
-      const int oi1 = __float_as_int(xb[o + 2]);
-      const bool other = ob1 < B1 || (ob1 == B1 && oi1 < I1);
-      const float lose = other ? B1 : ob1;
-      B2 = fminf(fminf(B2, ob2), lose);
-      if (other) { B1 = ob1; I1 = oi1; }
+      top2_merge(B1, B2, I1, xb[o], xb[o + 1], __float_as_int(xb[o + 2]));
     }
-    const int64_t po = (int64_t)gc * bpad + prow0 + tid;
-    ws.part_key[po] = I1 == INT_MAX ? LLONG_MAX : pack_key(B1, (unsigned)I1);
-    ws.part_b2[po] = B2;
+    top2_store(ws, (int64_t)gc * bpad, prow0 + tid, B1, B2, I1);
   }
 }
 
@@ -325,10 +295,8 @@ __global__ __launch_bounds__(512, 1) void search_screen_kernel(const float* __re
 // 37 % against 32 % of their cycles (one slice of register prefetch is all that fits beside
 // the 128 accumulators and 48 registers of running top-2 state), MFMA busy 42 % against 55 %.
 // Not the product path: kept for A/B in diagnostic builds (EF_SCREEN_VG=1).
-bool screen_vg_enabled() {
-#ifdef EF_DIAGNOSTICS  // EF_SCREEN_VG=1: this kernel for the screen's main pass (A/B)
+bool screen_vg_enabled() {  // EF_SCREEN_VG=1: this kernel for the screen's main pass (A/B)
   if (const char* e = getenv("EF_SCREEN_VG")) return atoi(e) != 0;
-#endif
   return false;
 }
 
@@ -337,9 +305,7 @@ bool screen_vg_enabled() {
 hipError_t launch_search_screen(hipStream_t s, int kh, int metric, const SearchPlan& pl, const float* q1,
                                 const float* G1, const float* aux, int64_t n, int64_t bpad, const SearchWs& ws) {
   const dim3 grid((unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
-  if (pl.n_ptiles % pl.pblk != 0 || pl.nchunks % pl.cblk != 0 || (pl.nchunks * pl.n_ptiles) % 8 != 0 ||
-      (pl.nchunks * pl.n_ptiles / 8) % (pl.cblk * pl.pblk) != 0 || bpad % SP != 0)
-    return hipErrorInvalidValue;
+  if (!block_deal_ok(pl, SP, bpad)) return hipErrorInvalidValue;
   // 32-bit byte offsets: probe rows and the gallery (G1 rows * kh * 4 < 2^32)
   if (bpad * (int64_t)kh * 4 >= ((int64_t)1 << 32) || n * (int64_t)kh * 4 >= ((int64_t)1 << 32) ||
       (int64_t)pl.tiles_per_chunk * (kh / SBK) >= ((int64_t)1 << 31))

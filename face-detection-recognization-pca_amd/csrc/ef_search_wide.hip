@@ -19,53 +19,20 @@
 #include "ef_search_common.hpp"
 
 #include <algorithm>
-#include <climits>
 
 namespace ef {
 
-// Diagnostic builds only (timing, wrong results): EF_WIDE_ABL 1 = no per-slice barrier,
-// 2 = no arg-best epilogue, 3 = no DMA after the first slices.
-#ifndef EF_WIDE_ABL
-#define EF_WIDE_ABL 0
-#endif
-#ifndef EF_WIDE_STAGGER  // wide16: n > 0 = the upper four waves issue their DMA after A block n - 1
-#define EF_WIDE_STAGGER 2  // measured: 8.96 -> 8.76 ms at C5 (1: 8.83, 4: 9.03, 6: 9.36)
-#endif
-#ifndef EF_WIDE_INTERLEAVE
-#define EF_WIDE_INTERLEAVE 0
-#endif
-#ifndef EF_WIDE_ROLES  // wide16: 1 = waves 0-3 issue every gallery DMA piece, 4-7 every probe piece (experiment)
-#define EF_WIDE_ROLES 0
-#endif
-#ifndef EF_WIDE_SERP  // wide16: 1 = serpentine k-slice order over a sweep's tiles (experiment)
-#define EF_WIDE_SERP 1  // with EF_WIDE3_PB 8: C5 HBM fetch 12.0 -> 8.1 GB per launch, same time (profiles/r04/c5_hbm_ab.txt)
-#endif
+// search_wide16_kernel: the upper four waves issue their slice DMA after A block
+// kWideStagger - 1 (0 would be: with the lower four, at the slice's start).
+// Measured: 8.96 -> 8.76 ms at C5 (1: 8.83, 4: 9.03, 6: 9.36)
+constexpr int kWideStagger = 2;
+static_assert(kWideStagger >= 1 && kWideStagger <= 8, "an A block of the slice");
 
 constexpr int WR = kWideRowTile;    // gallery rows per tile
 constexpr int WP = kWideProbeTile;  // probes per workgroup
 constexpr int WBK = 32;             // k per slice
 constexpr int WSL = WR * WBK;       // floats per gallery slice (= per probe slice)
 static_assert(WR == 128 && WP == 128, "4 waves x 32 probes, 4 x 32-row blocks");
-
-typedef short bf16x8w __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// min of three floats as one v_min3_f32, without the compiler's IEEE-mode canonicalisation
-// of each input (scores are finite or +inf, never NaN)
-__device__ __forceinline__ float min3_raw(float a, float b, float c) {
-  float r;
-  asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ float max3_raw(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-__device__ __forceinline__ bf16x8w as_bf16x8w(const float4& v) {
-  bf16x8w r;
-  __builtin_memcpy(&r, &v, 16);
-  return r;
-}
 
 // Row geometry of a sweep: KP > 0 is a compile-time row length (256 | 512); KP = 0 takes
 // kp_rt, any multiple of 128 above 512 (full-rank per-person models, train-v5.py:539-545),
@@ -105,43 +72,21 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
   const int h = lane >> 5;
   const int c32 = lane & 31;
 
-  const int64_t tiles_total = (n + WR - 1) / WR;
-  const int64_t t0 = (int64_t)gc * tiles_per_chunk;
-  const int64_t t1 = t0 + tiles_per_chunk < tiles_total ? t0 + tiles_per_chunk : tiles_total;
+  int64_t t0, t1;
+  chunk_range<WR>(n, gc, tiles_per_chunk, t0, t1);
   const int64_t s0 = (int64_t)pt * WP + wave * 32 + c32;  // this lane's probe slot
 
   if (t0 >= t1) {
     if constexpr (!COLLECT) {
-      if (h == 0) {
-        ws.part_key[(int64_t)gc * bpad + s0] = LLONG_MAX;
-        ws.part_b2[(int64_t)gc * bpad + s0] = __builtin_inff();
-      }
+      if (h == 0) top2_store_empty(ws, (int64_t)gc * bpad, s0);
     }
     return;
   }
 
-  // DMA geometry: a slice is 16 pieces of 1 KiB (8 rows x 128 B); wave w issues pieces
-  // 4w..4w+3 of the gallery slice and of the probe slice.  Lane l of piece j carries
-  // row 8j + (l >> 3), physical 16-B chunk l & 7, which holds logical chunk
-  // (l & 7) ^ ((row >> 1) & 7) = (l & 7) ^ ((4 * jj + (l >> 4)) & 7).
-  // Per-lane byte offsets are fixed for the whole sweep (SGPR-base DMA: the slice's base
-  // address is wave-uniform), so a slice's 8 DMAs cost no per-lane address arithmetic.
-  const int prow = lane >> 3;
+  // DMA geometry (wide_dma_offsets): 16 pieces per slice and operand, swizzle (row >> 1) & 7
   unsigned goff[4], qoff[4];
-#pragma unroll
-  for (int jj = 0; jj < 4; ++jj) {
-    const int slot = pt * WP + (wave * 4 + jj) * 8 + prow;
-    int qrow = slot;
-    if constexpr (COLLECT) qrow = slot < n_amb ? ws.amb_list[slot] : 0;
-    const unsigned lch16 = (unsigned)(((lane & 7) ^ ((4 * jj + (lane >> 4)) & 7)) * 16);
-    goff[jj] = (unsigned)((wave * 4 + jj) * 8 + prow) * (geo.kp * 4) + lch16;
-    qoff[jj] = (unsigned)qrow * (geo.kp * 4) + lch16;
-  }
-  const unsigned aoff = (unsigned)lane * 4;
-  float thr = -__builtin_inff();
-  if constexpr (COLLECT) {
-    if (s0 < n_amb) thr = ws.thr[s0];
-  }
+  wide_dma_offsets<7, WP, COLLECT>(ws, pt, wave, lane, n_amb, geo.kp * 4, goff, qoff);
+  const float thr = collect_threshold<COLLECT>(ws, s0, n_amb);
   // settle these loads before the loop (a loop-merged wait would drain the LDS-DMA)
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) asm volatile("" ::"v"(qoff[jj]));
@@ -150,19 +95,15 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
   const unsigned lds_base = lds_addr(smem);
   const int64_t n_it = (t1 - t0) * NS;
   // DMA of slice it into buffer buf, piece jj of this wave's four (+ the tile's aux).
+  const unsigned aoff = (unsigned)lane * 4;
   auto issue_piece = [&](int64_t it, int buf, int jj) {
     const int64_t t = t0 + geo.tile(it);
     const int sl = geo.slice(it);
-    const int nrem = (int)((n - t * WR) < WR ? (n - t * WR) : WR);
+    const int nrem = tile_rows<WR>(n, t);
     const unsigned long long gb = (unsigned long long)(size_t)(G + t * WR * geo.kp + sl * WBK);
     const unsigned long long qb = (unsigned long long)(size_t)(qpad + sl * WBK);
     const int j = wave * 4 + jj;
-    unsigned go = goff[jj];
-    if (nrem < WR) {  // tail tile: rows past the end re-read the last row (masked later)
-      const unsigned row = go / (geo.kp * 4);
-      go = (row < (unsigned)nrem ? row : (unsigned)(nrem - 1)) * (geo.kp * 4) + go % (geo.kp * 4);
-    }
-    glds16s(go, gb, lds_base + (unsigned)((buf * 2 * WSL + j * 256) * 4));
+    glds16s(wide_tail_clamp<WR>(goff[jj], nrem, geo.kp * 4), gb, lds_base + (unsigned)((buf * 2 * WSL + j * 256) * 4));
     glds16s(qoff[jj], qb, lds_base + (unsigned)((buf * 2 * WSL + WSL + j * 256) * 4));
     if (jj == 3 && sl == 0 && wave == 0) {  // the tile's ||g||^2 (L2) or 1/||g|| (cosine)
       const unsigned long long ab = (unsigned long long)(size_t)(aux + t * WR);
@@ -185,12 +126,7 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
   auto consume = [&](const f32x16& v, int rowbase) {
     if constexpr (COLLECT) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (v[r] <= thr) {
-          const int pos = atomicAdd(&ws.cand_cnt[s0], 1);
-          if (pos < kCandMax) ws.cand[s0 * kCandMax + pos] = rowbase + (r & 3) + 8 * (r >> 2) + 4 * h;
-        }
-      }
+      for (int r = 0; r < 16; ++r) collect_hit(ws, s0, thr, v[r], rowbase, (r & 3) + 8 * (r >> 2) + 4 * h);
     } else {
       // uniform skip of blocks that cannot change the running top-2 (ef_search.hip consume)
       float mn = v[0];
@@ -223,14 +159,7 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
     const int buf = (int)(it & 1);
     const int sl = geo.slice(it);
     const float* const sAux = smem + 4 * WSL + (int)(geo.tile(it) & 1) * WR;
-#if EF_WIDE_INTERLEAVE == 0
-#if EF_WIDE_ABL == 3
-    if (it + 1 < 2)
-#else
-    if (it + 1 < n_it)
-#endif
-      issue(it + 1, buf ^ 1);  // lands under this slice's MFMAs
-#endif
+    if (it + 1 < n_it) issue(it + 1, buf ^ 1);  // lands under this slice's MFMAs
     if (sl == 0) {
       // L2: start from -||g||^2 / 2 and accumulate q.g, so that -2 acc = ||g||^2 - 2 q.g
       // with the rounding of the chain scaled exactly by -2.  Cosine: start from 0.
@@ -266,11 +195,6 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
       for (int rb = 0; rb < 4; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[rb].z, bq.z, acc[rb], 0, 0, 0);
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb) acc[rb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[rb].w, bq.w, acc[rb], 0, 0, 0);
-#if EF_WIDE_INTERLEAVE
-      // one DMA piece pair of slice it+1 per 16 MFMAs (buffer buf^1 was released by the
-      // previous slice's barrier)
-      if (it + 1 < n_it) issue_piece(it + 1, buf ^ 1, j);
-#endif
     }
     if (sl == NS - 1) {
       const int64_t t = t0 + geo.tile(it);
@@ -296,50 +220,27 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
           for (int r = 0; r < 16; ++r)
             if (tbase + rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= n) acc[rb][r] = INF;
         }
-#if EF_WIDE_ABL == 2
-        b1 = fminf(b1, acc[rb][0]);
-        (void)tbase;
-#else
         consume(acc[rb], tbase + rb * 32);  // blocks in row order (tie rule)
-#endif
       }
     }
-#if EF_WIDE_ABL != 1
     dma_wait_all();
     __syncthreads();  // slice it+1 landed; everyone is done reading buffer buf
-#endif
   }
 
   if constexpr (!COLLECT) {
     const float ob1 = __shfl_xor(b1, 32);
     const int oi1 = __shfl_xor(i1, 32);
     const float ob2 = __shfl_xor(b2, 32);
-    const bool other = ob1 < b1 || (ob1 == b1 && oi1 < i1);
-    const float lose = other ? b1 : ob1;
-    b2 = fminf(fminf(b2, ob2), lose);
-    if (other) { b1 = ob1; i1 = oi1; }
-    if (h == 0) {
-      const int64_t o = (int64_t)gc * bpad + s0;
-      ws.part_key[o] = i1 == INT_MAX ? LLONG_MAX : pack_key(b1, (unsigned)i1);
-      ws.part_b2[o] = b2;
-    }
+    top2_merge(b1, b2, i1, ob1, ob2, oi1);
+    if (h == 0) top2_store(ws, (int64_t)gc * bpad, s0, b1, b2, i1);
   }
   };  // body
   if constexpr (COLLECT) {
-    // collect pass: n_ptiles carries the collect plan's chunk count; the grid strides over
-    // the (chunk, queued probe tile) items, so a handful of queued probes still spread over
-    // the whole grid instead of one workgroup per main-pass chunk
-    const int n_amb = *ws.amb_count;
-    const int items = ((n_amb + 128 - 1) / 128) * n_ptiles;
-    for (int item = blockIdx.x; item < items; item += gridDim.x) body(item % n_ptiles, item / n_ptiles, n_amb);
+    collect_items<WP>(ws, n_ptiles, body);  // n_ptiles carries the collect plan's chunk count
   } else {
-    const int total = gridDim.x;  // host guarantees total % 8 == 0
-    const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
-    // (chunk, probe tile) blocks of cblk x pblk, one block per XCD (see search_plan)
-    const int bsz = cblk * pblk;
-    const int blk = lin / bsz, r = lin - blk * bsz;
-    const int nbp = n_ptiles / pblk;
-    body((blk / nbp) * cblk + r / pblk, (blk % nbp) * pblk + r % pblk, 0);
+    int gc, pt;
+    xcd_block_deal(xcd_lin(), n_ptiles, pblk, cblk, gc, pt);
+    body(gc, pt, 0);
   }
 }
 
@@ -375,9 +276,8 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
   const int c32 = lane & 31;
   const int pg = wave & 3, rh = wave >> 2;  // probe group (64 probes), row half (128 rows)
 
-  const int64_t tiles_total = (n + W3R - 1) / W3R;
-  const int64_t t0 = (int64_t)gc * tiles_per_chunk;
-  const int64_t t1 = t0 + tiles_per_chunk < tiles_total ? t0 + tiles_per_chunk : tiles_total;
+  int64_t t0, t1;
+  chunk_range<W3R>(n, gc, tiles_per_chunk, t0, t1);
   int64_t sl0[2];  // this lane's probe slots
   sl0[0] = (int64_t)pt * W3P + 64 * pg + c32;
   sl0[1] = sl0[0] + 32;
@@ -386,34 +286,18 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
     if constexpr (!COLLECT) {
       if (h == 0 && rh == 0) {
 #pragma unroll
-        for (int pb = 0; pb < 2; ++pb) {
-          ws.part_key[(int64_t)gc * bpad + sl0[pb]] = LLONG_MAX;
-          ws.part_b2[(int64_t)gc * bpad + sl0[pb]] = __builtin_inff();
-        }
+        for (int pb = 0; pb < 2; ++pb) top2_store_empty(ws, (int64_t)gc * bpad, sl0[pb]);
       }
     }
     return;
   }
 
-  // DMA geometry (as search_wide_kernel): a slice is 32 pieces of 1 KiB (8 rows x 128 B)
-  // for the gallery and 32 for the probes; wave w issues pieces 4w..4w+3 of each.
-  const int prow = lane >> 3;
+  // DMA geometry (wide_dma_offsets): 32 pieces per slice and operand, swizzle (row >> 1) & 7
   unsigned goff[4], qoff[4];
+  wide_dma_offsets<7, W3P, COLLECT>(ws, pt, wave, lane, n_amb, geo.kp * 4, goff, qoff);
+  float thr[2];
 #pragma unroll
-  for (int jj = 0; jj < 4; ++jj) {
-    const int slot = pt * W3P + (wave * 4 + jj) * 8 + prow;
-    int qrow = slot;
-    if constexpr (COLLECT) qrow = slot < n_amb ? ws.amb_list[slot] : 0;
-    const unsigned lch16 = (unsigned)(((lane & 7) ^ ((4 * jj + (lane >> 4)) & 7)) * 16);
-    goff[jj] = (unsigned)((wave * 4 + jj) * 8 + prow) * (geo.kp * 4) + lch16;
-    qoff[jj] = (unsigned)qrow * (geo.kp * 4) + lch16;
-  }
-  float thr[2] = {-__builtin_inff(), -__builtin_inff()};
-  if constexpr (COLLECT) {
-#pragma unroll
-    for (int pb = 0; pb < 2; ++pb)
-      if (sl0[pb] < n_amb) thr[pb] = ws.thr[sl0[pb]];
-  }
+  for (int pb = 0; pb < 2; ++pb) thr[pb] = collect_threshold<COLLECT>(ws, sl0[pb], n_amb);
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) asm volatile("" ::"v"(qoff[jj]));
   asm volatile("" ::"v"(thr[0]), "v"(thr[1]));
@@ -423,18 +307,13 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
   auto issue = [&](int64_t it, int buf) {
     const int64_t t = t0 + geo.tile(it);
     const int sl = geo.slice(it);
-    const int nrem = (int)((n - t * W3R) < W3R ? (n - t * W3R) : W3R);
+    const int nrem = tile_rows<W3R>(n, t);
     const unsigned long long gb = (unsigned long long)(size_t)(G3 + t * W3R * geo.kp + sl * WBK);
     const unsigned long long qb = (unsigned long long)(size_t)(q3 + sl * WBK);
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int j = wave * 4 + jj;
-      unsigned go = goff[jj];
-      if (nrem < W3R) {  // tail tile: rows past the end re-read the last row (masked later)
-        const unsigned row = go / (geo.kp * 4);
-        go = (row < (unsigned)nrem ? row : (unsigned)(nrem - 1)) * (geo.kp * 4) + go % (geo.kp * 4);
-      }
-      glds16s(go, gb, lds_base + (unsigned)((buf * 2 * W3SL + j * 256) * 4));
+      glds16s(wide_tail_clamp<W3R>(goff[jj], nrem, geo.kp * 4), gb, lds_base + (unsigned)((buf * 2 * W3SL + j * 256) * 4));
       glds16s(qoff[jj], qb, lds_base + (unsigned)((buf * 2 * W3SL + W3SL + j * 256) * 4));
     }
     if (sl == 0 && wave == 0) {  // the tile's ||g||^2 (L2) or 1/||g|| (cosine)
@@ -454,12 +333,8 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
   auto consume = [&](const f32x16& v, int rowbase, int pb) {
     if constexpr (COLLECT) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (v[r] <= thr[pb]) {
-          const int pos = atomicAdd(&ws.cand_cnt[sl0[pb]], 1);
-          if (pos < kCandMax) ws.cand[sl0[pb] * kCandMax + pos] = rowbase + (r & 3) + 8 * (r >> 2) + 4 * h;
-        }
-      }
+      for (int r = 0; r < 16; ++r)
+        collect_hit(ws, sl0[pb], thr[pb], v[r], rowbase, (r & 3) + 8 * (r >> 2) + 4 * h);
     } else {
       float mn = v[0];
 #pragma unroll
@@ -491,12 +366,7 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
     const int buf = (int)(it & 1);
     const int sl = geo.slice(it);
     const float* const sAux = smem + 4 * W3SL + (int)(geo.tile(it) & 1) * W3R + 128 * rh;
-#if EF_WIDE_ABL == 3
-    if (it + 1 < 2)  // diagnostic builds only: no slice DMA after the first (results invalid)
-#else
-    if (it + 1 < n_it)
-#endif
-      issue(it + 1, buf ^ 1);  // lands under this slice's MFMAs
+    if (it + 1 < n_it) issue(it + 1, buf ^ 1);  // lands under this slice's MFMAs
     if (sl == 0) {
       // L2: start from -||g||^2 / 2 and accumulate q.g (-2 acc = ||g||^2 - 2 q.g); cosine: 0
 #pragma unroll
@@ -521,16 +391,16 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int ph = ((h * 4 + 2 * i) ^ sw) * 4, pl = ((h * 4 + 2 * i + 1) ^ sw) * 4;
-      bf16x8w bh[2], bl[2];
+      bf16x8 bh[2], bl[2];
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb) {
-        bh[pb] = as_bf16x8w(*reinterpret_cast<const float4*>(sq + pb * 32 * WBK + ph));
-        bl[pb] = as_bf16x8w(*reinterpret_cast<const float4*>(sq + pb * 32 * WBK + pl));
+        bh[pb] = as_bf16x8(*reinterpret_cast<const float4*>(sq + pb * 32 * WBK + ph));
+        bl[pb] = as_bf16x8(*reinterpret_cast<const float4*>(sq + pb * 32 * WBK + pl));
       }
 #pragma unroll
       for (int rb = 0; rb < 4; ++rb) {
-        const bf16x8w ah = as_bf16x8w(*reinterpret_cast<const float4*>(sg + rb * 32 * WBK + ph));
-        const bf16x8w al = as_bf16x8w(*reinterpret_cast<const float4*>(sg + rb * 32 * WBK + pl));
+        const bf16x8 ah = as_bf16x8(*reinterpret_cast<const float4*>(sg + rb * 32 * WBK + ph));
+        const bf16x8 al = as_bf16x8(*reinterpret_cast<const float4*>(sg + rb * 32 * WBK + pl));
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
           acc[rb][pb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[pb], acc[rb][pb], 0, 0, 0);
@@ -581,10 +451,7 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
       const float ob1 = __shfl_xor(b1[pb], 32);
       const int oi1 = __shfl_xor(i1[pb], 32);
       const float ob2 = __shfl_xor(b2[pb], 32);
-      const bool other = ob1 < b1[pb] || (ob1 == b1[pb] && oi1 < i1[pb]);
-      const float lose = other ? b1[pb] : ob1;
-      b2[pb] = fminf(fminf(b2[pb], ob2), lose);
-      if (other) { b1[pb] = ob1; i1[pb] = oi1; }
+      top2_merge(b1[pb], b2[pb], i1[pb], ob1, ob2, oi1);
       if (rh == 1 && h == 0) {
         const int o = ((pg * 2 + pb) * 32 + c32) * 3;
         xb[o] = b1[pb];
@@ -597,33 +464,18 @@ __global__ __launch_bounds__(512, 1) void search_wide3_kernel(
 #pragma unroll
       for (int pb = 0; pb < 2; ++pb) {
         const int o = ((pg * 2 + pb) * 32 + c32) * 3;
-        const float ob1 = xb[o], ob2 = xb[o + 1];
-        const int oi1 = __float_as_int(xb[o + 2]);
-        const bool other = ob1 < b1[pb] || (ob1 == b1[pb] && oi1 < i1[pb]);
-        const float lose = other ? b1[pb] : ob1;
-        b2[pb] = fminf(fminf(b2[pb], ob2), lose);
-        if (other) { b1[pb] = ob1; i1[pb] = oi1; }
-        const int64_t po = (int64_t)gc * bpad + sl0[pb];
-        ws.part_key[po] = i1[pb] == INT_MAX ? LLONG_MAX : pack_key(b1[pb], (unsigned)i1[pb]);
-        ws.part_b2[po] = b2[pb];
+        top2_merge(b1[pb], b2[pb], i1[pb], xb[o], xb[o + 1], __float_as_int(xb[o + 2]));
+        top2_store(ws, (int64_t)gc * bpad, sl0[pb], b1[pb], b2[pb], i1[pb]);
       }
     }
   }
   };  // body
   if constexpr (COLLECT) {
-    // collect pass: n_ptiles carries the collect plan's chunk count; the grid strides over
-    // the (chunk, queued probe tile) items, so a handful of queued probes still spread over
-    // the whole grid instead of one workgroup per main-pass chunk
-    const int n_amb = *ws.amb_count;
-    const int items = ((n_amb + 256 - 1) / 256) * n_ptiles;
-    for (int item = blockIdx.x; item < items; item += gridDim.x) body(item % n_ptiles, item / n_ptiles, n_amb);
+    collect_items<W3P>(ws, n_ptiles, body);  // n_ptiles carries the collect plan's chunk count
   } else {
-    const int total = gridDim.x;  // host guarantees total % 8 == 0
-    const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
-    const int bsz = cblk * pblk;
-    const int blk = lin / bsz, rr = lin - blk * bsz;
-    const int nbp = n_ptiles / pblk;
-    body((blk / nbp) * cblk + rr / pblk, (blk % nbp) * pblk + rr % pblk, 0);
+    int gc, pt;
+    xcd_block_deal(xcd_lin(), n_ptiles, pblk, cblk, gc, pt);
+    body(gc, pt, 0);
   }
 }
 
@@ -668,9 +520,8 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
   const int qd = lane >> 4, r16 = lane & 15;
   const int pg = wave & 3, rh = wave >> 2;
 
-  const int64_t tiles_total = (n + W3R - 1) / W3R;
-  const int64_t t0 = (int64_t)gc * tiles_per_chunk;
-  const int64_t t1 = t0 + tiles_per_chunk < tiles_total ? t0 + tiles_per_chunk : tiles_total;
+  int64_t t0, t1;
+  chunk_range<W3R>(n, gc, tiles_per_chunk, t0, t1);
   int64_t sl0[4];  // this lane's probe slots (probe 16 pb + r16 of the wave's 64)
 #pragma unroll
   for (int pb = 0; pb < 4; ++pb) sl0[pb] = (int64_t)pt * W3P + 64 * pg + 16 * pb + r16;
@@ -678,6 +529,9 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
   if (t0 >= t1) {
     if constexpr (!COLLECT) {
       if (qd == 0 && rh == 0) {
+        // top2_store_empty written out: with the helper every main-pass instantiation of this
+        // kernel spills two more SGPRs (5 -> 7 at <256, L2, main pass, HI1>, which sits at 256
+        // VGPRs with no slack)
 #pragma unroll
         for (int pb = 0; pb < 4; ++pb) {
           ws.part_key[(int64_t)gc * bpad + sl0[pb]] = LLONG_MAX;
@@ -688,32 +542,10 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
     return;
   }
 
-  // DMA geometry of search_wide3_kernel with this kernel's swizzle: lane l of piece j
-  // carries row 8 j + (l >> 3), physical chunk l & 7 = logical chunk (l & 7) ^ s(row),
-  // s(row) = (row >> 1) & 5 = (4 jj + (l >> 4)) & 5.
+  // DMA geometry of search_wide3_kernel with this kernel's swizzle s(row) = (row >> 1) & 5
+  // (wide_dma_offsets<5, ..> written out: through the helper the run-time-KP cosine COLLECT
+  // instantiations, already spilling at 256 VGPRs, spill two more VGPRs, 8 -> 10)
   const int prow = lane >> 3;
-#if EF_WIDE_ROLES
-  // split roles: waves 0-3 carry the 32 gallery pieces of a slice (8 each, issued at the
-  // slice's start: the gallery streams from HBM / MALL), waves 4-7 the 32 probe pieces
-  // (L2-resident, issued at the stagger point)
-  const bool gwave = wave < 4;
-  unsigned off[8];
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) {
-    const int j = (wave & 3) * 8 + jj;
-    const unsigned lch16 = (unsigned)(((lane & 7) ^ ((4 * jj + (lane >> 4)) & 5)) * 16);
-    if (gwave) {
-      off[jj] = (unsigned)(j * 8 + prow) * (geo.kp * 4) + lch16;
-    } else {
-      const int slot = pt * W3P + j * 8 + prow;
-      int qrow = slot;
-      if constexpr (COLLECT) qrow = slot < n_amb ? ws.amb_list[slot] : 0;
-      off[jj] = (unsigned)qrow * (geo.kp * 4) + lch16;
-    }
-  }
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) asm volatile("" ::"v"(off[jj]));
-#else
   unsigned goff[4], qoff[4];
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) {
@@ -726,13 +558,9 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
   }
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) asm volatile("" ::"v"(qoff[jj]));
-#endif
-  float thr[4] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-  if constexpr (COLLECT) {
+  float thr[4];
 #pragma unroll
-    for (int pb = 0; pb < 4; ++pb)
-      if (sl0[pb] < n_amb) thr[pb] = ws.thr[sl0[pb]];
-  }
+  for (int pb = 0; pb < 4; ++pb) thr[pb] = collect_threshold<COLLECT>(ws, sl0[pb], n_amb);
   asm volatile("" ::"v"(thr[0]), "v"(thr[1]), "v"(thr[2]), "v"(thr[3]));
 
   const unsigned lds_base = lds_addr(smem);
@@ -742,47 +570,25 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
   auto issue_piece = [&](int64_t it, int buf, int p) {
     const int64_t t = t0 + geo.tile(it);
     int sl = geo.slice(it);
-#if EF_WIDE_SERP
     // serpentine k order: odd tiles of the sweep walk the slices backwards, so the probe
-    // slices used last by one tile are the first the next tile re-reads (L2 reuse)
+    // slices used last by one tile are the first the next tile re-reads (L2 reuse).  With 8
+    // probe tiles per XCD block: C5 HBM fetch 12.0 -> 8.1 GB per launch, same time
+    // (profiles/r04/c5_hbm_ab.txt)
     if ((t - t0) & 1) sl = NS - 1 - sl;
-#endif
-#if EF_WIDE_ROLES
-    const int jj = p, j = (wave & 3) * 8 + jj;
-    if (gwave) {
-      const int nrem = (int)((n - t * W3R) < W3R ? (n - t * W3R) : W3R);
-      const unsigned long long gb = (unsigned long long)(size_t)(G3 + t * W3R * geo.kp + sl * WBK);
-      unsigned go = off[jj];
-      if (nrem < W3R) {  // tail tile: rows past the end re-read the last row (masked later)
-        const unsigned row = go / (geo.kp * 4);
-        go = (row < (unsigned)nrem ? row : (unsigned)(nrem - 1)) * (geo.kp * 4) + go % (geo.kp * 4);
-      }
-      glds16s(go, gb, lds_base + (unsigned)((buf * 2 * W3SL + j * 256) * 4));
-    } else {
-      const unsigned long long qb = (unsigned long long)(size_t)(q3 + sl * WBK);
-      glds16s(off[jj], qb, lds_base + (unsigned)((buf * 2 * W3SL + W3SL + j * 256) * 4));
-    }
-#else
     const int jj = p >> 1, j = wave * 4 + jj;
     if ((p & 1) == 0) {
-      const int nrem = (int)((n - t * W3R) < W3R ? (n - t * W3R) : W3R);
+      const int nrem = tile_rows<W3R>(n, t);
       const unsigned long long gb = (unsigned long long)(size_t)(G3 + t * W3R * geo.kp + sl * WBK);
-      unsigned go = goff[jj];
-      if (nrem < W3R) {  // tail tile: rows past the end re-read the last row (masked later)
-        const unsigned row = go / (geo.kp * 4);
-        go = (row < (unsigned)nrem ? row : (unsigned)(nrem - 1)) * (geo.kp * 4) + go % (geo.kp * 4);
-      }
-      glds16s(go, gb, lds_base + (unsigned)((buf * 2 * W3SL + j * 256) * 4));
+      glds16s(wide_tail_clamp<W3R>(goff[jj], nrem, geo.kp * 4), gb, lds_base + (unsigned)((buf * 2 * W3SL + j * 256) * 4));
     } else {
       const unsigned long long qb = (unsigned long long)(size_t)(q3 + sl * WBK);
       glds16s(qoff[jj], qb, lds_base + (unsigned)((buf * 2 * W3SL + W3SL + j * 256) * 4));
     }
-#endif
   };
   auto issue = [&](int64_t it, int buf) {
     const int64_t t = t0 + geo.tile(it);
     const int sl = geo.slice(it);
-    const int nrem = (int)((n - t * W3R) < W3R ? (n - t * W3R) : W3R);
+    const int nrem = tile_rows<W3R>(n, t);
 #pragma unroll
     for (int p = 0; p < 8; ++p) issue_piece(it, buf, p);
     if (sl == 0 && wave == 0) {  // the tile's ||g||^2 (L2) or 1/||g|| (cosine)
@@ -805,12 +611,7 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
 #pragma unroll
       for (int rb = 0; rb < 8; ++rb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (v[rb][r] <= thr[pb]) {
-            const int pos = atomicAdd(&ws.cand_cnt[sl0[pb]], 1);
-            if (pos < kCandMax) ws.cand[sl0[pb] * kCandMax + pos] = rowbase + 16 * rb + 4 * qd + r;
-          }
-        }
+        for (int r = 0; r < 4; ++r) collect_hit(ws, sl0[pb], thr[pb], v[rb][r], rowbase, 16 * rb + 4 * qd + r);
     } else {
       // L2: v holds the raw accumulators a (score -2 a, exact): the block's best score is
       // -2 max(a), so the skip test needs 16 v_max3 and one multiply instead of 32
@@ -860,18 +661,10 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
     const int buf = (int)(it & 1);
     const int sl = geo.slice(it);
     const float* const sAux = smem + 4 * W3SL + (int)(geo.tile(it) & 1) * W3R + 128 * rh;
-#if EF_WIDE_ABL == 3
-    const bool more = it + 1 < 2;  // diagnostic builds only: no slice DMA after the first (results invalid)
-#else
     const bool more = it + 1 < n_it;
-#endif
-#if EF_WIDE_STAGGER
-    // waves w and w + 4 share a SIMD: the upper four issue their DMA burst half-way through
-    // the slice, so each SIMD's MFMA pipe is fed by one wave while the other issues
+    // waves w and w + 4 share a SIMD: the upper four issue their DMA burst part-way through
+    // the slice (kWideStagger), so each SIMD's MFMA pipe is fed by one wave while the other issues
     if (more && wave < 4) issue(it + 1, buf ^ 1);
-#else
-    if (more) issue(it + 1, buf ^ 1);  // lands under this slice's MFMAs
-#endif
     if (sl == 0) {
       // L2: start from -||g||^2 / 2 and accumulate q.g (-2 acc = ||g||^2 - 2 q.g); cosine: 0
 #pragma unroll
@@ -887,16 +680,16 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
     }
     const float* sg = smem + buf * 2 * W3SL + (128 * rh + r16) * WBK;
     const float* sq = smem + buf * 2 * W3SL + W3SL + (64 * pg + r16) * WBK;
-    bf16x8w bh[4], bl[4];
+    bf16x8 bh[4], bl[4];
 #pragma unroll
     for (int pb = 0; pb < 4; ++pb) {
-      bh[pb] = as_bf16x8w(*reinterpret_cast<const float4*>(sq + 16 * pb * WBK + ph));
-      bl[pb] = as_bf16x8w(*reinterpret_cast<const float4*>(sq + 16 * pb * WBK + pl));
+      bh[pb] = as_bf16x8(*reinterpret_cast<const float4*>(sq + 16 * pb * WBK + ph));
+      bl[pb] = as_bf16x8(*reinterpret_cast<const float4*>(sq + 16 * pb * WBK + pl));
     }
 #pragma unroll
     for (int rb = 0; rb < 8; ++rb) {
-      const bf16x8w ah = as_bf16x8w(*reinterpret_cast<const float4*>(sg + 16 * rb * WBK + ph));
-      const bf16x8w al = as_bf16x8w(*reinterpret_cast<const float4*>(sg + 16 * rb * WBK + pl));
+      const bf16x8 ah = as_bf16x8(*reinterpret_cast<const float4*>(sg + 16 * rb * WBK + ph));
+      const bf16x8 al = as_bf16x8(*reinterpret_cast<const float4*>(sg + 16 * rb * WBK + pl));
 #pragma unroll
       for (int pb = 0; pb < 4; ++pb) {
         if constexpr (HI1) {  // k steps 0 and 1 of the 64-k slice
@@ -908,9 +701,7 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
           acc[rb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[pb], acc[rb][pb], 0, 0, 0);
         }
       }
-#if EF_WIDE_STAGGER
-      if (rb == EF_WIDE_STAGGER - 1 && more && wave >= 4) issue(it + 1, buf ^ 1);
-#endif
+      if (rb == kWideStagger - 1 && more && wave >= 4) issue(it + 1, buf ^ 1);
     }
     if (sl == NS - 1) {
       const int64_t t = t0 + geo.tile(it);
@@ -946,23 +737,11 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
       for (int pb = 0; pb < 4; ++pb) {
         const f32x4 v[8] = {acc[0][pb], acc[1][pb], acc[2][pb], acc[3][pb],
                             acc[4][pb], acc[5][pb], acc[6][pb], acc[7][pb]};
-#if EF_WIDE_ABL == 2
-        {  // diagnostic builds only: the screen's min without the top-2 update (every
-           // accumulator stays live, so no MFMA is dead code)
-          float mn = v[0][0];
-#pragma unroll
-          for (int e = 1; e + 1 < 32; e += 2) mn = min3_raw(mn, v[e >> 2][e & 3], v[(e + 1) >> 2][(e + 1) & 3]);
-          b1[pb] = fminf(b1[pb], fminf(mn, v[7][3]));
-        }
-#else
         consume(v, tbase, pb);
-#endif
       }
     }
-#if EF_WIDE_ABL != 1
     dma_wait_all();
     __syncthreads();  // slice it+1 landed; everyone is done reading buffer buf
-#endif
   }
 
   if constexpr (!COLLECT) {
@@ -975,10 +754,7 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
         const float ob1 = __shfl_xor(b1[pb], off);
         const int oi1 = __shfl_xor(i1[pb], off);
         const float ob2 = __shfl_xor(b2[pb], off);
-        const bool other = ob1 < b1[pb] || (ob1 == b1[pb] && oi1 < i1[pb]);
-        const float lose = other ? b1[pb] : ob1;
-        b2[pb] = fminf(fminf(b2[pb], ob2), lose);
-        if (other) { b1[pb] = ob1; i1[pb] = oi1; }
+        top2_merge(b1[pb], b2[pb], i1[pb], ob1, ob2, oi1);
       }
       if (rh == 1 && qd == 0) {
         const int o = ((pg * 4 + pb) * 16 + r16) * 3;
@@ -992,30 +768,22 @@ __global__ __launch_bounds__(512, 1) void search_wide16_kernel(
 #pragma unroll
       for (int pb = 0; pb < 4; ++pb) {
         const int o = ((pg * 4 + pb) * 16 + r16) * 3;
-        const float ob1 = xb[o], ob2 = xb[o + 1];
-        const int oi1 = __float_as_int(xb[o + 2]);
-        const bool other = ob1 < b1[pb] || (ob1 == b1[pb] && oi1 < i1[pb]);
-        const float lose = other ? b1[pb] : ob1;
-        b2[pb] = fminf(fminf(b2[pb], ob2), lose);
-        if (other) { b1[pb] = ob1; i1[pb] = oi1; }
-        const int64_t po = (int64_t)gc * bpad + sl0[pb];
-        ws.part_key[po] = i1[pb] == INT_MAX ? LLONG_MAX : pack_key(b1[pb], (unsigned)i1[pb]);
-        ws.part_b2[po] = b2[pb];
+        top2_merge(b1[pb], b2[pb], i1[pb], xb[o], xb[o + 1], __float_as_int(xb[o + 2]));
+        top2_store(ws, (int64_t)gc * bpad, sl0[pb], b1[pb], b2[pb], i1[pb]);
       }
     }
   }
   };  // body
   if constexpr (COLLECT) {
+    // collect_items<W3P>(ws, n_ptiles, body) written out: called through the helper, every
+    // COLLECT instantiation of this kernel needs 1-2 more VGPRs or spills one more
     const int n_amb = *ws.amb_count;
-    const int items = ((n_amb + 256 - 1) / 256) * n_ptiles;
+    const int items = ((n_amb + W3P - 1) / W3P) * n_ptiles;
     for (int item = blockIdx.x; item < items; item += gridDim.x) body(item % n_ptiles, item / n_ptiles, n_amb);
   } else {
-    const int total = gridDim.x;  // host guarantees total % 8 == 0
-    const int lin = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
-    const int bsz = cblk * pblk;
-    const int blk = lin / bsz, rr = lin - blk * bsz;
-    const int nbp = n_ptiles / pblk;
-    body((blk / nbp) * cblk + rr / pblk, (blk % nbp) * pblk + rr % pblk, 0);
+    int gc, pt;
+    xcd_block_deal(xcd_lin(), n_ptiles, pblk, cblk, gc, pt);
+    body(gc, pt, 0);
   }
 }
 
@@ -1023,9 +791,7 @@ template <int KP, int M, bool HI1 = false>
 static hipError_t wide3_t(hipStream_t s, bool collect, bool w16, const SearchPlan& pl, const float* q3,
                           const float* G3, const float* aux, int64_t n, int64_t bpad, const SearchWs& ws, int kp) {
   const dim3 grid((unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
-  if (pl.n_ptiles % pl.pblk != 0 || pl.nchunks % pl.cblk != 0 || (pl.nchunks * pl.n_ptiles) % 8 != 0 ||
-      (pl.nchunks * pl.n_ptiles / 8) % (pl.cblk * pl.pblk) != 0 || bpad % W3P != 0)
-    return hipErrorInvalidValue;  // the block deal would not be a bijection
+  if (!block_deal_ok(pl, W3P, bpad)) return hipErrorInvalidValue;
   if (w16 || HI1) {
     if (collect)
       hipLaunchKernelGGL((search_wide16_kernel<KP, M, true, HI1>), dim3((unsigned)pl.c_grid), block, 0, s, q3, G3,
@@ -1047,9 +813,7 @@ template <int KP, int M>
 static hipError_t wide_t(hipStream_t s, bool collect, int s3, const SearchPlan& pl, const float* qpad,
                          const float* G, const float* aux, int64_t n, int64_t bpad, const SearchWs& ws, int kp) {
   const dim3 grid((unsigned)(pl.nchunks * pl.n_ptiles)), block(256);
-  if (pl.n_ptiles % pl.pblk != 0 || pl.nchunks % pl.cblk != 0 || (pl.nchunks * pl.n_ptiles) % 8 != 0 ||
-      (pl.nchunks * pl.n_ptiles / 8) % (pl.cblk * pl.pblk) != 0)
-    return hipErrorInvalidValue;  // the block deal would not be a bijection
+  if (!block_deal_ok(pl, WP, bpad)) return hipErrorInvalidValue;
   // 32-bit geometry of the kernels: probe rows addressed by unsigned byte offsets, and (KP = 0)
   // the flattened (tile, slice) counter of a sweep divided in 32 bits
   const int64_t ns = kp / WBK;
@@ -1077,9 +841,10 @@ hipError_t launch_search_wide(hipStream_t s, int kp, int metric, bool collect, i
     if (kp % 128 != 0 || bpad * (int64_t)kh * 4 >= ((int64_t)1 << 31) ||
         (int64_t)std::max(pl.tiles_per_chunk, pl.c_tpc) * ns >= ((int64_t)1 << 31))
       return hipErrorInvalidValue;
-    // main pass at the compiled widths: the gallery-in-VGPRs screen (ef_search_screen.hip)
+#ifdef EF_DIAGNOSTICS  // A/B: the gallery-in-VGPRs main pass at its compiled widths (ef_search_screen.hip)
     if (!collect && (kh == 128 || kh == 256) && screen_vg_enabled())
       return launch_search_screen(s, kh, metric, pl, qpad, G, aux, n, bpad, ws);
+#endif
     switch (kp) {
       case 256:
         return l2 ? wide3_t<128, EF_METRIC_L2, true>(s, collect, true, pl, qpad, G, aux, n, bpad, ws, kh)

@@ -8,6 +8,7 @@ import pytest
 
 from conftest import golden
 from oracle import eigenface_oracle as orc
+from parity_util import assert_exact_argbest
 
 pytestmark = pytest.mark.gpu
 
@@ -195,6 +196,60 @@ def test_split_kernel_shapes_agree(split, k):
         np.testing.assert_array_equal(k16, k32)
         np.testing.assert_array_equal(k3232, k32)
     assert split.get_option("search_split_bf16") == 2
+
+
+@pytest.mark.parametrize("opt", [0, 1, 2, 3])
+@pytest.mark.parametrize("k", [128, 256, 640])
+def test_tail_tile_and_empty_chunks_every_scan(eng, k, opt):
+    """769 gallery rows = three full 256-row tiles plus one row, 257 probes = two probe tiles:
+    the wide split kernels plan 8 chunks of which 4 are empty, their last tile holds a single
+    row, and the lone row past the tile boundary is the planted best of every tenth probe.
+    Every scan arithmetic (0 fp32, 1 / 2 the two split-bf16 kernel shapes, 3 the bf16 screen;
+    k = 128 the narrow kernels, 256 the compiled wide ones, 640 the run-time row length)
+    returns the fp32 scan's keys and the fp64 first-arg-best (tests/parity_util.py)."""
+    rng = np.random.default_rng(769 + k)
+    n, b = 769, 257
+    g = rng.standard_normal((n, k)).astype(np.float32)
+    q = rng.standard_normal((b, k)).astype(np.float32)
+    q[::10] = g[n - 1] + rng.standard_normal((len(q[::10]), k)).astype(np.float32) * 0.05
+    try:
+        for metric in ("l2", "cosine"):
+            eng.set_option("search_split_bf16", 0)
+            eng.set_gallery(g)
+            k32 = eng.search_keys(q, metric)
+            eng.set_option("search_split_bf16", opt)
+            ks = eng.search_keys(q, metric)
+            np.testing.assert_array_equal(ks, k32)
+            idx = (ks & 0xFFFFFFFF).astype(np.int64)
+            assert_exact_argbest(q, g, idx, metric)
+            np.testing.assert_array_equal(idx[::10], n - 1)
+    finally:
+        eng.set_option("search_split_bf16", 0)
+
+
+@pytest.mark.parametrize("k", [128, 512])
+def test_option2_several_tiles_per_chunk(eng, k):
+    """The 32x32x16 split kernels (option 2: search_kernel<S3>, search_wide3_kernel) sweeping
+    more than one tile per chunk: 4096 probes = 16 probe tiles, so 5003 rows are planned as
+    79 64-row tiles in 32 chunks of 3 (k = 128) or 20 256-row tiles in 16 chunks of 2
+    (k = 512) — double-buffered tile hand-over inside a chunk, a ragged last tile and empty
+    trailing chunks at once.  Keys equal the fp32 scan's; every probe finds its planted row."""
+    rng = np.random.default_rng(5003 + k)
+    n, b = 5003, 4096
+    g = rng.standard_normal((n, k)).astype(np.float32)
+    t = rng.integers(0, n, b)
+    q = (g[t] + rng.standard_normal((b, k)).astype(np.float32) * 0.3).astype(np.float32)
+    try:
+        for metric in ("l2", "cosine"):
+            eng.set_option("search_split_bf16", 0)
+            eng.set_gallery(g)
+            k32 = eng.search_keys(q, metric)
+            eng.set_option("search_split_bf16", 2)
+            k2 = eng.search_keys(q, metric)
+            np.testing.assert_array_equal(k2, k32)
+            np.testing.assert_array_equal((k2 & 0xFFFFFFFF).astype(np.int64), t)
+    finally:
+        eng.set_option("search_split_bf16", 0)
 
 
 @pytest.mark.parametrize("k", [64, 128, 512])

@@ -122,6 +122,16 @@ def test_product_library_reads_no_environment_knobs():
     assert not re.search(r"\bgetenv\b", out)
 
 
+def test_product_library_has_no_diagnostic_screen_kernel():
+    """The gallery-in-VGPRs screen (csrc/ef_search_screen.hip) was measured slower than the
+    product path and is built by `make diag` only: the product library defines no symbol
+    of it (launcher, A/B switch or kernel stub)."""
+    from eigenface import _native
+    res = subprocess.run(["nm", "-D", "--defined-only", _native.LIB_PATH], capture_output=True, text=True)
+    assert res.returncode == 0 and "ef_search" in res.stdout, res.stderr  # nm ran and saw the library
+    assert "search_screen" not in res.stdout and "screen_vg" not in res.stdout
+
+
 def test_host_match_merge_is_exact():
     """ef_matches_merge on the host (no GPU): fp64 scores decide across parts even when
     their fp32 keys tie; exact ties and near-ties within 1e-12 go to the lowest index;

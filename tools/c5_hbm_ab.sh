@@ -1,7 +1,7 @@
 #!/bin/bash
 # C5 split-bf16 wide scan: HBM re-read experiment.  For the base library
-# and variant libraries (tools/variant.sh: EF_WIDE3_PB probe tiles per XCD block,
-# EF_WIDE_SERP serpentine k-slice order), the C5 bench line and one FETCH_SIZE pass of
+# and variant libraries (tools/variant.sh; the round-4 run compared probe tiles per XCD block and the
+# serpentine k-slice order, both since settled in the source), the C5 bench line and one FETCH_SIZE pass of
 # search_wide16_kernel.  usage: bash tools/c5_hbm_ab.sh <tag> <variant>...
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 9

@@ -1,6 +1,6 @@
 #!/bin/bash
 # C5 headline (split-bf16 wide scan) for the base library and each variant library
-# (tools/wide_variants.sh / tools/variant.sh), alternated twice: value, average launch, frac.
+# (tools/variant.sh), alternated twice: value, average launch, frac.
 # usage: [SPLIT=3] bash tools/c5_variant_bench.sh <tag> <variant>...   (SPLIT: the scan option, default 1)
 export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 9

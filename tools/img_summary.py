@@ -1,4 +1,4 @@
-"""Summarise the image-side rocprofv3 passes (tools/r05_capture.sh part `image`) into
+"""Summarise the image-side rocprofv3 passes (the `image` part of a capture run) into
 profiles/<round>/pmc_summary_tmatch.json and pmc_summary_haar.json.
 
   tmatch: tm_corr_kernel (the template localiser's int8 MFMA correlation): MFMA busy

@@ -1,6 +1,6 @@
 """The streamed JPEG ingest under a kernel + memory-copy trace: 6 warm-up calls, then 20
 back-to-back calls of bench's 4096 face crops (timing hooks off), so the trace shows where
-the device idles between batches.  Run under rocprofv3 (tools/r06_jpeg_timeline.sh)."""
+the device idles between batches.  Run under rocprofv3."""
 import gc
 import os
 import sys
