@@ -105,10 +105,44 @@ std::vector<SearchPiece> search_pieces(int64_t b, int kp) {
   return v;
 }
 
+// EF_OPT_SEARCH_PREFIX auto: the prefix length and the smallest gallery it engages for at
+// padded k = 128 (smaller galleries are launch-bound)
+constexpr int kPrefixAutoK1 = 32;
+constexpr int64_t kPrefixAutoMinRows = 65536;
+constexpr int kPrefixGuardSkips = 16;  // searches kept off the prefix scan after a bad one
+
+// The prefix length of this search, 0 = the plain full-k pipeline.  Also runs the guard: when
+// the last prefix search whose counters have arrived (never waited for) sent more than half
+// of its probe tiles to the full-k scan, this search and the next 15 skip the prefix scan —
+// it would cost its own pass on top of most of a full one.  Results do not depend on it.
+static int prefix_k1(ef_ctx* c, int metric) {
+  if (metric != EF_METRIC_L2 || c->opt_search_split_bf16 != 0 || c->g_kp > 128 || c->opt_search_prefix == 0) return 0;
+  int k1 = (int)c->opt_search_prefix;
+  if (k1 == 1) k1 = c->g_kp == 128 && c->n_gallery >= kPrefixAutoMinRows ? kPrefixAutoK1 : 0;
+  if (k1 <= 0 || k1 >= c->g_kp) return 0;
+  if (c->prefix_ev_pending) {
+    const hipError_t q = hipEventQuery(c->prefix_ev);
+    (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure of a later launch
+    if (q == hipSuccess) {
+      c->prefix_ev_pending = false;
+      const int64_t fb_tiles = ((int64_t)c->prefix_host[0] + kSearchProbeTile - 1) / kSearchProbeTile;
+      if (2 * fb_tiles > c->prefix_ev_tiles) c->prefix_skip_left = kPrefixGuardSkips;
+    }
+  }
+  if (c->prefix_skip_left > 0) {
+    --c->prefix_skip_left;
+    c->stats_skipped = true;
+    return 0;
+  }
+  return k1;
+}
+
 // Search the probes already in ctx->q_pad (at least round_up(b, 256) rows, kp = ctx->g_kp)
 // of this rank's gallery: keys_dev[b] and, when match_dev is non-null, the fp64 match
 // records, piece by piece (search_pieces).
 static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long* keys_dev, ef_match* match_dev) {
+  c->stats_probes = b;
+  c->stats_prefix = c->stats_skipped = false;
   if (c->n_gallery == 0) {
     EF_HIP(c, launch_keys_none(c->stream, keys_dev, b, match_dev), "keys");
     return EF_OK;
@@ -116,7 +150,8 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
   if (bpad < round_up(b, kSearchProbeTile))
     return set_err(c, EF_E_INVALID, "search: probe buffer shorter than the batch");
   const std::vector<SearchPiece> pieces = search_pieces(b, c->g_kp);
-  std::vector<SearchPlan> plans;
+  const int k1 = prefix_k1(c, metric);
+  std::vector<SearchPlan> plans, plans1;  // plans1: the prefix scan's (k1 > 0)
   int64_t bpad_max = 0;
   size_t parts = 0;
   for (const SearchPiece& p : pieces) {
@@ -124,6 +159,10 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
     plans.push_back(search_plan(p.bpad, c->n_gallery, c->g_kp, c->opt_search_split_bf16 != 0));
     bpad_max = std::max(bpad_max, p.bpad);
     parts = std::max(parts, (size_t)plans.back().nchunks * (size_t)p.bpad);
+    if (k1 > 0) {
+      plans1.push_back(search_plan(p.bpad, c->n_gallery, k1, false, prefix_tile_rows(k1)));
+      parts = std::max(parts, (size_t)plans1.back().nchunks * (size_t)p.bpad);
+    }
   }
   // workspace carve-out (16-byte aligned pieces), sized for the largest piece
   auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
@@ -167,6 +206,55 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
       c->g3_layout = layout;
     }
     G3 = static_cast<const float*>(c->G3.p);
+  }
+  if (k1 > 0) {
+    if (!c->g1_valid || c->g1_k1 != k1) {
+      EF_TRY(ensure(c, c->G1, (size_t)c->n_gallery * k1 * sizeof(float)));
+      EF_TRY(ensure(c, c->gnorm1, (size_t)c->n_gallery * 2 * sizeof(float)));
+      EF_HIP(c,
+             launch_prefix_gallery(c->stream, static_cast<const float*>(c->G.p), c->n_gallery, c->g_kp, k1,
+                                   static_cast<float*>(c->G1.p), static_cast<float*>(c->gnorm1.p)),
+             "prefix gallery");
+      c->g1_valid = true;
+      c->g1_k1 = k1;
+    }
+    if (!c->prefix_host) EF_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->prefix_host), 16, hipHostMallocDefault), "pinned counters");
+    if (!c->prefix_ev) EF_HIP(c, hipEventCreateWithFlags(&c->prefix_ev, hipEventDisableTiming), "event");
+    const size_t nq1 = al((size_t)bpad_max * k1 * 4), nq2 = al((size_t)bpad_max * c->g_kp * 4);
+    const size_t nk2 = al((size_t)bpad_max * 8), nm2 = al((size_t)bpad_max * sizeof(ef_match));
+    EF_TRY(ensure(c, c->prefix_ws, nq1 + nq2 + nlist + nk2 + nm2));
+    char* pb = static_cast<char*>(c->prefix_ws.p);
+    PrefixWs pw;
+    pw.q1 = reinterpret_cast<float*>(pb);
+    pb += nq1;
+    pw.qpad2 = reinterpret_cast<float*>(pb);
+    pb += nq2;
+    pw.list = reinterpret_cast<int*>(pb);
+    pb += nlist;
+    pw.keys2 = reinterpret_cast<long long*>(pb);
+    pb += nk2;
+    pw.match2 = reinterpret_cast<ef_match*>(pb);
+    EF_HIP(c, hipMemsetAsync(ws.amb_count + 2, 0, sizeof(int), c->stream), "zero counters");
+    int64_t tiles = 0;
+    for (size_t i = 0; i < pieces.size(); ++i) {
+      const SearchPiece& p = pieces[i];
+      ws.match = match_dev ? match_dev + p.off : nullptr;
+      tiles += p.bpad / kSearchProbeTile;
+      EF_HIP(c,
+             launch_search_prefix(c->stream, c->g_kp, k1, plans[i], plans1[i], static_cast<const float*>(c->q_pad.p) + p.off * c->g_kp,
+                                  p.bpad, p.b, static_cast<const float*>(c->G.p), aux, static_cast<const float*>(c->G1.p),
+                                  static_cast<const float*>(c->gnorm1.p), c->n_gallery, c->g_offset, c->gmax2_host, ws,
+                                  pw, keys_dev + p.off, c),
+             "prefix search");
+    }
+    // the counters follow the search to the host; nobody waits for them here
+    EF_HIP(c, hipMemcpyAsync(c->prefix_host, ws.amb_count + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream),
+           "D2H prefix counters");
+    EF_HIP(c, hipEventRecord(c->prefix_ev, c->stream), "event record");
+    c->prefix_ev_pending = true;
+    c->prefix_ev_tiles = tiles;
+    c->stats_prefix = true;
+    return EF_OK;
   }
   for (size_t i = 0; i < pieces.size(); ++i) {
     const SearchPiece& p = pieces[i];
@@ -420,7 +508,7 @@ void ef_destroy(ef_ctx* c) {
     (void)hipEventDestroy(t.b);
   }
   DevBuf* bufs[] = {&c->mean,      &c->W,         &c->W16,       &c->W16f,      &c->mean_r,    &c->mean_u8, &c->corr,
-                    &c->G,         &c->G3,        &c->q3,        &c->gnorm2,    &c->ginv,    &c->gmax2,
+                    &c->G,         &c->G3,        &c->G1,        &c->gnorm1,    &c->prefix_ws, &c->q3,        &c->gnorm2,    &c->ginv,    &c->gmax2,
                     &c->q_pad,     &c->keys,      &c->search_ws, &c->p_stage,   &c->proj_part,
                     &c->feats_dev, &c->jpeg_ws,   &c->jpeg_out,  &c->jpeg_rows, &c->jpeg_up[0], &c->jpeg_up[1]};
   for (DevBuf* b : bufs) release(*b);
@@ -429,6 +517,8 @@ void ef_destroy(ef_ctx* c) {
     if (c->jpeg_up_done[i]) (void)hipEventDestroy(c->jpeg_up_done[i]);
     if (c->jpeg_ws_free[i]) (void)hipEventDestroy(c->jpeg_ws_free[i]);
   }
+  if (c->prefix_host) (void)hipHostFree(c->prefix_host);
+  if (c->prefix_ev) (void)hipEventDestroy(c->prefix_ev);
   if (c->jpeg_done) (void)hipEventDestroy(c->jpeg_done);
   if (c->jpeg_copy) (void)hipStreamDestroy(c->jpeg_copy);
   for (int i = 0; i < 2; ++i)
@@ -593,6 +683,9 @@ int ef_gallery_set(ef_ctx* c, const float* G, int64_t n, int32_t k, int64_t offs
   (void)hipSetDevice(c->device);
   c->n_gallery = 0;
   c->g3_valid = false;
+  c->g1_valid = false;
+  c->prefix_ev_pending = false;  // the guard's history belongs to the gallery it was seen on
+  c->prefix_skip_left = 0;
   if (n > 0) {
     EF_TRY(ensure(c, c->G, (size_t)n * kp * sizeof(float)));
     EF_TRY(ensure(c, c->gnorm2, (size_t)n * sizeof(float)));
@@ -774,6 +867,15 @@ int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
       if (value < 0 || value > 3) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_SPLIT_BF16 must be 0, 1, 2 or 3");
       c->opt_search_split_bf16 = value;
       return EF_OK;
+    case EF_OPT_SEARCH_PREFIX:
+      if (value != 0 && value != 1 && value != 16 && value != 32 && value != 64)
+        return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_PREFIX must be 0, 1, 16, 32 or 64");
+      if (value >= 16 && c->g_kp > 0 && value >= c->g_kp)
+        return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_PREFIX: the prefix must be shorter than the gallery's padded k");
+      c->opt_search_prefix = value;
+      c->prefix_ev_pending = false;  // a new setting starts with a clean guard
+      c->prefix_skip_left = 0;
+      return EF_OK;
     case EF_OPT_HOST_THREADS:
       if (value < 0 || value > 256) return set_err(c, EF_E_INVALID, "EF_OPT_HOST_THREADS must be 0..256");
       g_host_threads.store((int)value, std::memory_order_relaxed);
@@ -796,6 +898,7 @@ int ef_get_option(const ef_ctx* c, int32_t option, int64_t* value) {
     case EF_OPT_JPEG_PART_FILES: *value = c->opt_jpeg_part_files; return EF_OK;
     case EF_OPT_FIT_CHEBYSHEV: *value = c->opt_fit_chebyshev; return EF_OK;
     case EF_OPT_HOST_THREADS: *value = host_threads(); return EF_OK;
+    case EF_OPT_SEARCH_PREFIX: *value = c->opt_search_prefix; return EF_OK;
     default: return EF_E_INVALID;
   }
 }
@@ -815,6 +918,18 @@ void ef_keys_decode(const int64_t* keys, int64_t b, int32_t metric, float* best,
     if (best) best[i] = metric == EF_METRIC_COSINE ? -v : v;
     if (idx) idx[i] = (int64_t)(uint32_t)(key & 0xffffffffll);
   }
+}
+
+int ef_search_stats(ef_ctx* c, int64_t out[4]) {
+  if (!c || !out) return EF_E_INVALID;
+  (void)hipSetDevice(c->device);
+  EF_HIP(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+  const int64_t fb = c->stats_prefix ? (int64_t)c->prefix_host[0] : 0;
+  out[0] = c->stats_probes;
+  out[1] = c->stats_prefix ? c->stats_probes - fb : 0;
+  out[2] = fb;
+  out[3] = c->stats_skipped ? 1 : 0;
+  return EF_OK;
 }
 
 int ef_timing_enable(ef_ctx* c, int on) {

@@ -60,6 +60,18 @@ struct SearchPlan {
   int c_chunks = 1, c_tpc = 1, c_grid = 8;
 };
 
+// Scratch of one prefix search (EF_OPT_SEARCH_PREFIX; device pointers).  The counters of the
+// path live beside SearchWs::amb_count: amb_count[1] = probes of this piece sent to the
+// full-k scan (the device count of the second run), amb_count[2] = their total over the
+// search's pieces.
+struct PrefixWs {
+  float* q1;         // [bpad][K1] the probes' first K1 components
+  float* qpad2;      // [bpad][KP] the unproven probes' rows, in list order
+  int* list;         // [bpad] probe of each unproven slot
+  long long* keys2;  // [bpad] keys of the second run, by slot
+  ef_match* match2;  // [bpad] match records of the second run, by slot
+};
+
 // one launch of a (possibly piecewise) search: probes [off, off + b), launched and planned
 // with bpad = round_up(b, 256) rows (ef_api.hip search_pieces)
 struct SearchPiece {
@@ -120,6 +132,24 @@ struct ef_ctx {
   ef::DevBuf G3;     // split-bf16 copy of G (same bytes), built on the first split search
   bool g3_valid = false;
   float gmax2_host = 0.f;
+  // prefix scan (EF_OPT_SEARCH_PREFIX): compact copy of the first g1_k1 components of every
+  // row with their squared norms, built on the first eligible search like G3
+  int64_t opt_search_prefix = 1;
+  ef::DevBuf G1;      // float[n][g1_k1]
+  ef::DevBuf gnorm1;  // float[2][n]: ||g[:K1]||^2, then the aux kernel's unused 1/||.|| output
+  bool g1_valid = false;
+  int g1_k1 = 0;
+  ef::DevBuf prefix_ws;  // per-call scratch of the prefix path (ef::PrefixWs carve-out)
+  // counters of the last prefix search, copied to pinned host memory behind the search
+  // ([0] probes sent to the full-k scan); the next search reads them once prefix_ev has passed
+  int* prefix_host = nullptr;
+  hipEvent_t prefix_ev = nullptr;
+  bool prefix_ev_pending = false;
+  int64_t prefix_ev_tiles = 0;  // probe tiles of the search prefix_ev belongs to
+  int prefix_skip_left = 0;     // searches the guard still keeps off the prefix scan
+  // what ef_search_stats reports: {probes, used the prefix scan, guard skipped}
+  int64_t stats_probes = 0;
+  bool stats_prefix = false, stats_skipped = false;
 
   // per-call scratch (grown on demand, never shrunk)
   ef::DevBuf q_pad;     // float[bpad][kp]
@@ -188,13 +218,25 @@ void timer_arm(ef_ctx* c, int kernel, TimerEvt* t);
 void timer_commit(ef_ctx* c, TimerEvt* t);
 
 // ---- launchers (defined in the .hip files) -------------------------------------------
-SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3);
+// tile_rows: gallery rows per tile when not the kernel family's own (the prefix scan)
+SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows = 0);
+int prefix_tile_rows(int k1);  // rows per tile of the prefix scan at prefix length k1
 std::vector<SearchPiece> search_pieces(int64_t b, int kp);
 // G3: split-bf16 copy of G (EF_OPT_SEARCH_SPLIT_BF16) or null for the fp32 kernels; Q3: scratch
 // [bpad][kp] for the split probes (kp > 128 with G3 only)
 hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl, const float* qpad, float* Q3,
                          int64_t bpad, int64_t b, const float* G, const float* G3, const float* aux, int64_t n,
                          int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, ef_ctx* c);
+// Prefix search (EF_OPT_SEARCH_PREFIX; L2, fp32 scan, k1 < kp <= 128): the scan over the
+// compact prefix copy (G1, gnorm1), the proof per probe, and the full-k pipeline of
+// launch_search on the unproven probes.  Same keys / match records as launch_search.
+hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan& pl, const SearchPlan& pl1,
+                                const float* qpad, int64_t bpad,
+                                int64_t b, const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
+                                int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
+                                long long* keys, ef_ctx* c);
+// G1[n][k1] <- G[n][kp][:k1], gnorm1[n] = ||G1 row||^2 (gnorm1 holds 2 n floats)
+hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, float* G1, float* gnorm1);
 hipError_t launch_split_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);
 // single-bf16 copy for the bf16 screen (EF_OPT_SEARCH_SPLIT_BF16 = 3), kp % 64 == 0
 hipError_t launch_hi_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);

@@ -41,6 +41,11 @@
 // chain; the winner is still re-scored from the fp32 gallery in fp64, so keys and match
 // records equal the fp32 path's bit for bit whenever both resolve
 // (tests/test_gpu_search_split.py; at the full C3 size, tests/test_gpu_c3_full.py).
+//
+// Prefix scan (EF_OPT_SEARCH_PREFIX; L2, fp32 scan): search_kernel<K1> over a compact copy
+// of the rows' first K1 components gives a lower bound of every distance;
+// reduce_prefix_kernel proves the winner from it where it can, and only the unproven probes
+// go through passes 1-3 at full k (launch_search_prefix).
 #include "ef_search_common.hpp"
 
 #include <cstdlib>
@@ -70,7 +75,12 @@ __device__ __forceinline__ void split8(const float* x, bf16x8& hi, bf16x8& lo) {
 // Each wave keeps its 32 probes as one B block (KP/2 VGPRs, pre-scaled) and runs the
 // tile's two 32-row blocks as two independent accumulator chains; the arg-best epilogue
 // is a branch-free top-2 in row order on registers.  <= 128 VGPRs -> 4 waves per SIMD.
-template <int KP, int METRIC, bool COLLECT, bool S3 = false>
+// CNT (main pass of the prefix path's second run, launch_search_prefix): the probe count is
+// on the device (ws.amb_count[1]); workgroups whose probe tile starts at or past it return.
+// TGT: gallery rows per LDS tile, TGT / 32 independent accumulator chains per wave.  64
+// everywhere but the prefix scan at K1 <= 32, whose tiles hold so few MFMAs that the
+// per-tile costs (barrier, DMA issue and wait, first LDS reads) show; 128 rows halve them.
+template <int KP, int METRIC, bool COLLECT, bool S3 = false, bool CNT = false, int TGT = TG>
 __global__ __launch_bounds__(512, 4) void search_kernel(
     const float* __restrict__ qpad, const float* __restrict__ G, const float* __restrict__ aux, int64_t n,
     int n_ptiles, int tiles_per_chunk, int64_t bpad, SearchWs ws) {
@@ -78,10 +88,12 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   constexpr int KH = KP / 2;
   constexpr int CPR = KP / 4;                                          // 16-B chunks per row
   constexpr int SW = (CPR & 15) == 0 ? 16 : ((CPR & 7) == 0 ? 8 : 4);  // XOR swizzle width
-  constexpr int NI = TG * CPR / 64;                                    // 1-KiB LDS-DMA pieces per tile
+  constexpr int NB = TGT / 32;                                         // 32-row MFMA blocks per tile
+  constexpr int NI = TGT * CPR / 64;                                   // 1-KiB LDS-DMA pieces per tile
   constexpr int PPW = (NI + NW - 1) / NW;                              // pieces per wave
   constexpr int RP = 64 / CPR;                                         // rows per piece
   static_assert((NI % NW == 0 || NI < NW) && RP * CPR == 64 && TG == 64, "tile must be whole 1-KiB pieces");
+  static_assert(TGT == 64 || (TGT == 128 && KP <= 32 && !S3), "128-row tiles: the fp32 scan at KP <= 32");
   // KP = 128 (the k = 128 headline shape): no swizzle.  LDS piece p (1 KiB + 16 B pad)
   // holds row p of the tile's first 32-row block and row 32 + p of the second, so the
   // lane reading row c32 of either block uses one base (c32 * 1040 B) plus immediate
@@ -90,13 +102,13 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   // keeps every ds_read_b128 lane group conflict-free.  One full-wave DMA per piece.
   constexpr bool PAD = KP == 128;
   constexpr int PS = 2 * KP + 4;          // PAD: floats per piece (two rows + 16 B)
-  constexpr int TGS = PAD ? 32 * PS : TG * KP;  // floats per tile buffer
+  constexpr int TGS = PAD ? 32 * PS : TGT * KP;  // floats per tile buffer
 
   // Unpadded [TG][KP] tiles filled by global_load_lds (lane-linear 1-KiB pieces); the
   // chunk order inside each row is XOR-swizzled by (row & (SW-1)) on the SOURCE address so
   // the A-fragment ds_read_b128s (16 lanes = 16 rows, same logical chunk) hit distinct
   // banks.  All LDS lives in one array (a second __shared__ object can de-pipeline).
-  __shared__ __attribute__((aligned(16))) float smem[2 * TGS + 2 * TG];
+  __shared__ __attribute__((aligned(16))) float smem[2 * TGS + 2 * TGT];
   float* const sG0 = smem;
   float* const sAux0 = smem + 2 * TGS;
 
@@ -111,7 +123,7 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   const int lrow = lane / CPR, lc = lane % CPR;  // this lane's (row, chunk) inside a piece
 
   int64_t t0, t1;
-  chunk_range<TG>(n, gc, tiles_per_chunk, t0, t1);
+  chunk_range<TGT>(n, gc, tiles_per_chunk, t0, t1);
   const int64_t s0 = (int64_t)pt * 256 + wave * 32 + c32;  // this lane's probe slot
 
   if (t0 >= t1) {  // empty chunk: publish "no candidate" so the reducer can skip it
@@ -130,13 +142,13 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   // Full tiles use the SGPR-base DMA form: per piece one v_xor + one v_lshl_add (every VALU
   // instruction in this loop costs MFMA issue time); the tail tile clamps rows instead.
   auto issue_tile = [&](int64_t t, int buf) {
-    const int nrem = (int)((n - t * TG) < TG ? (n - t * TG) : TG);
+    const int nrem = (int)((n - t * TGT) < TGT ? (n - t * TGT) : TGT);
     if constexpr (PAD) {  // piece p = rows p (lanes 0-31) and 32 + p (lanes 32-63)
       const unsigned m0 = lds_base + (unsigned)(buf * TGS * 4);
       unsigned lid;  // re-derived in place (a loop-long VGPR would be spilled by hipcc)
       asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
-      if (nrem == TG) {
-        const unsigned long long gb = uniform_ptr(G + t * TG * KP);
+      if (nrem == TGT) {
+        const unsigned long long gb = uniform_ptr(G + t * TGT * KP);
         if (wave == 0) glds4s(lid * 4u, uniform_ptr(aux + t * TG), lds_base + (unsigned)((2 * TGS + buf * TG) * 4));
         const unsigned voff = ((lid >> 5) * 32 * KP + (lid & 31) * 4) * 4;
 #pragma unroll
@@ -145,7 +157,7 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
           glds16s(voff, gb + (unsigned long long)(p * KP * 4), m0 + (unsigned)(p * PS * 4));
         }
       } else {
-        const float* gbase = G + t * TG * KP;
+        const float* gbase = G + t * TGT * KP;
 #pragma unroll
         for (int jj = 0; jj < PPW; ++jj) {
           const int p = wave * PPW + jj;
@@ -162,8 +174,8 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
     }
     int lx = lcx, lr = lrow;
     asm volatile("" : "+v"(lx), "+v"(lr));  // recompute per tile (no hoisted per-piece VGPRs)
-    if (nrem == TG) {
-      const unsigned long long gb = uniform_ptr(G + t * TG * KP);
+    if (nrem == TGT) {
+      const unsigned long long gb = uniform_ptr(G + t * TGT * KP);
       const unsigned lro = (unsigned)(lr * KP * 4);
 #pragma unroll
       for (int jj = 0; jj < PPW; ++jj) {
@@ -174,9 +186,15 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
                   lds_base + (unsigned)((buf * TGS + j * 256) * 4));
         }
       }
-      if (wave == 0) glds4s((unsigned)lane * 4u, uniform_ptr(aux + t * TG), lds_base + (unsigned)((2 * TGS + buf * TG) * 4));
+      if constexpr (TGT == 64) {
+        if (wave == 0) glds4s((unsigned)lane * 4u, uniform_ptr(aux + t * TG), lds_base + (unsigned)((2 * TGS + buf * TG) * 4));
+      } else {  // one 64-row half of the norms per wave
+        if (wave < TGT / 64)
+          glds4s((unsigned)lane * 4u, uniform_ptr(aux + t * TGT + wave * 64),
+                 lds_base + (unsigned)((2 * TGS + buf * TGT + wave * 64) * 4));
+      }
     } else {
-      const float* gbase = G + t * TG * KP;  // wave-uniform
+      const float* gbase = G + t * TGT * KP;  // wave-uniform
 #pragma unroll
       for (int jj = 0; jj < PPW; ++jj) {
         const int j = wave * PPW + jj;
@@ -187,9 +205,16 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
           glds16(gbase + row * KP + ((lx ^ sj) << 2), lds_base + (unsigned)((buf * TGS + j * 256) * 4));
         }
       }
-      if (wave == 0) {
-        const int row = lane < nrem ? lane : nrem - 1;
-        glds4(aux + t * TG + row, lds_base + (unsigned)((2 * TGS + buf * TG) * 4));  // one 4-B piece per lane
+      if constexpr (TGT == 64) {
+        if (wave == 0) {
+          const int row = lane < nrem ? lane : nrem - 1;
+          glds4(aux + t * TG + row, lds_base + (unsigned)((2 * TGS + buf * TG) * 4));  // one 4-B piece per lane
+        }
+      } else {
+        if (wave < TGT / 64) {
+          const int row = wave * 64 + lane < nrem ? wave * 64 + lane : nrem - 1;
+          glds4(aux + t * TGT + row, lds_base + (unsigned)((2 * TGS + buf * TGT + wave * 64) * 4));
+        }
       }
     }
   };
@@ -302,12 +327,56 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
     const int buf = (int)((t - t0) & 1);
     if (t + 1 < t1) issue_tile(t + 1, buf ^ 1);  // lands under this tile's MFMAs
     const float* tileG = sG0 + buf * TGS;
-    const float* tileA = sAux0 + buf * TG;
-    const bool tail = (t + 1) * TG > n;
-    const int tbase = (int)(t * TG);
+    const float* tileA = sAux0 + buf * TGT;
+    const bool tail = (t + 1) * TGT > n;
+    const int tbase = (int)(t * TGT);
     int swz = PAD ? 0 : c32 & (SW - 1);  // rows c32 and 32 + c32 share (row & (SW-1)), SW <= 16
     // opaque per tile: stops hipcc hoisting all KH/4 swizzled addresses out of the loop
     if constexpr (!PAD) asm volatile("" : "+v"(swz));
+    if constexpr (TGT != 64) {
+      // NB blocks at once: NB independent accumulator chains sharing the B operand, block
+      // bi = rows 32 bi + c32 (the same swizzle: 32 is a multiple of SW)
+      const float* arow = tileG + c32 * KP;
+      f32x16 acc[NB];
+#pragma unroll
+      for (int bi = 0; bi < NB; ++bi) acc[bi] = acc_init(tileA + 32 * bi);
+#pragma unroll
+      for (int s = 0; s < KH; s += 4) {
+        const int chunk = (h * (CPR / 2) + s / 4) ^ swz;
+        float4 a[NB];
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi) a[bi] = *reinterpret_cast<const float4*>(arow + bi * 32 * KP + chunk * 4);
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[bi].x, qb[s], acc[bi], 0, 0, 0);
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[bi].y, qb[s + 1], acc[bi], 0, 0, 0);
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[bi].z, qb[s + 2], acc[bi], 0, 0, 0);
+#pragma unroll
+        for (int bi = 0; bi < NB; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[bi].w, qb[s + 3], acc[bi], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);  // bound the A prefetch depth
+      }
+#pragma unroll
+      for (int bi = 0; bi < NB; ++bi) {
+        if constexpr (METRIC != EF_METRIC_L2) {  // cosine: -(q.g) * (1/||g||)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4 x = *reinterpret_cast<const float4*>(tileA + 32 * bi + 8 * q + 4 * h);
+            acc[bi][4 * q] *= x.x; acc[bi][4 * q + 1] *= x.y; acc[bi][4 * q + 2] *= x.z; acc[bi][4 * q + 3] *= x.w;
+          }
+        }
+        if (tail) {  // uniform: only the last tile has rows past n
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (tbase + 32 * bi + (r & 3) + 8 * (r >> 2) + 4 * h >= n) acc[bi][r] = INF;
+        }
+      }
+#pragma unroll
+      for (int bi = 0; bi < NB; ++bi) consume(acc[bi], tbase + 32 * bi);  // in row order (tie rule)
+      dma_wait_all();
+      __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
+      continue;
+    }
     const float* arow0 = tileG + (PAD ? c32 * PS : c32 * KP);
     const float* arow1 = PAD ? arow0 + KP : tileG + (32 + c32) * KP;
 
@@ -386,6 +455,9 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
     // one chunk are co-resident on it
     const int lin = xcd_lin();
     const int gc = lin / n_ptiles;
+    if constexpr (CNT) {
+      if ((lin - gc * n_ptiles) * kSearchProbeTile >= ws.amb_count[1]) return;  // workgroup-uniform
+    }
     body(gc, lin - gc * n_ptiles, 0);
   }
 }
@@ -627,7 +699,8 @@ __global__ __launch_bounds__(512, 4) void search16_kernel(
 // KP = 0: row length kp_rt at run time (k > 512).
 // S3: the scan's arithmetic — 0 fp32, 1 split bf16 (hi + lo), 2 single bf16 (the screen of
 // EF_OPT_SEARCH_SPLIT_BF16 = 3) — which sets the bound below.
-template <int KP, int METRIC, int S3 = 0>
+// CNT: the probe count is on the device (ws.amb_count[1], the prefix path's second run).
+template <int KP, int METRIC, int S3 = 0, bool CNT = false>
 __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ qpad, int64_t b, int64_t bpad,
                                                      int nchunks, const float* __restrict__ G, int64_t n,
                                                      int64_t g_offset, float gmax2, SearchWs ws,
@@ -636,6 +709,9 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ q
   const int lane = threadIdx.x & 63;
   const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= b) return;
+  if constexpr (CNT) {
+    if (p >= ws.amb_count[1]) return;
+  }
   long long kmin = LLONG_MAX;
   for (int c = lane; c < nchunks; c += 64) {
     const long long k = ws.part_key[(int64_t)c * bpad + p];
@@ -770,6 +846,128 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
   }
 }
 
+// ---- prefix path (EF_OPT_SEARCH_PREFIX, launch_search_prefix) ---------------------------
+// Reduce of the prefix scan, one wave per probe.  The scan ran search_kernel<K1, L2> over
+// the first K1 components of every row, so the per-chunk records hold fp32 prefix scores
+// s1(g) = fl(||g[:K1]||^2 - 2 q[:K1].g[:K1]).  w = the scan's winner, r2 = its runner-up
+// score = min of s1 over every row other than w (ties included).
+//
+// Proof that w is the answer.  In exact arithmetic, for every row g,
+//   D(g) = ||q - g||^2 >= ||q[:K1] - g[:K1]||^2 = q1 + S1(g),  q1 = ||q[:K1]||^2,
+// S1 the exact prefix score (the other KP - K1 squared differences are >= 0), and the scan's
+// rounding obeys |s1(g) - S1(g)| <= e1: the fp32 L2 bound of reduce_kernel with the chain
+// length K1 (||q|| and gmax2 of the full rows are upper bounds of the prefix's).  Hence
+//   D(g) >= q1 + r2 - e1   for every g != w.
+// The test is  q1 + r2 - delta1 > Dw + tol  with Dw = D(w) in fp64 (score64, the value the
+// key is built from), tol the tie window of resolve_kernel and delta1 = 4 e1 (reduce_kernel's
+// doubling for two compared scores and its x2 safety factor are kept).  When it holds,
+// every other row's distance exceeds Dw + tol: w is the unique arg-min outside the tie
+// window, which is what the full-k pipeline returns (its fp64 resolution keeps the lowest
+// index among rows within tol of the minimum — only w).  One-sided safety of the test's own
+// rounding: q1 and Dw are fp64 sums of <= 128 terms (relative error < 2^-45), r2 converts
+// exactly, and the three fp64 adds round to 2^-53 relative — together below 1e-13 of
+// (q1 + |r2| + Dw), while the 3 e1 of slack in delta1 is >= 3 (K1 + 4) 2^-24 gmax2 and tol
+// adds 1e-12 (Dw + ||q||^2 + gmax2) on the same side; |r2| <= ||q||^2 + gmax2 + 2 ||q|| gm.
+// A NaN anywhere makes the comparison false.  Unproven probes are appended to `list`
+// (count at ws.amb_count[1]) for the full-k pipeline.
+template <int KP, int K1>
+__global__ __launch_bounds__(256) void reduce_prefix_kernel(const float* __restrict__ qpad, int64_t b, int64_t bpad,
+                                                            int nchunks, const float* __restrict__ G,
+                                                            int64_t g_offset, float gmax2, SearchWs ws,
+                                                            long long* __restrict__ keys, int* __restrict__ list) {
+  const int lane = threadIdx.x & 63;
+  const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= b) return;
+  long long kmin = LLONG_MAX;
+  for (int c = lane; c < nchunks; c += 64) {
+    const long long k = ws.part_key[(int64_t)c * bpad + p];
+    kmin = k < kmin ? k : kmin;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long o = __shfl_xor(kmin, off);
+    kmin = o < kmin ? o : kmin;
+  }
+  if (kmin == LLONG_MAX) {  // no row scored (cannot happen with n > 0): the full-k run decides
+    if (lane == 0) list[atomicAdd(ws.amb_count + 1, 1)] = (int)p;
+    return;
+  }
+  float r2 = __builtin_inff();
+  for (int c = lane; c < nchunks; c += 64) {
+    const long long k = ws.part_key[(int64_t)c * bpad + p];
+    r2 = fminf(r2, ws.part_b2[(int64_t)c * bpad + p]);
+    if (k != kmin && k != LLONG_MAX) r2 = fminf(r2, key_value(k));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) r2 = fminf(r2, __shfl_xor(r2, off));
+
+  const float b1 = key_value(kmin);
+  const unsigned row = (unsigned)(kmin & 0xffffffffll);
+  const float* q = qpad + p * KP;
+  const double dw = score64<KP, EF_METRIC_L2>(q, G + (int64_t)row * KP, lane);
+  double qq64 = 0.0, q1 = 0.0;
+  for (int c = lane; c < KP; c += 64) {
+    const double t = (double)q[c] * (double)q[c];
+    qq64 += t;
+    if (c < K1) q1 += t;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    qq64 += __shfl_xor(qq64, off);
+    q1 += __shfl_xor(q1, off);
+  }
+  const float u = 5.9604645e-08f;  // 2^-24
+  const float qn = sqrtf((float)qq64), gm = sqrtf(gmax2);
+  const float delta1 = 2.f * (2.f * ((K1 + 4) * u * 1.01f * (2.f * qn * gm + gmax2) + 4.f * u * fabsf(b1)));
+  const double scale = qq64 + (double)gmax2;
+  const double tol = 1e-12 * (fabs(dw) + scale);
+  if (lane == 0) {
+    if (q1 + (double)r2 - (double)delta1 > dw + tol) {
+      const long long key = pack_key((float)dw, (unsigned)(row + g_offset));
+      keys[p] = key;
+      if (ws.match) ws.match[p] = ef_match{dw, scale, key};
+    } else {
+      list[atomicAdd(ws.amb_count + 1, 1)] = (int)p;
+    }
+  }
+}
+
+// dst[rows][c4_dst] <- the first c4_dst 16-B chunks of src[rows][c4_src] (the prefix copies of
+// the gallery and of the probes).
+__global__ void prefix_cols_kernel(const float4* __restrict__ src, int64_t rows, int c4_src, int c4_dst,
+                                   float4* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * c4_dst) return;
+  const int64_t r = i / c4_dst;
+  dst[i] = src[r * c4_src + (i - r * c4_dst)];
+}
+
+// Second run's probes: out[slot] <- qpad[list[slot]] for the *count unproven probes; the
+// rest of their last 256-probe tile is zeroed (scanned, never reduced).
+__global__ void prefix_gather_kernel(const float4* __restrict__ qpad, const int* __restrict__ list,
+                                     const int* __restrict__ count, int64_t bpad, int c4, float4* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bpad * c4) return;
+  const int64_t r = i / c4;
+  const int cnt = *count;
+  if (r >= ((int64_t)cnt + kSearchProbeTile - 1) / kSearchProbeTile * kSearchProbeTile) return;
+  out[i] = r < cnt ? qpad[(int64_t)list[r] * c4 + (i - r * c4)] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// Second run's results back to their probes; counters = ws.amb_count ([1] this piece's
+// count, [2] the search's running total for ef_search_stats and the guard).
+__global__ void prefix_scatter_kernel(const int* __restrict__ list, int* __restrict__ counters,
+                                      const long long* __restrict__ keys2, const ef_match* __restrict__ match2,
+                                      long long* __restrict__ keys, ef_match* __restrict__ match) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int cnt = counters[1];
+  if (i == 0) counters[2] += cnt;  // one thread of the launch; kernels of a stream run in order
+  if (i >= cnt) return;
+  const int p = list[i];
+  keys[p] = keys2[i];
+  if (match) match[p] = match2[i];
+}
+
 // dst[rows_pad][kp] <- src[rows][k] with zero padding.
 __global__ void pad_rows_kernel(const float* __restrict__ src, int64_t rows, int k, int64_t rows_pad,
                                 float* __restrict__ dst, int kp) {
@@ -851,12 +1049,14 @@ __global__ __launch_bounds__(256) void max_kernel(const float* __restrict__ x, i
 }
 
 // ------------------------------------------------------------------------ launchers
-SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3) {
+int prefix_tile_rows(int k1) { return k1 <= 32 ? 128 : TG; }
+
+SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows) {
   SearchPlan pl;
   const bool wide = kp > 128;
   const bool w3 = wide && s3;  // split-bf16 wide kernel: 256 x 256 tiles, one workgroup per CU
   pl.n_ptiles = (int)(bpad / (w3 ? kWide3ProbeTile : wide ? kWideProbeTile : kSearchProbeTile));
-  const int64_t rows_per_tile = w3 ? kWide3RowTile : wide ? kWideRowTile : TG;
+  const int64_t rows_per_tile = tile_rows ? tile_rows : w3 ? kWide3RowTile : wide ? kWideRowTile : TG;
   const int64_t tiles = (n + rows_per_tile - 1) / rows_per_tile;
   // ~512 workgroups = one resident wave of them (2 per CU): every chunk is swept by a
   // workgroup that starts at launch, so there is no tail round (measured: 90.1 % vs 89.6 %
@@ -1029,6 +1229,82 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl
                                                  true, &tev, c, kp);
   }
 #undef EF_SEARCH_CASE
+}
+
+// Prefix search.  pl1 = search_plan(bpad, n, K1, false, prefix_tile_rows(K1)) plans the
+// prefix scan, pl the second run (the plain plan of KP).
+//   1. Q1 <- the probes' first K1 columns; search_kernel<K1> over (Q1, G1, gnorm1): the
+//      timed main launch, a K1 / KP share of the full scan's MFMAs, in 128-row tiles at
+//      K1 <= 32 (prefix_tile_rows; profiles/r08).
+//   2. reduce_prefix_kernel: proven probes get their key / match record, the others are listed.
+//   3. The listed probes' rows are gathered into qpad2 and go through search_t's sequence
+//      (main scan, reduce, COLLECT, resolve) with the device count in place of b; the grids
+//      are sized for bpad and the work past the count returns at once, so the host never
+//      learns the count.  Their keys / records are scattered back by the list.
+template <int KP, int K1>
+static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const SearchPlan& pl1, const float* qpad, int64_t bpad, int64_t b,
+                                  const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
+                                  int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
+                                  long long* keys, ef_ctx* c) {
+  constexpr int M = EF_METRIC_L2;
+  const dim3 grid((unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
+  const dim3 pgrid((unsigned)((b + 3) / 4));
+  hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((bpad * (K1 / 4) + 255) / 256)), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(qpad), bpad, KP / 4, K1 / 4, reinterpret_cast<float4*>(pw.q1));
+  TimerEvt tev;
+  timer_begin(c, EF_KERNEL_SEARCH, &tev);
+  hipLaunchKernelGGL((search_kernel<K1, M, false, false, false, (K1 <= 32 ? 128 : TG)>),
+                     dim3((unsigned)(pl1.nchunks * pl1.n_ptiles)), block, 0, s, pw.q1, G1, gnorm1, n, pl1.n_ptiles,
+                     pl1.tiles_per_chunk, bpad, ws);
+  timer_end(c, &tev);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(ws.amb_count, 0, 2 * sizeof(int), s);  // [0] queued for fp64, [1] unproven
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((reduce_prefix_kernel<KP, K1>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl1.nchunks, G, g_offset,
+                     gmax2, ws, keys, pw.list);
+  hipLaunchKernelGGL(prefix_gather_kernel, dim3((unsigned)((bpad * (KP / 4) + 255) / 256)), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(qpad), pw.list, ws.amb_count + 1, bpad, KP / 4,
+                     reinterpret_cast<float4*>(pw.qpad2));
+  SearchWs w2 = ws;
+  w2.match = ws.match ? pw.match2 : nullptr;
+  hipLaunchKernelGGL((search_kernel<KP, M, false, false, true>), grid, block, 0, s, pw.qpad2, G, gnorm2, n,
+                     pl.n_ptiles, pl.tiles_per_chunk, bpad, w2);
+  hipLaunchKernelGGL((reduce_kernel<KP, M, 0, true>), pgrid, dim3(256), 0, s, pw.qpad2, b, bpad, pl.nchunks, G, n,
+                     g_offset, gmax2, w2, pw.keys2, KP);
+  hipLaunchKernelGGL((search_kernel<KP, M, true>), dim3((unsigned)pl.c_grid), block, 0, s, pw.qpad2, G, gnorm2, n,
+                     pl.c_chunks, pl.c_tpc, bpad, w2);
+  hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, dim3(256), 0, s, pw.qpad2, G, n, g_offset, gmax2, w2, pw.keys2,
+                     KP);
+  hipLaunchKernelGGL(prefix_scatter_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, s, pw.list, ws.amb_count,
+                     pw.keys2, w2.match, keys, ws.match);
+  return hipGetLastError();
+}
+
+hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan& pl, const SearchPlan& pl1,
+                                const float* qpad, int64_t bpad,
+                                int64_t b, const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
+                                int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
+                                long long* keys, ef_ctx* c) {
+#define EF_PREFIX_CASE(KPV, K1V)                                                                                  \
+  if (kp == KPV && k1 == K1V)                                                                                     \
+    return search_prefix_t<KPV, K1V>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, n, g_offset, gmax2, ws, pw, keys, c);
+  EF_PREFIX_CASE(128, 64)
+  EF_PREFIX_CASE(128, 32)
+  EF_PREFIX_CASE(128, 16)
+  EF_PREFIX_CASE(64, 32)
+  EF_PREFIX_CASE(64, 16)
+  EF_PREFIX_CASE(32, 16)
+#undef EF_PREFIX_CASE
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, float* G1, float* gnorm1) {
+  hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((n * (k1 / 4) + 255) / 256)), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(G), n, kp / 4, k1 / 4, reinterpret_cast<float4*>(G1));
+  // the norms as gallery_aux_kernel computes gnorm2 (its 1/||g|| output goes to the spare half)
+  hipLaunchKernelGGL(gallery_aux_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, G1, n, k1, gnorm1, gnorm1 + n);
+  return hipGetLastError();
 }
 
 __global__ void keys_fill_kernel(long long* keys, int64_t b, ef_match* match) {

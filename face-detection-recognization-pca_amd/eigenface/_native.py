@@ -34,6 +34,7 @@ EF_OPT_SEARCH_SPLIT_BF16 = 7
 EF_OPT_JPEG_PART_FILES = 8
 EF_OPT_FIT_CHEBYSHEV = 9
 EF_OPT_HOST_THREADS = 10
+EF_OPT_SEARCH_PREFIX = 11
 EF_E_NUMERIC = -5
 
 
@@ -113,6 +114,7 @@ _SIGS = {
     "ef_timing_enable": ([vp, C.c_int], C.c_int),
     "ef_timing_get": ([vp, i32, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
     "ef_timing_reset": ([vp], C.c_int),
+    "ef_search_stats": ([vp, C.POINTER(i64)], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

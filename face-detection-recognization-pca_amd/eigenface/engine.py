@@ -40,7 +40,8 @@ _OPTIONS = {"fit_max_iters": N.EF_OPT_FIT_MAX_ITERS, "fit_fp32_coarse": N.EF_OPT
             "cov_slab_bytes": N.EF_OPT_COV_SLAB_BYTES, "tm_int64_sums": N.EF_OPT_TM_INT64_SUMS,
             "haar_ordered": N.EF_OPT_HAAR_ORDERED, "jpeg_chunk_bits": N.EF_OPT_JPEG_CHUNK_BITS,
             "search_split_bf16": N.EF_OPT_SEARCH_SPLIT_BF16, "jpeg_part_files": N.EF_OPT_JPEG_PART_FILES,
-            "fit_chebyshev": N.EF_OPT_FIT_CHEBYSHEV, "host_threads": N.EF_OPT_HOST_THREADS}
+            "fit_chebyshev": N.EF_OPT_FIT_CHEBYSHEV, "host_threads": N.EF_OPT_HOST_THREADS,
+            "search_prefix": N.EF_OPT_SEARCH_PREFIX}
 
 
 def host_cpu_share():
@@ -233,14 +234,21 @@ class Engine:
     def set_option(self, option, value):
         """Context tunable (include/eigenface.h EF_OPT_*): "fit_max_iters",
         "fit_fp32_coarse", "cov_slab_bytes", "tm_int64_sums", "haar_ordered", "jpeg_chunk_bits",
-        "search_split_bf16", "jpeg_part_files", "fit_chebyshev", "host_threads" (process-wide) or
-        the code."""
+        "search_split_bf16", "jpeg_part_files", "fit_chebyshev", "host_threads" (process-wide),
+        "search_prefix" or the code."""
         self._chk(self._lib.ef_set_option(self._h, _option(option), int(value)))
 
     def get_option(self, option):
         v = C.c_int64(0)
         self._chk(self._lib.ef_get_option(self._h, _option(option), C.byref(v)))
         return int(v.value)
+
+    def search_stats(self):
+        """(probes, proven by the prefix scan, sent to the full-k scan, guard skipped) of the
+        most recent search (ef_search_stats); synchronises the stream."""
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.ef_search_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     # --------------------------------------------------------------- multi-GPU
     @staticmethod

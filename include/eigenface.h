@@ -273,6 +273,13 @@ int ef_comm_info(const ef_ctx* ctx, int32_t* nranks, int32_t* rank);
 #define EF_OPT_HOST_THREADS 10     /* host worker threads for the JPEG parse / destuff, PROCESS-WIDE
                                       (any context sets it) [0: min(16, hardware threads)]; the
                                       Python Engine sets the job's CPU share (API v7) */
+#define EF_OPT_SEARCH_PREFIX 11    /* L2 fp32 scans at padded k <= 128: scan the first K1 components of
+                                      every row (a lower bound of the distance), prove the winner
+                                      from it and send only unproven probes through the full-k
+                                      scan; results are those of 0.  0: off; 1 [default]: auto
+                                      (K1 = 32 at padded k = 128 and >= 65536 rows, else off);
+                                      16 / 32 / 64: that K1 at any size (must be < the padded k of
+                                      the gallery in place) */
 int ef_set_option(ef_ctx* ctx, int32_t option, int64_t value);
 int ef_get_option(const ef_ctx* ctx, int32_t option, int64_t* value);
 
@@ -380,6 +387,12 @@ int ef_haar_detect(ef_ctx* ctx, const uint8_t* gray, int32_t h, int32_t w, int64
 int ef_timing_enable(ef_ctx* ctx, int on);
 int ef_timing_get(ef_ctx* ctx, int32_t kernel_id, double* total_ms, int64_t* launches);
 int ef_timing_reset(ef_ctx* ctx);
+
+/* Prefix-scan counters of the most recent search on this context (EF_OPT_SEARCH_PREFIX):
+ * out = {probes, proven by the prefix scan, sent to the full-k scan, 1 if the guard skipped
+ * the prefix scan}.  A search the prefix scan does not apply to reports {probes, 0, 0, 0}.
+ * Synchronises the context's stream. */
+int ef_search_stats(ef_ctx* ctx, int64_t out[4]);
 
 #ifdef __cplusplus
 }
