@@ -41,51 +41,87 @@ int ensure(ef_ctx* c, DevBuf& b, size_t bytes) {
   return EF_OK;
 }
 
-void release(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
+// ---- the owning handles (ef_internal.hpp): the only places that free ----------------
+void free_device(void* p) { (void)hipFree(p); }
+void free_pinned(void* p) { (void)hipHostFree(p); }
+void free_event(hipEvent_t e) { (void)hipEventDestroy(e); }
+void free_stream(hipStream_t s) { (void)hipStreamDestroy(s); }
+
+hipError_t event_get(Event& e, hipStream_t record_on, unsigned flags) {
+  if (e.p) return hipSuccess;
+  hipError_t rc = hipEventCreateWithFlags(&e.p, flags);
+  if (rc != hipSuccess) e.p = nullptr;
+  else if (record_on) rc = hipEventRecord(e.p, record_on);
+  return rc;
+}
+
+hipError_t stream_get(Stream& s) {
+  if (s.p) return hipSuccess;
+  const hipError_t rc = hipStreamCreateWithFlags(&s.p, hipStreamNonBlocking);
+  if (rc != hipSuccess) s.p = nullptr;
+  return rc;
+}
+
+hipError_t pinned_alloc(PinnedBuf& b, size_t bytes) {
+  b.reset();
+  const hipError_t rc = hipHostMalloc(&b.p, bytes, hipHostMallocDefault);
+  if (rc != hipSuccess) b.p = nullptr;
+  else b.bytes = bytes;
+  return rc;
+}
+
+hipError_t SideJoin::fork() {
+  hipError_t e = stream_get(side_.s);
+  if (e == hipSuccess) e = event_get(side_.forked);
+  if (e == hipSuccess) e = event_get(side_.done);
+  if (e == hipSuccess) e = hipEventRecord(side_.forked, main_);
+  if (e == hipSuccess) e = hipStreamWaitEvent(side_.s, side_.forked, 0);
+  forked_ = e == hipSuccess;
+  return e;
+}
+
+hipError_t SideJoin::done() {
+  const hipError_t e = hipEventRecord(side_.done, side_.s);
+  done_ = e == hipSuccess;
+  return e;
+}
+
+hipError_t SideJoin::join() {
+  if (!forked_) return hipSuccess;
+  forked_ = false;
+  // an exit between fork() and done(): whatever the side stream holds by now
+  if (!done_ && hipEventRecord(side_.done, side_.s) != hipSuccess) return hipStreamSynchronize(side_.s);
+  return hipStreamWaitEvent(main_, side_.done, 0);
+}
+
+// Timer events carry timestamps (the default flags).  A TimerEvt that is not queued frees
+// its events when it goes out of scope.
+static bool timer_events(ef_ctx* c, int kernel, TimerEvt* t) {
+  t->kernel = -1;
+  if (!c->timing) return false;
+  if (event_get(t->a, nullptr, hipEventDefault) != hipSuccess) return false;
+  if (event_get(t->b, nullptr, hipEventDefault) != hipSuccess) return false;
+  t->kernel = kernel;
+  return true;
 }
 
 void timer_begin(ef_ctx* c, int kernel, TimerEvt* t) {
-  t->kernel = -1;
-  if (!c->timing) return;
-  if (hipEventCreate(&t->a) != hipSuccess) return;
-  if (hipEventCreate(&t->b) != hipSuccess) { (void)hipEventDestroy(t->a); return; }
-  t->kernel = kernel;
-  (void)hipEventRecord(t->a, c->stream);
+  if (timer_events(c, kernel, t)) (void)hipEventRecord(t->a, c->stream);
 }
 
-void timer_arm(ef_ctx* c, int kernel, TimerEvt* t) {
-  t->kernel = -1;
-  if (!c->timing) return;
-  if (hipEventCreate(&t->a) != hipSuccess) return;
-  if (hipEventCreate(&t->b) != hipSuccess) { (void)hipEventDestroy(t->a); return; }
-  t->kernel = kernel;
-}
+void timer_arm(ef_ctx* c, int kernel, TimerEvt* t) { (void)timer_events(c, kernel, t); }
 
 void timer_commit(ef_ctx* c, TimerEvt* t) {
-  if (t->kernel >= 0) c->pending.push_back(*t);
+  if (t->kernel >= 0) c->pending.push_back(std::move(*t));
+  t->kernel = -1;
 }
 
 void timer_end(ef_ctx* c, TimerEvt* t) {
   if (t->kernel < 0) return;
   (void)hipEventRecord(t->b, c->stream);
-  c->pending.push_back(*t);
+  c->pending.push_back(std::move(*t));
+  t->kernel = -1;
 }
-
-static int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-#define EF_TRY(expr)                         \
-  do {                                       \
-    int _rc = (expr);                        \
-    if (_rc != EF_OK) return _rc;            \
-  } while (0)
-#define EF_HIP(ctx, expr, what)                           \
-  do {                                                    \
-    hipError_t _e = (expr);                               \
-    if (_e != hipSuccess) return hip_err(ctx, _e, what);  \
-  } while (0)
 
 // The pieces search_local launches for b probes of kp floats: whole 256-probe tiles, at
 // most as many per piece as keep a probe row's byte offset below 2^31 (the kernels' 32-bit
@@ -125,7 +161,7 @@ static int prefix_k1(ef_ctx* c, int metric) {
     (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure of a later launch
     if (q == hipSuccess) {
       c->prefix_ev_pending = false;
-      const int64_t fb_tiles = ((int64_t)c->prefix_host[0] + kSearchProbeTile - 1) / kSearchProbeTile;
+      const int64_t fb_tiles = round_up(*static_cast<const int*>(c->prefix_host.p), kSearchProbeTile) / kSearchProbeTile;
       if (2 * fb_tiles > c->prefix_ev_tiles) c->prefix_skip_left = kPrefixGuardSkips;
     }
   }
@@ -164,27 +200,12 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
       parts = std::max(parts, (size_t)plans1.back().nchunks * (size_t)p.bpad);
     }
   }
-  // workspace carve-out (16-byte aligned pieces), sized for the largest piece
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t nkb = al(parts * 8), nb2 = al(parts * 4);
-  const size_t ncnt = al(16), nlist = al((size_t)bpad_max * 4), nthr = al((size_t)bpad_max * 4);
-  const size_t ncand = al((size_t)bpad_max * kCandMax * 4), ncc = al((size_t)bpad_max * 4);
-  EF_TRY(ensure(c, c->search_ws, nkb + nb2 + ncnt + nlist + nthr + ncand + ncc));
-  char* base = static_cast<char*>(c->search_ws.p);
-  SearchWs ws;
-  ws.part_key = reinterpret_cast<long long*>(base);
-  base += nkb;
-  ws.part_b2 = reinterpret_cast<float*>(base);
-  base += nb2;
-  ws.amb_count = reinterpret_cast<int*>(base);
-  base += ncnt;
-  ws.amb_list = reinterpret_cast<int*>(base);
-  base += nlist;
-  ws.thr = reinterpret_cast<float*>(base);
-  base += nthr;
-  ws.cand = reinterpret_cast<int*>(base);
-  base += ncand;
-  ws.cand_cnt = reinterpret_cast<int*>(base);
+  // workspace carve-out, sized for the largest piece
+  Carve size_ws, cv;
+  carve_search_ws(size_ws, parts, (size_t)bpad_max);
+  EF_TRY(ensure(c, c->search_ws, size_ws.total));
+  cv.base = c->search_ws.p;
+  SearchWs ws = carve_search_ws(cv, parts, (size_t)bpad_max);
   const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? c->gnorm2.p : c->ginv.p);
   const float* G3 = nullptr;
   float* Q3 = nullptr;
@@ -218,22 +239,13 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
       c->g1_valid = true;
       c->g1_k1 = k1;
     }
-    if (!c->prefix_host) EF_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->prefix_host), 16, hipHostMallocDefault), "pinned counters");
-    if (!c->prefix_ev) EF_HIP(c, hipEventCreateWithFlags(&c->prefix_ev, hipEventDisableTiming), "event");
-    const size_t nq1 = al((size_t)bpad_max * k1 * 4), nq2 = al((size_t)bpad_max * c->g_kp * 4);
-    const size_t nk2 = al((size_t)bpad_max * 8), nm2 = al((size_t)bpad_max * sizeof(ef_match));
-    EF_TRY(ensure(c, c->prefix_ws, nq1 + nq2 + nlist + nk2 + nm2));
-    char* pb = static_cast<char*>(c->prefix_ws.p);
-    PrefixWs pw;
-    pw.q1 = reinterpret_cast<float*>(pb);
-    pb += nq1;
-    pw.qpad2 = reinterpret_cast<float*>(pb);
-    pb += nq2;
-    pw.list = reinterpret_cast<int*>(pb);
-    pb += nlist;
-    pw.keys2 = reinterpret_cast<long long*>(pb);
-    pb += nk2;
-    pw.match2 = reinterpret_cast<ef_match*>(pb);
+    if (!c->prefix_host.p) EF_HIP(c, pinned_alloc(c->prefix_host, 16), "pinned counters");
+    EF_HIP(c, event_get(c->prefix_ev), "event");
+    Carve size_pw, cvp;
+    carve_prefix_ws(size_pw, (size_t)bpad_max, k1, c->g_kp);
+    EF_TRY(ensure(c, c->prefix_ws, size_pw.total));
+    cvp.base = c->prefix_ws.p;
+    const PrefixWs pw = carve_prefix_ws(cvp, (size_t)bpad_max, k1, c->g_kp);
     EF_HIP(c, hipMemsetAsync(ws.amb_count + 2, 0, sizeof(int), c->stream), "zero counters");
     int64_t tiles = 0;
     for (size_t i = 0; i < pieces.size(); ++i) {
@@ -248,7 +260,7 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
              "prefix search");
     }
     // the counters follow the search to the host; nobody waits for them here
-    EF_HIP(c, hipMemcpyAsync(c->prefix_host, ws.amb_count + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream),
+    EF_HIP(c, hipMemcpyAsync(c->prefix_host.p, ws.amb_count + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream),
            "D2H prefix counters");
     EF_HIP(c, hipEventRecord(c->prefix_ev, c->stream), "event record");
     c->prefix_ev_pending = true;
@@ -359,6 +371,47 @@ static int stage_probes(ef_ctx* c, const void* P, int dtype, int64_t b, uint32_t
   return EF_OK;
 }
 
+// Where one call's keys, match records and features (each optional) are written: the caller's
+// own pointers with EF_MEM_DEVICE, else the context's staging buffers, which fetch() copies
+// to the caller's host pointers before it synchronises.
+struct Results {
+  bool dev;
+  int64_t b;
+  int64_t* keys;  // as the caller gave them
+  ef_match* match;
+  float* feats;
+  long long* kdev = nullptr;  // where the kernels write
+  ef_match* mdev = nullptr;
+  float* fdev = nullptr;
+
+  int stage_feats(ef_ctx* c) {  // needs the model's k
+    if (!feats) return EF_OK;
+    fdev = feats;
+    if (dev) return EF_OK;
+    EF_TRY(ensure(c, c->feats_dev, (size_t)b * c->k * sizeof(float)));
+    fdev = static_cast<float*>(c->feats_dev.p);
+    return EF_OK;
+  }
+  // keys are always produced (bpad of them, then the records, in ctx->keys when staged)
+  int stage_keys(ef_ctx* c, int64_t bpad) {
+    EF_TRY(ensure(c, c->keys, (size_t)bpad * sizeof(long long) + (size_t)b * sizeof(ef_match)));
+    kdev = (dev && keys) ? reinterpret_cast<long long*>(keys) : static_cast<long long*>(c->keys.p);
+    if (match) mdev = dev ? match : reinterpret_cast<ef_match*>(static_cast<char*>(c->keys.p) + bpad * sizeof(long long));
+    return EF_OK;
+  }
+  int fetch(ef_ctx* c) const {
+    if (dev) return EF_OK;  // stream-ordered; the caller synchronises
+    auto d2h = [&](void* dst, const void* src, size_t bytes) {
+      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    EF_HIP(c, d2h(keys, kdev, (size_t)b * sizeof(long long)), "D2H keys");
+    EF_HIP(c, d2h(match, mdev, (size_t)b * sizeof(ef_match)), "D2H matches");
+    EF_HIP(c, d2h(feats, fdev, (size_t)b * c->k * sizeof(float)), "D2H features");
+    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+    return EF_OK;
+  }
+};
+
 namespace {
 class HostPool {
  public:
@@ -448,6 +501,12 @@ hipError_t allow_dynamic_lds(const void* fn, int bytes) {
 
 using namespace ef;
 
+ef_ctx::~ef_ctx() {
+  comm_release(this);
+  tm_release(this);
+  haar_release(this);
+}
+
 extern "C" {
 
 int ef_api_version(void) { return EF_API_VERSION; }
@@ -489,7 +548,7 @@ int ef_create(int device, ef_ctx** out) {
   if (hipSetDevice(device) != hipSuccess) return EF_E_HIP;
   ef_ctx* c = new ef_ctx();
   c->device = device;
-  if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+  if (stream_get(c->own_stream) != hipSuccess) {
     delete c;
     return EF_E_HIP;
   }
@@ -503,35 +562,8 @@ void ef_destroy(ef_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   (void)jpeg_quiesce(c);
-  for (auto& t : c->pending) {
-    (void)hipEventDestroy(t.a);
-    (void)hipEventDestroy(t.b);
-  }
-  DevBuf* bufs[] = {&c->mean,      &c->W,         &c->W16,       &c->W16f,      &c->mean_r,    &c->mean_u8, &c->corr,
-                    &c->G,         &c->G3,        &c->G1,        &c->gnorm1,    &c->prefix_ws, &c->q3,        &c->gnorm2,    &c->ginv,    &c->gmax2,
-                    &c->q_pad,     &c->keys,      &c->search_ws, &c->p_stage,   &c->proj_part,
-                    &c->feats_dev, &c->jpeg_ws,   &c->jpeg_out,  &c->jpeg_rows, &c->jpeg_up[0], &c->jpeg_up[1]};
-  for (DevBuf* b : bufs) release(*b);
-  for (int i = 0; i < 2; ++i) {
-    if (c->jpeg_pinned[i]) (void)hipHostFree(c->jpeg_pinned[i]);
-    if (c->jpeg_up_done[i]) (void)hipEventDestroy(c->jpeg_up_done[i]);
-    if (c->jpeg_ws_free[i]) (void)hipEventDestroy(c->jpeg_ws_free[i]);
-  }
-  if (c->prefix_host) (void)hipHostFree(c->prefix_host);
-  if (c->prefix_ev) (void)hipEventDestroy(c->prefix_ev);
-  if (c->jpeg_done) (void)hipEventDestroy(c->jpeg_done);
-  if (c->jpeg_copy) (void)hipStreamDestroy(c->jpeg_copy);
-  for (int i = 0; i < 2; ++i)
-    if (c->fit_side_ev[i]) (void)hipEventDestroy(c->fit_side_ev[i]);
-  if (c->fit_side) (void)hipStreamDestroy(c->fit_side);
-  for (int i = 0; i < 2; ++i)
-    if (c->tm_side_ev[i]) (void)hipEventDestroy(c->tm_side_ev[i]);
-  if (c->tm_side) (void)hipStreamDestroy(c->tm_side);
-  for (auto& b : c->fit_pool) release(b);
-  comm_release(c);
-  tm_release(c);
-  haar_release(c);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  for (const SideStream* side : {&c->fit_side, &c->tm_side})
+    if (side->s.p) (void)hipStreamSynchronize(side->s);
   delete c;
 }
 
@@ -566,18 +598,9 @@ int ef_trim(ef_ctx* c) {
   EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
   EF_HIP(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
   EF_HIP(c, jpeg_quiesce(c), "jpeg quiesce");
-  for (auto& b : c->fit_pool) release(b);
   c->fit_pool.clear();
-  release(c->jpeg_ws);
-  release(c->jpeg_out);
-  release(c->jpeg_rows);
-  release(c->jpeg_up[0]);
-  release(c->jpeg_up[1]);
-  for (int i = 0; i < 2; ++i) {
-    if (c->jpeg_pinned[i]) (void)hipHostFree(c->jpeg_pinned[i]);
-    c->jpeg_pinned[i] = nullptr;
-    c->jpeg_pinned_bytes[i] = 0;
-  }
+  for (DevBuf* b : {&c->jpeg_ws, &c->jpeg_out, &c->jpeg_rows, &c->jpeg_up[0], &c->jpeg_up[1]}) release(*b);
+  for (PinnedBuf& b : c->jpeg_pinned) b.reset();
   return EF_OK;
 }
 
@@ -589,51 +612,48 @@ int ef_model_set(ef_ctx* c, const float* mean, const float* W, int64_t d, int32_
   (void)hipSetDevice(c->device);
   const bool bf16 = (flags & EF_MODEL_BF16) != 0;
   const int kpw = bf16 ? (kp + 127) / 128 * 128 : proj_pad(kp);  // bf16 kernel: 128-column tiles
+  c->d = 0;  // no model until the last step has succeeded (never old dimensions over new buffers)
   EF_TRY(ensure(c, c->mean, (size_t)d * sizeof(float)));
   EF_TRY(ensure(c, c->W, (size_t)d * kpw * sizeof(float)));
   const hipMemcpyKind kind = (flags & EF_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   EF_HIP(c, hipMemcpyAsync(c->mean.p, mean, (size_t)d * sizeof(float), kind, c->stream), "copy mean");
-  const float* wsrc = W;
-  DevBuf tmp;
-  if (!(flags & EF_MEM_DEVICE)) {
-    EF_TRY(ensure(c, tmp, (size_t)d * k * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(tmp.p, W, (size_t)d * k * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { release(tmp); return hip_err(c, e, "copy W"); }
-    wsrc = static_cast<const float*>(tmp.p);
+  {
+    const float* wsrc = W;
+    DevBuf tmp;  // freed at the end of this block, after the synchronise (or by a hipFree that waits)
+    if (!(flags & EF_MEM_DEVICE)) {
+      EF_TRY(ensure(c, tmp, (size_t)d * k * sizeof(float)));
+      EF_HIP(c, hipMemcpyAsync(tmp.p, W, (size_t)d * k * sizeof(float), hipMemcpyHostToDevice, c->stream), "copy W");
+      wsrc = static_cast<const float*>(tmp.p);
+    }
+    EF_HIP(c, launch_pad_rows(c->stream, wsrc, d, k, d, static_cast<float*>(c->W.p), kpw), "pad W");
+    EF_HIP(c, hipStreamSynchronize(c->stream), "pad W");
   }
-  hipError_t e = launch_pad_rows(c->stream, wsrc, d, k, d, static_cast<float*>(c->W.p), kpw);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  release(tmp);
-  if (e != hipSuccess) return hip_err(c, e, "pad W");
+  c->mean_u8_ok = c->w16f_ok = false;
   if (bf16) {
     const int ldw = kpw;
     EF_TRY(ensure(c, c->W16, (size_t)ldw * d * sizeof(unsigned short)));
     EF_TRY(ensure(c, c->mean_r, (size_t)d * sizeof(float)));
     EF_TRY(ensure(c, c->corr, (size_t)ldw * sizeof(float)));
+    const size_t off = align256((size_t)d);  // the counter sits behind the bytes
+    EF_TRY(ensure(c, c->mean_u8, off + 16));
     const int nchunk = 256;
-    DevBuf cp;
+    DevBuf cp;  // the kernels that use it are synchronised below, before it goes out of scope
     EF_TRY(ensure(c, cp, (size_t)nchunk * ldw * sizeof(double)));
-    e = launch_bf16_model(c->stream, static_cast<const float*>(c->W.p), static_cast<const float*>(c->mean.p), d, ldw,
-                          static_cast<unsigned short*>(c->W16.p), static_cast<float*>(c->mean_r.p),
-                          static_cast<float*>(c->corr.p), static_cast<double*>(cp.p), nchunk);
     int bad = 1;
-    int* bad_dev = reinterpret_cast<int*>(static_cast<char*>(c->mean_u8.p));
-    if (e == hipSuccess) {
-      const size_t off = ((size_t)d + 255) & ~size_t(255);
-      const int rc = ensure(c, c->mean_u8, off + 16);
-      if (rc != EF_OK) { release(cp); return rc; }
-      bad_dev = reinterpret_cast<int*>(static_cast<char*>(c->mean_u8.p) + off);
-      e = hipMemsetAsync(bad_dev, 0, sizeof(int), c->stream);
-      if (e == hipSuccess)
-        e = launch_mean_u8(c->stream, static_cast<const float*>(c->mean_r.p), d, static_cast<uint8_t*>(c->mean_u8.p),
-                           bad_dev);
-      if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release(cp);
-    if (e != hipSuccess) return hip_err(c, e, "bf16 model");
+    int* bad_dev = reinterpret_cast<int*>(static_cast<char*>(c->mean_u8.p) + off);
+    EF_HIP(c,
+           launch_bf16_model(c->stream, static_cast<const float*>(c->W.p), static_cast<const float*>(c->mean.p), d, ldw,
+                             static_cast<unsigned short*>(c->W16.p), static_cast<float*>(c->mean_r.p),
+                             static_cast<float*>(c->corr.p), static_cast<double*>(cp.p), nchunk),
+           "bf16 model");
+    EF_HIP(c, hipMemsetAsync(bad_dev, 0, sizeof(int), c->stream), "bf16 model");
+    EF_HIP(c,
+           launch_mean_u8(c->stream, static_cast<const float*>(c->mean_r.p), d, static_cast<uint8_t*>(c->mean_u8.p),
+                          bad_dev),
+           "bf16 model");
+    EF_HIP(c, hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream), "bf16 model");
+    EF_HIP(c, hipStreamSynchronize(c->stream), "bf16 model");
     c->mean_u8_ok = bad == 0;
-    c->w16f_ok = false;
     if (bf16_frag_supported(d, ldw)) {
       EF_TRY(ensure(c, c->W16f, (size_t)ldw * d * sizeof(unsigned short)));
       EF_HIP(c, launch_bf16_frag(c->stream, static_cast<const unsigned short*>(c->W16.p), d, ldw, c->W16f.p),
@@ -660,18 +680,10 @@ int ef_project(ef_ctx* c, const void* P, int32_t dtype, int64_t b, float* F, uin
   const int64_t bpad = round_up(b, kSearchProbeTile);
   const void* Pd = nullptr;
   EF_TRY(stage_probes(c, P, dtype, b, flags, &Pd));
-  float* fdev = F;
-  if (!(flags & EF_MEM_DEVICE)) {
-    EF_TRY(ensure(c, c->feats_dev, (size_t)b * c->k * sizeof(float)));
-    fdev = static_cast<float*>(c->feats_dev.p);
-  }
-  EF_TRY(project_dev(c, Pd, dtype, b, bpad, fdev, &c->q_pad));
-  if (!(flags & EF_MEM_DEVICE)) {
-    EF_HIP(c, hipMemcpyAsync(F, fdev, (size_t)b * c->k * sizeof(float), hipMemcpyDeviceToHost, c->stream),
-           "D2H features");
-    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
-  }
-  return EF_OK;
+  Results r{(flags & EF_MEM_DEVICE) != 0, b, nullptr, nullptr, F};
+  EF_TRY(r.stage_feats(c));
+  EF_TRY(project_dev(c, Pd, dtype, b, bpad, r.fdev, &c->q_pad));
+  return r.fetch(c);
 }
 
 int ef_gallery_set(ef_ctx* c, const float* G, int64_t n, int32_t k, int64_t offset, uint32_t flags) {
@@ -696,17 +708,15 @@ int ef_gallery_set(ef_ctx* c, const float* G, int64_t n, int32_t k, int64_t offs
       EF_HIP(c, hipMemcpyAsync(c->G.p, G, (size_t)n * k * sizeof(float), kind, c->stream), "copy gallery");
     } else {
       const float* src = G;
-      DevBuf tmp;
+      DevBuf tmp;  // freed at the end of this block, after the synchronise (or by a hipFree that waits)
       if (!(flags & EF_MEM_DEVICE)) {
         EF_TRY(ensure(c, tmp, (size_t)n * k * sizeof(float)));
-        hipError_t e = hipMemcpyAsync(tmp.p, G, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { release(tmp); return hip_err(c, e, "copy gallery"); }
+        EF_HIP(c, hipMemcpyAsync(tmp.p, G, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice, c->stream),
+               "copy gallery");
         src = static_cast<const float*>(tmp.p);
       }
-      hipError_t e = launch_pad_rows(c->stream, src, n, k, n, static_cast<float*>(c->G.p), kp);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      release(tmp);
-      if (e != hipSuccess) return hip_err(c, e, "pad gallery");
+      EF_HIP(c, launch_pad_rows(c->stream, src, n, k, n, static_cast<float*>(c->G.p), kp), "pad gallery");
+      EF_HIP(c, hipStreamSynchronize(c->stream), "pad gallery");
     }
     EF_HIP(c,
            launch_gallery_aux(c->stream, static_cast<const float*>(c->G.p), n, kp,
@@ -745,21 +755,10 @@ static int search_impl(ef_ctx* c, const float* Q, int64_t b, int32_t metric, int
   }
   EF_HIP(c, launch_pad_rows(c->stream, qsrc, b, c->g_k, bpad, static_cast<float*>(c->q_pad.p), c->g_kp),
          "pad queries");
-  EF_TRY(ensure(c, c->keys, (size_t)bpad * sizeof(long long) + (size_t)b * sizeof(ef_match)));
-  long long* kdev = (dev && keys) ? reinterpret_cast<long long*>(keys) : static_cast<long long*>(c->keys.p);
-  ef_match* mdev = nullptr;
-  if (match) mdev = dev ? match : reinterpret_cast<ef_match*>(static_cast<char*>(c->keys.p) + bpad * sizeof(long long));
-  EF_TRY(search_qpad(c, bpad, b, metric, kdev, mdev));
-  if (!dev) {
-    if (keys)
-      EF_HIP(c, hipMemcpyAsync(keys, kdev, (size_t)b * sizeof(long long), hipMemcpyDeviceToHost, c->stream),
-             "D2H keys");
-    if (match)
-      EF_HIP(c, hipMemcpyAsync(match, mdev, (size_t)b * sizeof(ef_match), hipMemcpyDeviceToHost, c->stream),
-             "D2H matches");
-    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
-  }
-  return EF_OK;
+  Results r{dev, b, keys, match, nullptr};
+  EF_TRY(r.stage_keys(c, bpad));
+  EF_TRY(search_qpad(c, bpad, b, metric, r.kdev, r.mdev));
+  return r.fetch(c);
 }
 
 static int recognize_impl(ef_ctx* c, const void* P, int32_t dtype, int64_t b, int32_t metric, int64_t* keys,
@@ -777,35 +776,13 @@ static int recognize_impl(ef_ctx* c, const void* P, int32_t dtype, int64_t b, in
   const bool dev = flags & EF_MEM_DEVICE;
   const void* Pd = nullptr;
   EF_TRY(stage_probes(c, P, dtype, b, flags, &Pd));
-  float* fdev = nullptr;
-  if (feats) {
-    if (dev) {
-      fdev = feats;
-    } else {
-      EF_TRY(ensure(c, c->feats_dev, (size_t)b * c->k * sizeof(float)));
-      fdev = static_cast<float*>(c->feats_dev.p);
-    }
-  }
+  Results r{dev, b, keys, match, feats};
+  EF_TRY(r.stage_feats(c));
   int64_t bpad = 0;
-  EF_TRY(project_for_search(c, Pd, dtype, b, fdev, &bpad));
-  EF_TRY(ensure(c, c->keys, (size_t)bpad * sizeof(long long) + (size_t)b * sizeof(ef_match)));
-  long long* kdev = (dev && keys) ? reinterpret_cast<long long*>(keys) : static_cast<long long*>(c->keys.p);
-  ef_match* mdev = nullptr;
-  if (match) mdev = dev ? match : reinterpret_cast<ef_match*>(static_cast<char*>(c->keys.p) + bpad * sizeof(long long));
-  EF_TRY(search_qpad(c, bpad, b, metric, kdev, mdev));
-  if (!dev) {
-    if (keys)
-      EF_HIP(c, hipMemcpyAsync(keys, kdev, (size_t)b * sizeof(long long), hipMemcpyDeviceToHost, c->stream),
-             "D2H keys");
-    if (match)
-      EF_HIP(c, hipMemcpyAsync(match, mdev, (size_t)b * sizeof(ef_match), hipMemcpyDeviceToHost, c->stream),
-             "D2H matches");
-    if (feats)
-      EF_HIP(c, hipMemcpyAsync(feats, fdev, (size_t)b * c->k * sizeof(float), hipMemcpyDeviceToHost, c->stream),
-             "D2H features");
-    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
-  }
-  return EF_OK;
+  EF_TRY(project_for_search(c, Pd, dtype, b, r.fdev, &bpad));
+  EF_TRY(r.stage_keys(c, bpad));
+  EF_TRY(search_qpad(c, bpad, b, metric, r.kdev, r.mdev));
+  return r.fetch(c);
 }
 
 int ef_search(ef_ctx* c, const float* Q, int64_t b, int32_t metric, int64_t* keys, uint32_t flags) {
@@ -924,7 +901,7 @@ int ef_search_stats(ef_ctx* c, int64_t out[4]) {
   if (!c || !out) return EF_E_INVALID;
   (void)hipSetDevice(c->device);
   EF_HIP(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-  const int64_t fb = c->stats_prefix ? (int64_t)c->prefix_host[0] : 0;
+  const int64_t fb = c->stats_prefix ? (int64_t)*static_cast<const int*>(c->prefix_host.p) : 0;
   out[0] = c->stats_probes;
   out[1] = c->stats_prefix ? c->stats_probes - fb : 0;
   out[2] = fb;
@@ -947,8 +924,6 @@ static int timing_drain(ef_ctx* c) {
       c->t_ms[t.kernel] += ms;
       c->t_n[t.kernel] += 1;
     }
-    (void)hipEventDestroy(t.a);
-    (void)hipEventDestroy(t.b);
   }
   c->pending.clear();
   return EF_OK;

@@ -44,17 +44,6 @@ struct Bufs {
   }
 };
 
-#define EF_TRY(expr)              \
-  do {                            \
-    int _rc = (expr);             \
-    if (_rc != EF_OK) return _rc; \
-  } while (0)
-#define EF_HIP(ctx, expr, what)                          \
-  do {                                                   \
-    hipError_t _e = (expr);                              \
-    if (_e != hipSuccess) return hip_err(ctx, _e, what); \
-  } while (0)
-
 // Plain dense fp64 products of the subspace iteration with a large output (C.Q, Y.V, Q.V)
 // run on the tall matrix-core GEMM (ef_dgemm.hip), which takes B transposed: B^T is
 // written into bt_scratch (>= K x N doubles) first — at most dim x m, 32 MiB at C3, a few
@@ -379,13 +368,7 @@ int subspace_wide(ef_ctx* c, Bufs& B, const double* C, int64_t dim, int kk, int 
   // Jacobi rounds and small GEMMs leave most CUs idle); the first fine product waits for
   // them.  The guard orders the main stream after the side work on every exit, so no
   // later work (or a pool reallocation on the next fit) can overtake it.
-  struct SideJoin {
-    ef_ctx* c;
-    bool armed = false;
-    ~SideJoin() {
-      if (armed) (void)hipStreamWaitEvent(c->stream, c->fit_side_ev[1], 0);
-    }
-  } side_join{c};
+  SideJoin side_join(c->fit_side, s);
   bool side = true;
 #ifdef EF_DIAGNOSTICS  // EF_FIT_SIDE=0: the planes on the main stream at the first fine product (A/B)
   if (const char* e = getenv("EF_FIT_SIDE")) side = atoi(e) != 0;
@@ -395,14 +378,9 @@ int subspace_wide(ef_ctx* c, Bufs& B, const double* C, int64_t dim, int kk, int 
     EF_TRY(B.get(c, cq_i8_work_bytes(dim, m), &cq_work));
   }
   if (cq_i8 && side) {
-    if (!c->fit_side) EF_HIP(c, hipStreamCreateWithFlags(&c->fit_side, hipStreamNonBlocking), "fit side stream");
-    for (int i = 0; i < 2; ++i)
-      if (!c->fit_side_ev[i]) EF_HIP(c, hipEventCreateWithFlags(&c->fit_side_ev[i], hipEventDisableTiming), "fit event");
-    EF_HIP(c, hipEventRecord(c->fit_side_ev[0], s), "C ready");
-    EF_HIP(c, hipStreamWaitEvent(c->fit_side, c->fit_side_ev[0], 0), "side waits C");
-    EF_HIP(c, launch_cq_i8_planes(c->fit_side, C, dim, cq_planes), "C (int8 digit planes)");
-    EF_HIP(c, hipEventRecord(c->fit_side_ev[1], c->fit_side), "planes ready");
-    side_join.armed = true;
+    EF_HIP(c, side_join.fork(), "fit side stream (C ready)");
+    EF_HIP(c, launch_cq_i8_planes(c->fit_side.s, C, dim, cq_planes), "C (int8 digit planes)");
+    EF_HIP(c, side_join.done(), "planes ready");
   }
   std::vector<double> th(m), prev(m, 0.0);
   bool have_prev = false, prev_fine = false;
@@ -462,7 +440,7 @@ int subspace_wide(ef_ctx* c, Bufs& B, const double* C, int64_t dim, int kk, int 
       hipLaunchKernelGGL(f32_to_f64_shift_kernel, dim3(ew_blocks), dim3(256), 0, s, Y32, Q, dim * m, sigma, Y);
     } else if (cq_i8) {
       if (!cq_ready) {
-        if (side) EF_HIP(c, hipStreamWaitEvent(s, c->fit_side_ev[1], 0), "planes ready");
+        if (side) EF_HIP(c, side_join.join(), "planes ready");
         else EF_HIP(c, launch_cq_i8_planes(s, C, dim, cq_planes), "C (int8 digit planes)");
       }
       cq_ready = true;
@@ -1210,19 +1188,13 @@ extern "C" int ef_chol_inv(ef_ctx* c, const double* G, int32_t m, int64_t ldg, d
     return set_err(c, EF_E_INVALID, "ef_chol_inv: bad arguments (1 <= m <= 256, ldg >= m)");
   EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
+  // locals: every return below follows the synchronise, or a failed call after which the
+  // frees themselves wait for the device
   DevBuf dG, dL, dW, dI;
-  auto done = [&](int rc) {
-    release(dG);
-    release(dL);
-    release(dW);
-    release(dI);
-    return rc;
-  };
-  int rc = ensure(c, dG, (size_t)m * ldg * sizeof(double));
-  if (rc == EF_OK) rc = ensure(c, dL, (size_t)m * m * sizeof(double));
-  if (rc == EF_OK) rc = ensure(c, dW, chol_inv_work_elems(m) * sizeof(double));
-  if (rc == EF_OK) rc = ensure(c, dI, sizeof(int));
-  if (rc != EF_OK) return done(rc);
+  EF_TRY(ensure(c, dG, (size_t)m * ldg * sizeof(double)));
+  EF_TRY(ensure(c, dL, (size_t)m * m * sizeof(double)));
+  EF_TRY(ensure(c, dW, chol_inv_work_elems(m) * sizeof(double)));
+  EF_TRY(ensure(c, dI, sizeof(int)));
   hipError_t e = hipMemcpyAsync(dG.p, G, (size_t)m * ldg * sizeof(double), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(dL.p, Li, (size_t)m * m * sizeof(double), hipMemcpyHostToDevice, s);
   if (e == hipSuccess)
@@ -1232,7 +1204,7 @@ extern "C" int ef_chol_inv(ef_ctx* c, const double* G, int32_t m, int64_t ldg, d
   if (e == hipSuccess) e = hipMemcpyAsync(Li, dL.p, (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(&hinfo, dI.p, sizeof(int), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return done(hip_err(c, e, "ef_chol_inv"));
+  if (e != hipSuccess) return hip_err(c, e, "ef_chol_inv");
   *info = hinfo;
-  return done(EF_OK);
+  return EF_OK;
 }

@@ -35,23 +35,13 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "ef_internal.hpp"
 
 namespace ef {
-
-#define EF_TRY(expr)              \
-  do {                            \
-    int _rc = (expr);             \
-    if (_rc != EF_OK) return _rc; \
-  } while (0)
-#define EF_HIP(ctx, expr, what)                          \
-  do {                                                   \
-    hipError_t _e = (expr);                              \
-    if (_e != hipSuccess) return hip_err(ctx, _e, what); \
-  } while (0)
 
 struct HaarFeat {
   int x[3], y[3], w[3], h[3];
@@ -450,12 +440,7 @@ struct HaarState {
 };
 
 void haar_release(ef_ctx* c) {
-  if (!c || !c->haar) return;
-  HaarState* h = static_cast<HaarState*>(c->haar);
-  DevBuf* bufs[] = {&h->stages, &h->recs, &h->pix, &h->ii1,      &h->ii2,     &h->res, &h->vn,
-                    &h->layers, &h->rowstart, &h->work, &h->cand, &h->counters, &h->frame, &h->desc};
-  for (DevBuf* b : bufs) release(*b);
-  delete h;
+  delete c->haar;
   c->haar = nullptr;
 }
 
@@ -603,8 +588,8 @@ int ef_haar_set_cascade(ef_ctx* c, int32_t win_w, int32_t win_h, int32_t n_featu
   }
   EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
   haar_release(c);
-  HaarState* h = new HaarState();
-  c->haar = h;
+  // published in the context only by the last line: a failed upload leaves it without a cascade
+  std::unique_ptr<HaarState> h(new HaarState());
   h->ww = win_w;
   h->wh = win_h;
   h->nstages = n_stages;
@@ -638,6 +623,7 @@ int ef_haar_set_cascade(ef_ctx* c, int32_t win_w, int32_t win_h, int32_t n_featu
   }
   EF_TRY(ensure(c, h->recs, rc.size() * sizeof(HaarRec)));
   EF_HIP(c, hipMemcpy(h->recs.p, rc.data(), rc.size() * sizeof(HaarRec), hipMemcpyHostToDevice), "H2D records");
+  c->haar = h.release();
   return EF_OK;
 }
 
@@ -646,7 +632,7 @@ int ef_haar_detect(ef_ctx* c, const uint8_t* gray, int32_t H, int32_t W, int64_t
                    int32_t* rects_out, int32_t max_rects, int32_t* n_rects, int32_t* cand_out, int32_t max_cand,
                    int32_t* n_cand, uint32_t flags) {
   if (!c) return EF_E_INVALID;
-  HaarState* h = static_cast<HaarState*>(c->haar);
+  HaarState* h = c->haar;
   if (!h) return set_err(c, EF_E_STATE, "ef_haar_detect: call ef_haar_set_cascade first");
   if (!gray || H < 1 || W < 1 || ld < W || !(scale_factor > 1.0) || !n_rects || (max_rects > 0 && !rects_out))
     return set_err(c, EF_E_INVALID, "ef_haar_detect: bad arguments");

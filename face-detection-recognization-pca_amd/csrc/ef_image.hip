@@ -38,6 +38,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <memory>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -50,17 +51,6 @@ namespace ef {
 
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-#define EF_TRY(expr)              \
-  do {                            \
-    int _rc = (expr);             \
-    if (_rc != EF_OK) return _rc; \
-  } while (0)
-#define EF_HIP(ctx, expr, what)                          \
-  do {                                                   \
-    hipError_t _e = (expr);                              \
-    if (_e != hipSuccess) return hip_err(ctx, _e, what); \
-  } while (0)
 
 // ------------------------------------------------------------------------ ingest
 struct ImgDesc {
@@ -815,16 +805,26 @@ struct TmState {
 };
 
 void tm_release(ef_ctx* c) {
-  if (!c || !c->tm) return;
-  TmState* t = static_cast<TmState*>(c->tm);
-  DevBuf* bufs[] = {&t->raw,   &t->scaled, &t->bands, &t->d_probs, &t->d_pieces, &t->d_works, &t->d_stat,
-                    &t->parts, &t->f8,     &t->ii1,   &t->ii2,     &t->keys,     &t->frame_stage, &t->maps};
-  for (DevBuf* b : bufs) release(*b);
-  delete t;
+  delete c->tm;
   c->tm = nullptr;
 }
 
-static int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+// The integral images' row pass on the main stream, then their column pass: with `side` on
+// the side stream forked behind the row pass (the caller joins it before the score kernel).
+template <class T>
+static int tm_integrals(ef_ctx* c, TmState* t, SideJoin& col_join, bool side, const uint8_t* f, int64_t frame_ld) {
+  const int H = t->H, W = t->W;
+  const dim3 rows((unsigned)((H + 1 + 3) / 4)), cols((unsigned)((W + 1 + kColW - 1) / kColW));
+  T* ii1 = static_cast<T*>(t->ii1.p);
+  T* ii2 = static_cast<T*>(t->ii2.p);
+  hipLaunchKernelGGL(tm_rows_kernel<T>, rows, dim3(256), 0, c->stream, f, H, W, frame_ld,
+                     static_cast<int8_t*>(t->f8.p), t->pitch, ii1, ii2, static_cast<unsigned long long*>(t->keys.p),
+                     t->nprob);
+  if (side) EF_HIP(c, col_join.fork(), "tm side stream (rows done)");
+  hipLaunchKernelGGL(tm_cols_kernel<T>, cols, dim3(1024), 0, side ? c->tm_side.s.p : c->stream, H, W, ii1, ii2);
+  if (side) EF_HIP(c, col_join.done(), "cols done");
+  return EF_OK;
+}
 
 // Column groups of a tile whose row band has nrb live 32-row blocks: 4 (32 x 512) for one,
 // 2 (64 x 256) for two, when the kernel's A ring holds that shape's window (WROWS + 6
@@ -868,9 +868,9 @@ int ef_preprocess(ef_ctx* c, const uint8_t* data, const int64_t* offsets, const 
     src_bytes = end > src_bytes ? end : src_bytes;
   }
   // metadata + (host) pixels staged in one scratch buffer
-  const size_t dbytes = rup((int64_t)desc.size() * sizeof(ImgDesc), 256);
+  const size_t dbytes = round_up((int64_t)desc.size() * sizeof(ImgDesc), 256);
   const size_t obytes = (size_t)count * out_h * out_w;
-  const size_t need = dbytes + (dev ? 0 : rup(src_bytes, 256) + rup(obytes, 256));
+  const size_t need = dbytes + (dev ? 0 : round_up(src_bytes, 256) + round_up(obytes, 256));
   EF_TRY(ensure(c, c->p_stage, need));
   char* base = static_cast<char*>(c->p_stage.p);
   ImgDesc* ddesc = reinterpret_cast<ImgDesc*>(base);
@@ -882,7 +882,7 @@ int ef_preprocess(ef_ctx* c, const uint8_t* data, const int64_t* offsets, const 
     uint8_t* s = reinterpret_cast<uint8_t*>(base + dbytes);
     EF_HIP(c, hipMemcpyAsync(s, data, src_bytes, hipMemcpyHostToDevice, c->stream), "H2D images");
     src = s;
-    dst = reinterpret_cast<uint8_t*>(base + dbytes + rup(src_bytes, 256));
+    dst = reinterpret_cast<uint8_t*>(base + dbytes + round_up(src_bytes, 256));
   }
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_INGEST, &tev);
@@ -904,7 +904,7 @@ int ef_preprocess(ef_ctx* c, const uint8_t* data, const int64_t* offsets, const 
 int ef_tm_sums_bits(int32_t frame_h, int32_t frame_w, int64_t max_template_area) {
   if (frame_h <= 0 || frame_w <= 0 || max_template_area < 0) return EF_E_INVALID;
   if (max_template_area >= (int64_t)1 << 18) return 64;
-  if ((int64_t)(frame_h + 1) * (int64_t)(frame_w + 1) >= (int64_t)1 << 30) return 64;
+  if (((int64_t)frame_h + 1) * ((int64_t)frame_w + 1) >= (int64_t)1 << 30) return 64;
   return 32;
 }
 
@@ -918,13 +918,13 @@ int ef_tm_prepare(ef_ctx* c, const uint8_t* templ_data, const int64_t* templ_off
     return set_err(c, EF_E_INVALID, "ef_tm_prepare: bad arguments");
   if (n_problems > 65535) return set_err(c, EF_E_INVALID, "ef_tm_prepare: at most 65535 problems");
   EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
-  tm_release(c);
-  TmState* t = new TmState();
-  c->tm = t;
+  tm_release(c);  // first, so the old and the new state never coexist in device memory
+  // published in the context only by the last line: an early return leaves it without a localiser
+  std::unique_ptr<TmState> t(new TmState());
   t->H = frame_h;
   t->W = frame_w;
   t->nprob = n_problems;
-  t->pitch = rup((int64_t)frame_w + 640, 64);  // a 512-column tile's rows read past the frame
+  t->pitch = round_up((int64_t)frame_w + 640, 64);  // a 512-column tile's rows read past the frame
   t->ii64 = c->opt_tm_int64 != 0;
   if (ef_tm_sums_bits(frame_h, frame_w, 1) == 64) t->ii64 = true;  // frame-size rule alone
   const bool dev = flags & EF_MEM_DEVICE;
@@ -956,7 +956,7 @@ int ef_tm_prepare(ef_ctx* c, const uint8_t* templ_data, const int64_t* templ_off
     pb.wr = frame_w - tw + 1;
     pb.tmpl_off = scaled_bytes;
     rd.push_back(ImgDesc{templ_offsets[ti], scaled_bytes, templ_h[ti], templ_w[ti], 1, th, tw, 0});
-    scaled_bytes += rup((int64_t)th * tw, 16);
+    scaled_bytes += round_up((int64_t)th * tw, 16);
     const int npiece = (tw + piece_w - 1) / piece_w;
     const int nchunk = (th + kTmChunk - 1) / kTmChunk;
     pb.nparts = npiece * nchunk;
@@ -1051,14 +1051,16 @@ int ef_tm_prepare(ef_ctx* c, const uint8_t* templ_data, const int64_t* templ_off
                        static_cast<const TmPiece*>(t->d_pieces.p), static_cast<uint8_t*>(t->bands.p));
     EF_HIP(c, hipGetLastError(), "template prepare kernels");
   }
-  EF_HIP(c, hipStreamSynchronize(s), "sync");  // host vectors and staged descriptors go out of scope
+  // host vectors and staged descriptors go out of scope (on an early return t's frees wait)
+  EF_HIP(c, hipStreamSynchronize(s), "sync");
+  c->tm = t.release();
   return EF_OK;
 }
 
 int ef_tm_match(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, float* best_out, int32_t* x_out, int32_t* y_out,
                 float* maps_out, uint32_t flags) {
   if (!c) return EF_E_INVALID;
-  TmState* t = static_cast<TmState*>(c->tm);
+  TmState* t = c->tm;
   if (!t) return set_err(c, EF_E_STATE, "ef_tm_match: call ef_tm_prepare first");
   if (!frame || frame_ld < t->W) return set_err(c, EF_E_INVALID, "ef_tm_match: bad frame");
   EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
@@ -1075,42 +1077,17 @@ int ef_tm_match(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, float* best_o
   unsigned long long* keys = static_cast<unsigned long long*>(t->keys.p);
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_TMATCH, &tev);
-  const dim3 rgrid((unsigned)((H + 1 + 3) / 4)), cgrid((unsigned)((W + 1 + kColW - 1) / kColW));
   // The integral images' column pass runs on a side stream beside the correlation kernel
   // (it needs only the row pass; the score kernel joins both): its 8 KiB blocks fit next to
-  // a correlation workgroup's 147 KiB of LDS.
+  // a correlation workgroup's 147 KiB of LDS.  The guard joins it on every other exit too,
+  // so the next call's row pass cannot write ii1 / ii2 under it.
   bool side = t->nprob > 0 && t->nwork > 0;
 #ifdef EF_DIAGNOSTICS
   if (std::getenv("EF_TM_NOSIDE")) side = false;  // A/B: column pass in line
 #endif
-  if (side) {
-    if (!c->tm_side) EF_HIP(c, hipStreamCreateWithFlags(&c->tm_side, hipStreamNonBlocking), "tm side stream");
-    for (int i = 0; i < 2; ++i)
-      if (!c->tm_side_ev[i]) EF_HIP(c, hipEventCreateWithFlags(&c->tm_side_ev[i], hipEventDisableTiming), "tm event");
-  }
-  hipStream_t cs = side ? c->tm_side : s;  // the column pass's stream
-  if (t->ii64) {
-    long long* ii1 = static_cast<long long*>(t->ii1.p);
-    long long* ii2 = static_cast<long long*>(t->ii2.p);
-    hipLaunchKernelGGL(tm_rows_kernel<long long>, rgrid, dim3(256), 0, s, f, H, W, frame_ld, f8, t->pitch, ii1, ii2,
-                       keys, t->nprob);
-    if (side) {
-      EF_HIP(c, hipEventRecord(c->tm_side_ev[0], s), "rows done");
-      EF_HIP(c, hipStreamWaitEvent(cs, c->tm_side_ev[0], 0), "side waits rows");
-    }
-    hipLaunchKernelGGL(tm_cols_kernel<long long>, cgrid, dim3(1024), 0, cs, H, W, ii1, ii2);
-  } else {
-    unsigned* ii1 = static_cast<unsigned*>(t->ii1.p);
-    unsigned* ii2 = static_cast<unsigned*>(t->ii2.p);
-    hipLaunchKernelGGL(tm_rows_kernel<unsigned>, rgrid, dim3(256), 0, s, f, H, W, frame_ld, f8, t->pitch, ii1, ii2,
-                       keys, t->nprob);
-    if (side) {
-      EF_HIP(c, hipEventRecord(c->tm_side_ev[0], s), "rows done");
-      EF_HIP(c, hipStreamWaitEvent(cs, c->tm_side_ev[0], 0), "side waits rows");
-    }
-    hipLaunchKernelGGL(tm_cols_kernel<unsigned>, cgrid, dim3(1024), 0, cs, H, W, ii1, ii2);
-  }
-  if (side) EF_HIP(c, hipEventRecord(c->tm_side_ev[1], cs), "cols done");
+  SideJoin col_join(c->tm_side, s);
+  EF_TRY(t->ii64 ? tm_integrals<long long>(c, t, col_join, side, f, frame_ld)
+                 : tm_integrals<unsigned>(c, t, col_join, side, f, frame_ld));
   if (t->nprob > 0) {
     if (t->nwork > 0) {
       bool narrow = t->max_nkb <= 5;
@@ -1132,7 +1109,7 @@ int ef_tm_match(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, float* best_o
         maps = static_cast<float*>(t->maps.p);
       }
     }
-    if (side) EF_HIP(c, hipStreamWaitEvent(s, c->tm_side_ev[1], 0), "score waits cols");
+    EF_HIP(c, col_join.join(), "score waits cols");
     const int64_t sblk = 64;  // row-strided blocks per problem
     const dim3 sgrid((unsigned)sblk, (unsigned)t->nprob);
     const TmProblem* dp = static_cast<const TmProblem*>(t->d_probs.p);
@@ -1172,7 +1149,7 @@ int ef_tm_match(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, float* best_o
 
 int ef_tm_info(ef_ctx* c, int32_t* n_problems, int64_t* map_elems, int32_t* result_h, int32_t* result_w) {
   if (!c) return EF_E_INVALID;
-  TmState* t = static_cast<TmState*>(c->tm);
+  const TmState* t = c->tm;
   if (!t) return set_err(c, EF_E_STATE, "ef_tm_info: call ef_tm_prepare first");
   if (n_problems) *n_problems = t->nprob;
   if (map_elems) *map_elems = t->map_total;

@@ -11,7 +11,12 @@
 
 #include "../../include/eigenface.h"
 
+struct ef_ctx;
+
 namespace ef {
+
+int set_err(ef_ctx* c, int code, const std::string& msg);
+int hip_err(ef_ctx* c, hipError_t e, const char* what);
 
 // ---- padded widths ------------------------------------------------------------------
 // Gallery / probe features are stored with k zero-padded to KP in {16,32,64,128,256,512},
@@ -78,20 +83,124 @@ struct SearchPiece {
   int64_t off, b, bpad;
 };
 
-// ---- device buffer ------------------------------------------------------------------
-struct DevBuf {
-  void* p = nullptr;
+// ---- error propagation --------------------------------------------------------------
+#define EF_TRY(expr)              \
+  do {                            \
+    int _rc = (expr);             \
+    if (_rc != EF_OK) return _rc; \
+  } while (0)
+#define EF_HIP(ctx, expr, what)                              \
+  do {                                                       \
+    hipError_t _e = (expr);                                  \
+    if (_e != hipSuccess) return ef::hip_err(ctx, _e, what); \
+  } while (0)
+
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// ---- owning handles -----------------------------------------------------------------
+// Move-only owner of one HIP handle (p; bytes for memory).  The destructor and reset() free
+// through Free, the only caller of the HIP free / destroy functions (ef_api.hip); an empty
+// handle makes no HIP call, and a move leaves its source empty.
+template <class H, void (*Free)(H)>
+struct Owned {
+  H p = nullptr;
   size_t bytes = 0;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  Owned& operator=(Owned&& o) noexcept {
+    if (this != &o) { reset(); p = std::exchange(o.p, nullptr); bytes = std::exchange(o.bytes, 0); }
+    return *this;
+  }
+  ~Owned() { reset(); }
+  void reset() {
+    if (p) Free(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  operator H() const { return p; }
+};
+void free_device(void* p);
+void free_pinned(void* p);
+void free_event(hipEvent_t e);
+void free_stream(hipStream_t s);
+using DevBuf = Owned<void*, free_device>;      // grown with ensure(), freed early with release()
+using PinnedBuf = Owned<void*, free_pinned>;   // pinned_alloc()
+using Event = Owned<hipEvent_t, free_event>;   // created on first use: event_get()
+using Stream = Owned<hipStream_t, free_stream>;  // created on first use: stream_get()
+
+// An existing handle is kept.  A new event has timing disabled unless flags says otherwise
+// and, with record_on, is recorded there at once (waits on it pass until it is re-recorded).
+hipError_t event_get(Event& e, hipStream_t record_on = nullptr, unsigned flags = hipEventDisableTiming);
+hipError_t stream_get(Stream& s);                     // non-blocking
+hipError_t pinned_alloc(PinnedBuf& b, size_t bytes);  // frees what b held first
+
+// A side stream with the two events that order it against a main stream.
+struct SideStream {
+  Stream s;
+  Event forked, done;
+};
+// Fork / join of one call's side work.  fork() makes the side stream wait for what the main
+// stream has queued so far, done() marks the end of the side work, join() makes the main
+// stream wait for it.  Once forked, the destructor joins on every exit that did not, so
+// nothing queued on the main stream later (or a free after a synchronise) overtakes it.
+class SideJoin {
+ public:
+  SideJoin(SideStream& side, hipStream_t main) : side_(side), main_(main) {}
+  SideJoin(const SideJoin&) = delete;
+  ~SideJoin() { (void)join(); }
+  hipError_t fork();
+  hipError_t done();
+  hipError_t join();
+
+ private:
+  SideStream& side_;
+  hipStream_t main_;
+  bool forked_ = false, done_ = false;
 };
 
 struct TimerEvt {
-  hipEvent_t a, b;
-  int kernel;
+  Event a, b;
+  int kernel = -1;
 };
+
+// ---- workspace carve-out ------------------------------------------------------------
+// Hands out consecutive 256-byte-aligned typed pieces of one allocation.  The same carve
+// function runs twice — on a null base for the total, then on the allocation — so the sizes
+// and the pointers cannot disagree.
+struct Carve {
+  void* base = nullptr;
+  size_t total = 0;
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(static_cast<char*>(base) + total) : nullptr;
+    total += align256(count * sizeof(T));
+    return p;
+  }
+};
+// parts: the largest nchunks x bpad of the call's pieces; bpad: its largest piece (the
+// braces evaluate left to right, in member order; match stays null)
+inline SearchWs carve_search_ws(Carve& cv, size_t parts, size_t bpad) {
+  return SearchWs{cv.take<long long>(parts), cv.take<float>(parts), cv.take<int>(4), cv.take<int>(bpad),
+                  cv.take<float>(bpad), cv.take<int>(bpad * kCandMax), cv.take<int>(bpad), nullptr};
+}
+inline PrefixWs carve_prefix_ws(Carve& cv, size_t bpad, int k1, int kp) {
+  return PrefixWs{cv.take<float>(bpad * k1), cv.take<float>(bpad * kp), cv.take<int>(bpad),
+                  cv.take<long long>(bpad), cv.take<ef_match>(bpad)};
+}
+
+struct TmState;    // template-localiser state (ef_image.hip)
+struct HaarState;  // Haar cascade state (ef_haar.hip)
 
 }  // namespace ef
 
+// Every buffer, pinned block, event and stream below is an owning handle: `delete ctx` frees
+// all of it.  Members go in reverse declaration order, and the streams and events are declared
+// last, after every buffer whose work they order, so they go first: a stream destroyed with
+// work queued drains on its own, and the hipFree of a buffer waits for the device.
 struct ef_ctx {
+  ef_ctx() = default;
+  ~ef_ctx();  // the localiser, cascade and communicator first, then the members
   int device = 0;
   // tunables set with ef_set_option (include/eigenface.h EF_OPT_*)
   int64_t opt_fit_max_iters = 500;
@@ -104,8 +213,7 @@ struct ef_ctx {
   int g3_layout = 0;  // what G3 holds: 1 split (hi + lo) rows, 3 single-bf16 rows
   int64_t opt_jpeg_part_files = 8192;
   int64_t opt_fit_chebyshev = 1;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;  // own_stream or the caller's (ef_set_stream): not owned
   std::string err;
 
   // recognition model (p - mean) . W
@@ -142,8 +250,7 @@ struct ef_ctx {
   ef::DevBuf prefix_ws;  // per-call scratch of the prefix path (ef::PrefixWs carve-out)
   // counters of the last prefix search, copied to pinned host memory behind the search
   // ([0] probes sent to the full-k scan); the next search reads them once prefix_ev has passed
-  int* prefix_host = nullptr;
-  hipEvent_t prefix_ev = nullptr;
+  ef::PinnedBuf prefix_host;  // int[4]
   bool prefix_ev_pending = false;
   int64_t prefix_ev_tiles = 0;  // probe tiles of the search prefix_ev belongs to
   int prefix_skip_left = 0;     // searches the guard still keeps off the prefix scan
@@ -170,24 +277,12 @@ struct ef_ctx {
   // decode's kernels (a call on another stream, or a reallocation, waits for it).
   ef::DevBuf jpeg_ws, jpeg_out, jpeg_rows;
   ef::DevBuf jpeg_up[2];
-  void* jpeg_pinned[2] = {nullptr, nullptr};
-  size_t jpeg_pinned_bytes[2] = {0, 0};
-  hipEvent_t jpeg_up_done[2] = {nullptr, nullptr};
-  hipEvent_t jpeg_ws_free[2] = {nullptr, nullptr};
-  hipEvent_t jpeg_done = nullptr;
-  hipStream_t jpeg_copy = nullptr;  // upload stream (created on first use)
-  // the fit's side stream (created on first use): work off the critical path of the
-  // subspace iteration, e.g. the int8 digit planes of C during the coarse phase
-  hipStream_t fit_side = nullptr;
-  hipEvent_t fit_side_ev[2] = {nullptr, nullptr};
-  // the template localiser's side stream (created on first use): the integral images' column
-  // pass runs beside the correlation kernel
-  hipStream_t tm_side = nullptr;
-  hipEvent_t tm_side_ev[2] = {nullptr, nullptr};
+  ef::PinnedBuf jpeg_pinned[2];
   int jpeg_slot = 0;                // slot of the next staged batch
 
-  void* tm = nullptr;    // template-localiser state (ef_image.hip TmState), ef_tm_prepare
-  void* haar = nullptr;  // Haar cascade state (ef_haar.hip HaarState), ef_haar_set_cascade
+  // published only once completely built (ef_tm_prepare, ef_haar_set_cascade); null otherwise
+  ef::TmState* tm = nullptr;
+  ef::HaarState* haar = nullptr;
 
   // multi-GPU: RCCL communicator (ef_comm_init), null when single-rank
   void* comm = nullptr;
@@ -197,19 +292,30 @@ struct ef_ctx {
   ef::DevBuf q_local;      // float[cpad][kp] this rank's slice of the projected probes
 
   bool timing = false;
-  std::vector<ef::TimerEvt> pending;
   double t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int64_t t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+  // streams and events, all created on first use except own_stream (ef_create)
+  ef::Stream own_stream;
+  ef::Stream jpeg_copy;  // upload stream
+  ef::Event jpeg_up_done[2], jpeg_ws_free[2], jpeg_done;
+  ef::Event prefix_ev;
+  // the fit's side stream: work off the critical path of the subspace iteration, e.g. the
+  // int8 digit planes of C during the coarse phase
+  ef::SideStream fit_side;
+  // the template localiser's side stream: the integral images' column pass runs beside the
+  // correlation kernel
+  ef::SideStream tm_side;
+  std::vector<ef::TimerEvt> pending;  // timed kernels not yet read by ef_timing_get
 };
 
 namespace ef {
 
-int set_err(ef_ctx* c, int code, const std::string& msg);
+// delete the context's localiser / cascade state, if any
 void tm_release(ef_ctx* c);
 void haar_release(ef_ctx* c);
-int hip_err(ef_ctx* c, hipError_t e, const char* what);
 int ensure(ef_ctx* c, DevBuf& b, size_t bytes);
-void release(DevBuf& b);
+inline void release(DevBuf& b) { b.reset(); }
 void timer_begin(ef_ctx* c, int kernel, TimerEvt* t);
 void timer_end(ef_ctx* c, TimerEvt* t);
 // events created but not recorded: the launcher records them itself around the kernels

@@ -1531,7 +1531,6 @@ struct Staged {
 // only this slot and B, so it may run on a host thread while another slot's batch decodes.
 // Returns EF_OK, or an error code with the message in *err (the caller records it).
 int jpeg_ensure(ef_ctx* c, DevBuf& b, size_t bytes);
-hipError_t jpeg_event(hipEvent_t* ev, hipStream_t record_on);
 constexpr int kUploadPhases = 4;  // early upload: destuff + upload pieces per batch
 bool jpeg_early_upload() {
 #ifdef EF_DIAGNOSTICS  // EF_JPEG_EARLY_UP=0: the whole upload after staging, round 5's order (A/B)
@@ -1542,42 +1541,35 @@ bool jpeg_early_upload() {
 int stage_batch(ef_ctx* c, int slot, Batch& B, const uint8_t* data, const int64_t* offsets, Staged& S,
                 std::string* err, int64_t chunk_bits = 0, bool early_upload = false) {
   StageTimer tm;
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   size_t off = 0;
   S.slot = slot;
-  S.o_words = off; off += al((size_t)B.words * 4 + 32);  // BitStream reads up to 8 words past a segment
-  S.o_imgs = off; off += al(B.imgs.size() * sizeof(JImage));
-  S.o_pool = off; off += al(std::max<size_t>(B.T.huff.size(), 1) * sizeof(HuffTab));
-  S.o_q = off; off += al(std::max<size_t>(B.T.quant.size(), 1) * 2);
-  S.o_seg = off; off += al(B.segs.size() * sizeof(JSeg));
-  S.o_bs = off; off += al(B.block_start.size() * 8);
-  S.o_ic = off; off += al(B.ic.size() * 4);
-  S.o_ps = off; off += al(B.row_start.size() * 8);
-  S.o_desc = off; off += al(B.file_img.size() * 4);
+  S.o_words = off; off += align256((size_t)B.words * 4 + 32);  // BitStream reads up to 8 words past a segment
+  S.o_imgs = off; off += align256(B.imgs.size() * sizeof(JImage));
+  S.o_pool = off; off += align256(std::max<size_t>(B.T.huff.size(), 1) * sizeof(HuffTab));
+  S.o_q = off; off += align256(std::max<size_t>(B.T.quant.size(), 1) * 2);
+  S.o_seg = off; off += align256(B.segs.size() * sizeof(JSeg));
+  S.o_bs = off; off += align256(B.block_start.size() * 8);
+  S.o_ic = off; off += align256(B.ic.size() * 4);
+  S.o_ps = off; off += align256(B.row_start.size() * 8);
+  S.o_desc = off; off += align256(B.file_img.size() * 4);
   S.o_cseg = off;  // chunk table last: its size is known only after destuffing
   {  // make_chunks' bound: every segment has <= nbits / chunk_bits + 1 chunks
     const int64_t cb_min = (c->opt_jpeg_chunk_bits > 0 || chunk_bits > 0) ? 64 : 2048;
-    off += al(((size_t)(B.words * 32 / cb_min) + B.segs.size() + 1) * 4);
+    off += align256(((size_t)(B.words * 32 / cb_min) + B.segs.size() + 1) * 4);
   }
   S.pin_need = off;
   if (c->jpeg_up_done[slot]) {  // the upload that last read this slot
     const hipError_t e = hipEventSynchronize(c->jpeg_up_done[slot]);
     if (e != hipSuccess) { *err = hipGetErrorString(e); return EF_E_HIP; }
   }
-  if (c->jpeg_pinned_bytes[slot] < S.pin_need) {
-    if (c->jpeg_pinned[slot]) (void)hipHostFree(c->jpeg_pinned[slot]);
-    c->jpeg_pinned[slot] = nullptr;
-    c->jpeg_pinned_bytes[slot] = 0;
-    const size_t want = S.pin_need + S.pin_need / 4 + 4096;
-    const hipError_t e = hipHostMalloc(&c->jpeg_pinned[slot], want, hipHostMallocDefault);
+  if (c->jpeg_pinned[slot].bytes < S.pin_need) {
+    const hipError_t e = pinned_alloc(c->jpeg_pinned[slot], S.pin_need + S.pin_need / 4 + 4096);
     if (e != hipSuccess) {
-      c->jpeg_pinned[slot] = nullptr;
       *err = std::string("hipHostMalloc (jpeg staging): ") + hipGetErrorString(e);
       return EF_E_HIP;
     }
-    c->jpeg_pinned_bytes[slot] = want;
   }
-  char* h = static_cast<char*>(c->jpeg_pinned[slot]);
+  char* h = static_cast<char*>(c->jpeg_pinned[slot].p);
   S.h = h;
   tm.mark("pinned");
   S.words_up = 0;
@@ -1589,7 +1581,7 @@ int stage_batch(ef_ctx* c, int slot, Batch& B, const uint8_t* data, const int64_
   // not reallocate): the first call at a new size uploads whole, as without early upload.
   if (early_upload && c->jpeg_copy && !B.segs.empty() && c->jpeg_up[slot].p &&
       c->jpeg_up[slot].bytes >= S.pin_need + 16) {
-    hipError_t e = jpeg_event(&c->jpeg_ws_free[slot], c->stream);
+    hipError_t e = event_get(c->jpeg_ws_free[slot], c->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(c->jpeg_copy, c->jpeg_ws_free[slot], 0);
     char* up = static_cast<char*>(c->jpeg_up[slot].p);
     const size_t nseg = B.segs.size();
@@ -1634,13 +1626,6 @@ int jpeg_ensure(ef_ctx* c, DevBuf& b, size_t bytes) {
   return ensure(c, b, bytes);
 }
 
-hipError_t jpeg_event(hipEvent_t* ev, hipStream_t record_on) {
-  if (*ev) return hipSuccess;
-  hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-  if (e == hipSuccess && record_on) e = hipEventRecord(*ev, record_on);  // waits on it pass until re-recorded
-  return e;
-}
-
 // Device half: upload a staged batch (copy stream), entropy-decode and IDCT it, then either
 // colour-convert it into dout (device), each image at its out_off, or — for the ingest
 // (rz_dst) — resize every file of the batch to an (oh x ow) grey row of rz_dst straight from
@@ -1652,25 +1637,23 @@ int launch_batch(ef_ctx* c, Batch& B, const Staged& S, uint8_t* dout, uint8_t* r
                  int ow = 0) {
   hipStream_t s = c->stream;
   StageTimer tm;
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   const int slot = S.slot;
   const int nchunks = (int)B.chunk_seg.size();
   size_t off = 0;
-  const size_t o_S = off; off += al((size_t)nchunks * 8);
-  const size_t o_E0 = off; off += al((size_t)nchunks * 8);
-  const size_t o_E1 = off; off += al((size_t)nchunks * 8);
-  const size_t o_cnt = off; off += al((size_t)nchunks * 16);
-  const size_t o_G = off; off += al((size_t)nchunks * 4);
-  const size_t o_P = off; off += al((size_t)nchunks * 12);
-  const size_t o_flag = off; off += al(4 * (kDeviceRounds + 2));
-  const size_t o_cps = off; off += al((size_t)nchunks * kCheckpoints * sizeof(Checkpoint));
-  const size_t o_coef = off; off += al((size_t)B.coef_blocks * 64 * 2);
-  const size_t o_planes = off; off += al((size_t)B.plane_bytes + 16);
-  hipError_t e = hipSuccess;
-  if (!c->jpeg_copy) e = hipStreamCreateWithFlags(&c->jpeg_copy, hipStreamNonBlocking);
-  if (e == hipSuccess) e = jpeg_event(&c->jpeg_up_done[slot], nullptr);
-  if (e == hipSuccess) e = jpeg_event(&c->jpeg_ws_free[slot], s);
-  if (e == hipSuccess) e = jpeg_event(&c->jpeg_done, s);
+  const size_t o_S = off; off += align256((size_t)nchunks * 8);
+  const size_t o_E0 = off; off += align256((size_t)nchunks * 8);
+  const size_t o_E1 = off; off += align256((size_t)nchunks * 8);
+  const size_t o_cnt = off; off += align256((size_t)nchunks * 16);
+  const size_t o_G = off; off += align256((size_t)nchunks * 4);
+  const size_t o_P = off; off += align256((size_t)nchunks * 12);
+  const size_t o_flag = off; off += align256(4 * (kDeviceRounds + 2));
+  const size_t o_cps = off; off += align256((size_t)nchunks * kCheckpoints * sizeof(Checkpoint));
+  const size_t o_coef = off; off += align256((size_t)B.coef_blocks * 64 * 2);
+  const size_t o_planes = off; off += align256((size_t)B.plane_bytes + 16);
+  hipError_t e = stream_get(c->jpeg_copy);
+  if (e == hipSuccess) e = event_get(c->jpeg_up_done[slot]);
+  if (e == hipSuccess) e = event_get(c->jpeg_ws_free[slot], s);
+  if (e == hipSuccess) e = event_get(c->jpeg_done, s);
   if (e != hipSuccess) return hip_err(c, e, "jpeg decode");
   {
     int rc = jpeg_ensure(c, c->jpeg_ws, off);
@@ -1875,10 +1858,7 @@ int ef_jpeg_ingest(ef_ctx* c, const uint8_t* data, const int64_t* offsets, const
   } call_clock;
 #endif
   (void)hipSetDevice(c->device);
-  if (!c->jpeg_copy) {  // (created here, before any staging thread can use it)
-    const hipError_t e = hipStreamCreateWithFlags(&c->jpeg_copy, hipStreamNonBlocking);
-    if (e != hipSuccess) return hip_err(c, e, "jpeg ingest");
-  }
+  EF_HIP(c, stream_get(c->jpeg_copy), "jpeg ingest");  // (before any staging thread can use it)
   const int64_t row = (int64_t)out_h * out_w;
   // Parts of ~kIngestPart files, each staged (parse, destuff, tables, chunks, file -> image
   // map) into one of the context's two upload slots, the next part on a host thread

@@ -4,7 +4,8 @@
 //     every batched decode runs on untrusted files: each seed file plus deterministic
 //     mutations (bit flips, 0xFF / marker-byte injection, length-field tampering,
 //     truncation, splices), one file per call and all of them in one batch call;
-//   * ef_matches_merge (host form) and ef_keys_decode on random records.
+//   * ef_matches_merge (host form) and ef_keys_decode on random records;
+//   * ef_tm_sums_bits at the int32 limits.
 // A sanitizer report aborts the process (non-zero exit); tests/test_host_sanitizers.py
 // runs it on Pillow-encoded seeds.  usage: host_fuzz <iterations> <seed.jpg>...
 #include <algorithm>
@@ -127,6 +128,8 @@ int main(int argc, char** argv) {
     std::vector<int64_t> idx(b);
     ef_keys_decode(keys.data(), b, (int32_t)(t & 1), best.data(), idx.data());
   }
+  // the integral-image width rule at the int32 limits (H + 1 and W + 1 are formed in int64)
+  if (ef_tm_sums_bits(INT32_MAX, INT32_MAX, 1) != 64 || ef_tm_sums_bits(1, 1, 0) != 32) return 6;
   std::printf("host_fuzz: %d files (%ld parsed, %ld rejected), batch of %zu, 200 merges: clean\n", iters, ok, rejected,
               batch.size());
   return 0;
