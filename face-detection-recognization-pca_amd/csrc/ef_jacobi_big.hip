@@ -424,14 +424,30 @@ __global__ void bj_init_kernel(const double* __restrict__ A, int m, int64_t lda,
   V[e] = i == j ? 1.0 : 0.0;
 }
 
-// descending order (ties -> lower index first); evecs[r][rank] = V[r][i]
-__global__ void jbig_sort_kernel(const double* __restrict__ G, const double* __restrict__ V, int m, int mp,
-                                 double* __restrict__ evals, double* __restrict__ evecs, int64_t ldv) {
+// descending order (ties -> lower index first); evecs[r][rank] = V[r][i] / |V[:][i]|.
+// The column is scaled to unit length on the way out: what the accumulated rotations lose
+// in orthogonality is almost all in the column norms (each rotation's c^2 + s^2 is 1 only to
+// rounding, some thousands of them per column on a graded spectrum), and a norm costs one
+// more read of the column.  256 threads; the sum is taken in a fixed order.
+__global__ __launch_bounds__(256) void jbig_sort_kernel(const double* __restrict__ G, const double* __restrict__ V,
+                                                        int m, int mp, double* __restrict__ evals,
+                                                        double* __restrict__ evecs, int64_t ldv) {
   const int i = blockIdx.x;
   __shared__ int rank_s;
+  __shared__ double red[4];
   const double li = G[(int64_t)i * mp + i];
+  double ss = 0.0;
+  for (int rr = threadIdx.x; rr < m; rr += blockDim.x) {
+    const double v = V[(int64_t)rr * mp + i];
+    ss = fma(v, v, ss);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
   if (threadIdx.x == 0) rank_s = 0;
   __syncthreads();
+  const double n2 = (red[0] + red[1]) + (red[2] + red[3]);
+  const double scale = n2 > 0.0 ? 1.0 / sqrt(n2) : 1.0;
   int cnt = 0;
   for (int j = threadIdx.x; j < m; j += blockDim.x) {
     const double lj = G[(int64_t)j * mp + j];
@@ -441,7 +457,7 @@ __global__ void jbig_sort_kernel(const double* __restrict__ G, const double* __r
   __syncthreads();
   const int rank = rank_s;
   if (threadIdx.x == 0) evals[rank] = li;
-  for (int rr = threadIdx.x; rr < m; rr += blockDim.x) evecs[(int64_t)rr * ldv + rank] = V[(int64_t)rr * mp + i];
+  for (int rr = threadIdx.x; rr < m; rr += blockDim.x) evecs[(int64_t)rr * ldv + rank] = V[(int64_t)rr * mp + i] * scale;
 }
 
 static int padded_order(int m) { return m >= kBlockJacobiMin ? (m + 2 * BJ - 1) / (2 * BJ) * (2 * BJ) : m + (m & 1); }

@@ -297,7 +297,9 @@ __global__ __launch_bounds__(1024) void jacobi_kernel(const double* __restrict__
   if (tid < 2) rcnt[tid] = 0;
   __syncthreads();
   for (; sweep < max_sweeps; ++sweep) {
-    if (tid == 0) *flag = 0;
+    // round 0 counts in rcnt[0]; the previous sweep's final round (mp - 2, even) left its
+    // count there, and with one round per sweep (mp == 2) nothing else ever resets it
+    if (tid == 0) *flag = 0, rcnt[0] = 0;
     __syncthreads();
     for (int r = 0; r < mp - 1; ++r) {
       int* cnt = &rcnt[r & 1];
