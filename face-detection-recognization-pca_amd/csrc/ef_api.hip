@@ -785,6 +785,150 @@ static int recognize_impl(ef_ctx* c, const void* P, int32_t dtype, int64_t b, in
   return r.fetch(c);
 }
 
+// Top-m search of the probes in ctx->q_pad (search_local's contract): keys_dev[b][m] and,
+// when match_dev is non-null, match_dev[b][m].  The split scans of EF_OPT_SEARCH_SPLIT_BF16
+// apply (3, the single-bf16 screen, counts as 1); the prefix scan never does.
+static int search_topk_local(ef_ctx* c, int64_t bpad, int64_t b, int m, int metric, long long* keys_dev,
+                             ef_match* match_dev) {
+  const int cap = (int)c->opt_search_topk_cand;
+  if (cap < m) return set_err(c, EF_E_INVALID, "top-m search: EF_OPT_SEARCH_TOPK_CAND is below m");
+  EF_TRY(ensure(c, c->topk_counters, 4 * sizeof(unsigned long long)));
+  unsigned long long* counters = static_cast<unsigned long long*>(c->topk_counters.p);
+  EF_HIP(c, hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), c->stream), "zero counters");
+  c->topk_probes = b;
+  if (c->n_gallery == 0) {
+    EF_HIP(c, launch_keys_none(c->stream, keys_dev, b * m, match_dev), "keys");
+    return EF_OK;
+  }
+  if (bpad < round_up(b, kSearchProbeTile))
+    return set_err(c, EF_E_INVALID, "top-m search: probe buffer shorter than the batch");
+  const int split = c->opt_search_split_bf16 == 0 ? 0 : c->opt_search_split_bf16 == 2 ? 2 : 1;
+  const std::vector<SearchPiece> pieces = search_pieces(b, c->g_kp);
+  std::vector<SearchPlan> plans;
+  int64_t bpad_max = 0;
+  size_t parts = 0;
+  for (const SearchPiece& p : pieces) {
+    plans.push_back(search_plan(p.bpad, c->n_gallery, c->g_kp, split != 0, 0, m));
+    bpad_max = std::max(bpad_max, p.bpad);
+    parts = std::max(parts, (size_t)plans.back().nchunks * (size_t)p.bpad);
+  }
+  Carve size_ws, cv;
+  carve_search_ws(size_ws, parts, (size_t)bpad_max);
+  carve_topk_ws(size_ws, (size_t)bpad_max, (size_t)cap);
+  EF_TRY(ensure(c, c->search_ws, size_ws.total));
+  cv.base = c->search_ws.p;
+  const SearchWs ws = carve_search_ws(cv, parts, (size_t)bpad_max);
+  const TopkWs tw = carve_topk_ws(cv, (size_t)bpad_max, (size_t)cap);
+  const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? c->gnorm2.p : c->ginv.p);
+  const float* G3 = nullptr;
+  float* Q3 = nullptr;
+  if (split) {
+    if (c->g_kp > 128) {
+      EF_TRY(ensure(c, c->q3, (size_t)bpad_max * c->g_kp * sizeof(float)));
+      Q3 = static_cast<float*>(c->q3.p);
+    }
+    if (!c->g3_valid || c->g3_layout != 1) {  // the split (hi + lo) rows, also under option 3
+      EF_TRY(ensure(c, c->G3, (size_t)c->n_gallery * c->g_kp * sizeof(float)));
+      EF_HIP(c, launch_split_rows(c->stream, static_cast<const float*>(c->G.p), c->n_gallery, c->g_kp, c->G3.p),
+             "split gallery");
+      c->g3_valid = true;
+      c->g3_layout = 1;
+    }
+    G3 = static_cast<const float*>(c->G3.p);
+  }
+  for (size_t i = 0; i < pieces.size(); ++i) {
+    const SearchPiece& p = pieces[i];
+    EF_HIP(c,
+           launch_search_topk(c->stream, c->g_kp, metric, split, m, plans[i],
+                              static_cast<const float*>(c->q_pad.p) + p.off * c->g_kp, Q3, p.bpad, p.b,
+                              static_cast<const float*>(c->G.p), G3, aux, c->n_gallery, c->g_offset, c->gmax2_host,
+                              ws, tw, cap, counters, keys_dev + p.off * m, match_dev ? match_dev + p.off * m : nullptr),
+           "top-m search");
+  }
+  return EF_OK;
+}
+
+// ef_search_topk / ef_search_topk_matches / ef_recognize_topk: X is the probe features, or
+// (pixels) the probe pixels to project first.
+static int topk_impl(ef_ctx* c, const void* X, bool pixels, int32_t dtype, int64_t b, int32_t m, int32_t metric,
+                     int64_t* keys, ef_match* match, float* feats, uint32_t flags, const char* fn) {
+  if (!c) return EF_E_INVALID;
+  const std::string f(fn);
+  if (pixels && c->d == 0) return set_err(c, EF_E_STATE, f + ": no model (call ef_model_set)");
+  if (c->g_k == 0) return set_err(c, EF_E_STATE, f + ": no gallery (call ef_gallery_set)");
+  if (pixels && c->g_k != c->k) return set_err(c, EF_E_INVALID, f + ": gallery k != model k");
+  if (m < 1 || m > 64) return set_err(c, EF_E_INVALID, f + ": m must be 1 .. 64");
+  if (!X || (!keys && !match) || b < 0 || (pixels && dtype != EF_U8 && dtype != EF_F32) ||
+      (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE))
+    return set_err(c, EF_E_INVALID, f + ": bad arguments");
+  if (c->opt_search_topk_cand < m) return set_err(c, EF_E_INVALID, f + ": EF_OPT_SEARCH_TOPK_CAND is below m");
+  if (c->comm && c->comm_size > 1)
+    return set_err(c, EF_E_STATE, f + ": no top-m search over a communicator; search each shard for its records "
+                                      "(ef_search_topk_matches on a context without one) and merge them with "
+                                      "ef_matches_merge_topk");
+  if (b == 0) return EF_OK;
+  (void)hipSetDevice(c->device);
+  const bool dev = flags & EF_MEM_DEVICE;
+  Results r{dev, b, nullptr, nullptr, feats};  // the features' staging; keys and records below
+  int64_t bpad = round_up(b, kSearchProbeTile);
+  if (pixels) {
+    const void* Pd = nullptr;
+    EF_TRY(stage_probes(c, X, dtype, b, flags, &Pd));
+    EF_TRY(r.stage_feats(c));
+    EF_TRY(project_for_search(c, Pd, dtype, b, r.fdev, &bpad));
+  } else {
+    EF_TRY(ensure(c, c->q_pad, (size_t)bpad * c->g_kp * sizeof(float)));
+    const float* qsrc = static_cast<const float*>(X);
+    if (!dev) {
+      EF_TRY(ensure(c, c->p_stage, (size_t)b * c->g_k * sizeof(float)));
+      EF_HIP(c, hipMemcpyAsync(c->p_stage.p, X, (size_t)b * c->g_k * sizeof(float), hipMemcpyHostToDevice, c->stream),
+             "H2D queries");
+      qsrc = static_cast<const float*>(c->p_stage.p);
+    }
+    EF_HIP(c, launch_pad_rows(c->stream, qsrc, b, c->g_k, bpad, static_cast<float*>(c->q_pad.p), c->g_kp),
+           "pad queries");
+  }
+  const size_t nk = (size_t)b * m;
+  EF_TRY(ensure(c, c->keys, nk * (sizeof(long long) + sizeof(ef_match))));
+  long long* kdev = (dev && keys) ? reinterpret_cast<long long*>(keys) : static_cast<long long*>(c->keys.p);
+  ef_match* mdev = !match ? nullptr : dev ? match : reinterpret_cast<ef_match*>(static_cast<long long*>(c->keys.p) + nk);
+  EF_TRY(search_topk_local(c, bpad, b, m, metric, kdev, mdev));
+  if (!dev) {
+    if (keys) EF_HIP(c, hipMemcpyAsync(keys, kdev, nk * sizeof(long long), hipMemcpyDeviceToHost, c->stream), "D2H keys");
+    if (match) EF_HIP(c, hipMemcpyAsync(match, mdev, nk * sizeof(ef_match), hipMemcpyDeviceToHost, c->stream), "D2H matches");
+  }
+  return r.fetch(c);  // the features, then the synchronise of a host call
+}
+
+int ef_search_topk(ef_ctx* c, const float* Q, int64_t b, int32_t m, int32_t metric, int64_t* keys, uint32_t flags) {
+  if (c && !keys) return set_err(c, EF_E_INVALID, "ef_search_topk: bad arguments");
+  return topk_impl(c, Q, false, EF_F32, b, m, metric, keys, nullptr, nullptr, flags, "ef_search_topk");
+}
+
+int ef_search_topk_matches(ef_ctx* c, const float* Q, int64_t b, int32_t m, int32_t metric, ef_match* out,
+                           uint32_t flags) {
+  if (c && !out) return set_err(c, EF_E_INVALID, "ef_search_topk_matches: bad arguments");
+  return topk_impl(c, Q, false, EF_F32, b, m, metric, nullptr, out, nullptr, flags, "ef_search_topk_matches");
+}
+
+int ef_recognize_topk(ef_ctx* c, const void* P, int32_t dtype, int64_t b, int32_t m, int32_t metric, int64_t* keys,
+                      float* feats, uint32_t flags) {
+  if (c && !keys) return set_err(c, EF_E_INVALID, "ef_recognize_topk: bad arguments");
+  return topk_impl(c, P, true, dtype, b, m, metric, keys, nullptr, feats, flags, "ef_recognize_topk");
+}
+
+int ef_search_topk_stats(ef_ctx* c, int64_t out[4]) {
+  if (!c || !out) return EF_E_INVALID;
+  (void)hipSetDevice(c->device);
+  EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  unsigned long long dev[4] = {0, 0, 0, 0};
+  if (c->topk_counters.p)
+    EF_HIP(c, hipMemcpy(dev, c->topk_counters.p, sizeof dev, hipMemcpyDeviceToHost), "D2H top-m counters");
+  out[0] = c->topk_counters.p ? c->topk_probes : 0;
+  for (int i = 1; i < 4; ++i) out[i] = (int64_t)dev[i];
+  return EF_OK;
+}
+
 int ef_search(ef_ctx* c, const float* Q, int64_t b, int32_t metric, int64_t* keys, uint32_t flags) {
   if (c && !keys) return set_err(c, EF_E_INVALID, "ef_search: bad arguments");
   return search_impl(c, Q, b, metric, keys, nullptr, flags, "ef_search");
@@ -853,6 +997,10 @@ int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
       c->prefix_ev_pending = false;  // a new setting starts with a clean guard
       c->prefix_skip_left = 0;
       return EF_OK;
+    case EF_OPT_SEARCH_TOPK_CAND:
+      if (value < 16 || value > 4096) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_TOPK_CAND must be 16 .. 4096");
+      c->opt_search_topk_cand = value;
+      return EF_OK;
     case EF_OPT_HOST_THREADS:
       if (value < 0 || value > 256) return set_err(c, EF_E_INVALID, "EF_OPT_HOST_THREADS must be 0..256");
       g_host_threads.store((int)value, std::memory_order_relaxed);
@@ -876,6 +1024,7 @@ int ef_get_option(const ef_ctx* c, int32_t option, int64_t* value) {
     case EF_OPT_FIT_CHEBYSHEV: *value = c->opt_fit_chebyshev; return EF_OK;
     case EF_OPT_HOST_THREADS: *value = host_threads(); return EF_OK;
     case EF_OPT_SEARCH_PREFIX: *value = c->opt_search_prefix; return EF_OK;
+    case EF_OPT_SEARCH_TOPK_CAND: *value = c->opt_search_topk_cand; return EF_OK;
     default: return EF_E_INVALID;
   }
 }

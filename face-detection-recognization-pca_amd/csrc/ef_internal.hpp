@@ -41,7 +41,7 @@ inline int proj_pad(int kp) { return kp <= 64 ? 64 : (kp + 127) / 128 * 128; }
 constexpr int kSearchProbeTile = 256;   // probes per search workgroup (4 waves x 64)
 constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
-constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe
+constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
 
 // Workspace of one search call (device pointers).
 struct SearchWs {
@@ -53,6 +53,7 @@ struct SearchWs {
   int* cand;            // [bpad][kCandMax] candidate rows
   int* cand_cnt;        // [bpad]
   ef_match* match;      // [b] exact merge records (fp64 winner score), may be null
+  int cand_cap;         // rows kept per slot in cand (kCandMax; the top-m search sets its own), read on a hit
 };
 
 struct SearchPlan {
@@ -182,7 +183,22 @@ struct Carve {
 // braces evaluate left to right, in member order; match stays null)
 inline SearchWs carve_search_ws(Carve& cv, size_t parts, size_t bpad) {
   return SearchWs{cv.take<long long>(parts), cv.take<float>(parts), cv.take<int>(4), cv.take<int>(bpad),
-                  cv.take<float>(bpad), cv.take<int>(bpad * kCandMax), cv.take<int>(bpad), nullptr};
+                  cv.take<float>(bpad), cv.take<int>(bpad * kCandMax), cv.take<int>(bpad), nullptr, kCandMax};
+}
+// Scratch of one top-m search beside its SearchWs (ef_search_topk.hip; device pointers).  The
+// first collect / resolve round runs on the SearchWs queue (amb_count, amb_list, thr,
+// cand_cnt), the second on queue 2; cand replaces the SearchWs's 32-row lists.
+struct TopkWs {
+  int* cand;       // [bpad][cap] candidate rows of either round
+  int* list2;      // [bpad] probes whose first list overflowed
+  float* thr2;     // [bpad] their refined thresholds
+  int* cnt2;       // [bpad] their second candidate counts
+  int* list3;      // [bpad] probes whose second list overflowed too (full fp64 sweep)
+  int* counts;     // [0] probes in queue 2, [1] probes in queue 3
+};
+inline TopkWs carve_topk_ws(Carve& cv, size_t bpad, size_t cap) {
+  return TopkWs{cv.take<int>(bpad * cap), cv.take<int>(bpad), cv.take<float>(bpad), cv.take<int>(bpad),
+                cv.take<int>(bpad), cv.take<int>(4)};
 }
 inline PrefixWs carve_prefix_ws(Carve& cv, size_t bpad, int k1, int kp) {
   return PrefixWs{cv.take<float>(bpad * k1), cv.take<float>(bpad * kp), cv.take<int>(bpad),
@@ -263,6 +279,11 @@ struct ef_ctx {
   ef::DevBuf q3;        // split-bf16 probes [bpad][kp] (wide split-bf16 scans)
   ef::DevBuf keys;      // int64[bpad]
   ef::DevBuf search_ws; // SearchWs carve-out
+  // top-m search (ef_search_topk.hip): candidate rows kept per probe, and the counters of the
+  // most recent top-m search ({-, overflowed, swept, re-scored} on the device; probes here)
+  int64_t opt_search_topk_cand = 1024;
+  ef::DevBuf topk_counters;  // unsigned long long[4]
+  int64_t topk_probes = 0;
   ef::DevBuf p_stage;   // probe pixels staged from host
   ef::DevBuf proj_part; // float[nsplit][bpad][kpw]
   ef::DevBuf feats_dev; // float[b][k] staging for host output
@@ -325,7 +346,8 @@ void timer_commit(ef_ctx* c, TimerEvt* t);
 
 // ---- launchers (defined in the .hip files) -------------------------------------------
 // tile_rows: gallery rows per tile when not the kernel family's own (the prefix scan)
-SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows = 0);
+// min_chunks (the top-m search): at least round_up(min_chunks, 8) gallery chunks
+SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows = 0, int min_chunks = 0);
 int prefix_tile_rows(int k1);  // rows per tile of the prefix scan at prefix length k1
 std::vector<SearchPiece> search_pieces(int64_t b, int kp);
 // G3: split-bf16 copy of G (EF_OPT_SEARCH_SPLIT_BF16) or null for the fp32 kernels; Q3: scratch
@@ -347,6 +369,23 @@ hipError_t launch_split_rows(hipStream_t s, const float* G, int64_t n, int kp, v
 // single-bf16 copy for the bf16 screen (EF_OPT_SEARCH_SPLIT_BF16 = 3), kp % 64 == 0
 hipError_t launch_hi_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);
 hipError_t launch_keys_none(hipStream_t s, long long* keys, int64_t b, ef_match* match);
+// One scan launch of launch_search's kernels for (kp, metric, split): the main pass (per-chunk
+// top-2 records into ws) or the COLLECT pass over ws's queue.  split: 0 the fp32 kernels on G,
+// 1 / 2 the split-bf16 ones on the split copy (kp > 128: q is the split probes too).
+hipError_t launch_search_scan(hipStream_t s, int kp, int metric, bool collect, int split, const SearchPlan& pl,
+                              const float* q, const float* G, const float* aux, int64_t n, int64_t bpad,
+                              const SearchWs& ws);
+// Top-m search of one piece (ef_search_topk.hip): keys[b][m] and, when match is non-null,
+// match[b][m].  split as launch_search_scan; G3 / Q3 as launch_search; cap = rows of tw.cand
+// per probe; counters[1..3] accumulate what ef_search_topk_stats reports.
+hipError_t launch_search_topk(hipStream_t s, int kp, int metric, int split, int m, const SearchPlan& pl,
+                              const float* qpad, float* Q3, int64_t bpad, int64_t b, const float* G, const float* G3,
+                              const float* aux, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
+                              const TopkWs& tw, int cap, unsigned long long* counters, long long* keys,
+                              ef_match* match);
+// keys[b][m] (+ merged[b][m]) <- the top-m merge of parts x b x m records (ef_search_topk.hip)
+hipError_t launch_matches_merge_topk(hipStream_t s, const ef_match* parts, int nparts, int64_t b, int m,
+                                     long long* keys, ef_match* merged);
 // keys[b] (+ merged[b]) <- exact arg-best over parts x b match records (ef_comm.hip)
 hipError_t launch_matches_merge(hipStream_t s, const ef_match* parts, int nparts, int64_t b, long long* keys,
                                 ef_match* merged);

@@ -46,6 +46,9 @@
 // of the rows' first K1 components gives a lower bound of every distance;
 // reduce_prefix_kernel proves the winner from it where it can, and only the unproven probes
 // go through passes 1-3 at full k (launch_search_prefix).
+//
+// Top-m search (ef_search_topk.hip) launches pass 1 and the COLLECT pass of
+// these kernels through launch_search_scan, with its own threshold and resolution kernels.
 #include "ef_search_common.hpp"
 
 #include <cstdlib>
@@ -742,46 +745,12 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ q
   const unsigned row = (unsigned)(kmin & 0xffffffffll);
   const float* q = qpad + p * kpv;
   const double v = score64<KP, METRIC>(q, G + (int64_t)row * kpv, lane, kpv);
-  // rigorous bound on |fp32 score - exact score| (fp32 FMA chain of KP terms,
-  // fp32 ||g||^2 / 1/||g||, final rounding), doubled for the two compared scores
+  // rigorous bound on |fp32 score - exact score|, doubled for the two compared scores
   float qq = 0.f;
   for (int c = lane; c < kpv; c += 64) qq = __builtin_fmaf(q[c], q[c], qq);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) qq += __shfl_xor(qq, off);
-  const float u = 5.9604645e-08f;  // 2^-24
-  const float qn = sqrtf(qq);
-  float delta;
-  if constexpr (S3 == 2) {
-    // single-bf16 chain: |x - bf16(x)| <= 2^-8 |x| for both operands, so each product is
-    // within (2 + 2^-8) 2^-8 |q||g| of the exact one (2.01 2^-8 taken); KP exact products +
-    // the start value summed in fp32 (2u per add allowed), ||g||^2 itself to KP u
-    const float es = 2.01f * 3.90625e-03f;  // 2.01 * 2^-8
-    if constexpr (METRIC == EF_METRIC_L2) {
-      const float gm = sqrtf(gmax2);
-      delta = 2.f * (2.f * es * qn * gm + (kpv + 4) * 2.f * u * 1.01f * (2.02f * qn * gm + gmax2) +
-                     kpv * u * gmax2 + 4.f * u * fabsf(b1)) + 1e-30f;
-    } else {
-      delta = 2.f * ((es + (kpv + 8) * 2.f * u) * 1.01f * qn) + 1e-30f;
-    }
-  } else if constexpr (S3 == 1) {
-    // split-bf16 chain: dropped terms (lo.lo', hi.e', lo.e', e.q) <= 3.02 * 2^-16 |q||g| per
-    // element, 3 KP exact products + the start value summed in fp32 (2u per add allowed, in
-    // case the matrix core's adds do not round to nearest), ||g||^2 itself to KP u
-    const float es = 3.05f * 1.5258789e-05f;  // 3.05 * 2^-16
-    if constexpr (METRIC == EF_METRIC_L2) {
-      const float gm = sqrtf(gmax2);
-      delta = 2.f * (2.f * es * qn * gm + (3 * kpv + 4) * 2.f * u * 1.01f * (2.02f * qn * gm + gmax2) +
-                     kpv * u * gmax2 + 4.f * u * fabsf(b1)) + 1e-30f;
-    } else {
-      delta = 2.f * ((es + (3 * kpv + 8) * 2.f * u) * 1.01f * qn) + 1e-30f;
-    }
-  } else if constexpr (METRIC == EF_METRIC_L2) {
-    const float gm = sqrtf(gmax2);
-    delta = 2.f * ((kpv + 4) * u * 1.01f * (2.f * qn * gm + gmax2) + 4.f * u * fabsf(b1));
-  } else {
-    delta = 2.f * ((kpv + 8) * u * 1.01f * qn) + 1e-30f;
-  }
-  delta *= 2.f;  // safety factor
+  const float delta = scan_delta<METRIC, S3>(kpv, sqrtf(qq), gmax2, b1);  // ef_search_common.hpp
   double qq64 = 0.0;  // tie-tolerance scale of the fp64 resolution (resolve_kernel)
   if (METRIC == EF_METRIC_L2 && ws.match) {
     for (int c = lane; c < kpv; c += 64) qq64 = fma((double)q[c], (double)q[c], qq64);
@@ -1051,7 +1020,7 @@ __global__ __launch_bounds__(256) void max_kernel(const float* __restrict__ x, i
 // ------------------------------------------------------------------------ launchers
 int prefix_tile_rows(int k1) { return k1 <= 32 ? 128 : TG; }
 
-SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows) {
+SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows, int min_chunks) {
   SearchPlan pl;
   const bool wide = kp > 128;
   const bool w3 = wide && s3;  // split-bf16 wide kernel: 256 x 256 tiles, one workgroup per CU
@@ -1073,6 +1042,8 @@ SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows) 
   if (want > tiles) want = tiles;
   if (want < 1) want = 1;
   pl.nchunks = (int)(((want + 7) / 8) * 8);
+  // top-m search: 2 nchunks per-chunk scores bound the m-th best, so at least m chunks
+  if (min_chunks > 0) pl.nchunks = std::max(pl.nchunks, (min_chunks + 7) / 8 * 8);
   pl.tiles_per_chunk = (int)((tiles + pl.nchunks - 1) / pl.nchunks);
   if (pl.tiles_per_chunk < 1) pl.tiles_per_chunk = 1;
   // Wide kernel: the probes stream through LDS with every gallery tile, so an XCD whose
@@ -1098,6 +1069,11 @@ SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows) 
       pl.pblk = pb;
       pl.cblk = (int)(per_xcd / pb);
     }
+  }
+  // a raised chunk count can leave the block deal no bijection: one block per chunk then
+  if (min_chunks > 0 && wide && !block_deal_ok(pl, w3 ? kWide3ProbeTile : kWideProbeTile, bpad)) {
+    pl.pblk = pl.n_ptiles;
+    pl.cblk = 1;
   }
   return pl;
 }
@@ -1199,6 +1175,50 @@ static hipError_t search_t(hipStream_t s, const SearchPlan& pl, const float* qpa
   }
   hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, dim3(256), 0, s, qpad, G, n, g_offset, gmax2, ws, keys, kp);
   return hipGetLastError();
+}
+
+// One scan launch for the top-m search (ef_search_topk.hip): launch_search's kernels, main
+// pass or COLLECT, without its reduce / resolve.
+template <int KP, int M>
+static hipError_t scan_t(hipStream_t s, bool collect, int split, const SearchPlan& pl, const float* q, const float* G,
+                         const float* aux, int64_t n, int64_t bpad, const SearchWs& ws) {
+  const dim3 grid(collect ? (unsigned)pl.c_grid : (unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
+  const int a = collect ? pl.c_chunks : pl.n_ptiles, t = collect ? pl.c_tpc : pl.tiles_per_chunk;
+  if (split && KP == 128 && split != 2) {
+    if (collect)
+      hipLaunchKernelGGL((search16_kernel<M, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+    else
+      hipLaunchKernelGGL((search16_kernel<M, false>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+  } else if (split) {
+    if (collect)
+      hipLaunchKernelGGL((search_kernel<KP, M, true, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+    else
+      hipLaunchKernelGGL((search_kernel<KP, M, false, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+  } else if (collect) {
+    hipLaunchKernelGGL((search_kernel<KP, M, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+  } else {
+    hipLaunchKernelGGL((search_kernel<KP, M, false>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_search_scan(hipStream_t s, int kp, int metric, bool collect, int split, const SearchPlan& pl,
+                              const float* q, const float* G, const float* aux, int64_t n, int64_t bpad,
+                              const SearchWs& ws) {
+  if (kp > 128) return launch_search_wide(s, kp, metric, collect, split == 2 ? 2 : split ? 1 : 0, pl, q, G, aux, n, bpad, ws);
+#define EF_SCAN_CASE(KPV)                                                                              \
+  case KPV:                                                                                            \
+    return metric == EF_METRIC_L2 ? scan_t<KPV, EF_METRIC_L2>(s, collect, split, pl, q, G, aux, n, bpad, ws) \
+                                  : scan_t<KPV, EF_METRIC_COSINE>(s, collect, split, pl, q, G, aux, n, bpad, ws);
+  switch (kp) {
+    EF_SCAN_CASE(16)
+    EF_SCAN_CASE(32)
+    EF_SCAN_CASE(64)
+    EF_SCAN_CASE(128)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef EF_SCAN_CASE
 }
 
 hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl, const float* qpad, float* Q3,

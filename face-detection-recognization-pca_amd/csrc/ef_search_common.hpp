@@ -76,15 +76,15 @@ __device__ __forceinline__ void top2_store_empty(const SearchWs& ws, int64_t chu
   ws.part_b2[chunk_base + slot] = __builtin_inff();
 }
 // COLLECT pass: queue row row_base + row_off for the fp64 resolution of queued probe `slot`
-// when its fp32 score is within the slot's threshold (resolve_kernel re-scans the gallery
-// past kCandMax).  The row comes in two parts so that it is formed only on a hit: passed as
+// when its fp32 score is within the slot's threshold (at most ws.cand_cap rows are kept:
+// kCandMax for the top-1 search, whose resolve_kernel re-scans the gallery past it).  The row comes in two parts so that it is formed only on a hit: passed as
 // one value, the 16 rows of an unrolled block are computed ahead of the compares and cost up
 // to 10 VGPRs (search_kernel<64, .., COLLECT>: 96 -> 106).
 __device__ __forceinline__ void collect_hit(const SearchWs& ws, int64_t slot, float thr, float score, int row_base,
                                             int row_off) {
   if (score <= thr) {
     const int pos = atomicAdd(&ws.cand_cnt[slot], 1);
-    if (pos < kCandMax) ws.cand[slot * kCandMax + pos] = row_base + row_off;
+    if (pos < ws.cand_cap) ws.cand[slot * ws.cand_cap + pos] = row_base + row_off;
   }
 }
 // the slot's COLLECT threshold (main pass, or a slot past the queue: nothing qualifies)
@@ -95,6 +95,48 @@ __device__ __forceinline__ float collect_threshold(const SearchWs& ws, int64_t s
     if (slot < n_amb) thr = ws.thr[slot];
   }
   return thr;
+}
+
+// Rigorous bound on |scan score - exact score| (fp32 FMA chain of kpv terms, fp32 ||g||^2 /
+// 1/||g||, final rounding), doubled for two compared scores and doubled again as a safety
+// factor: delta = 4 e.  S3 is the scan's arithmetic (0 fp32, 1 split bf16, 2 single bf16),
+// qn = fp32 ||q||, b1 the score the bound is taken at.  reduce_kernel queues a probe whose
+// runner-up is within delta of the winner; topk_threshold_kernel widens its cut by it.
+template <int METRIC, int S3>
+__device__ __forceinline__ float scan_delta(int kpv, float qn, float gmax2, float b1) {
+  const float u = 5.9604645e-08f;  // 2^-24
+  float delta;
+  if constexpr (S3 == 2) {
+    // single-bf16 chain: |x - bf16(x)| <= 2^-8 |x| for both operands, so each product is
+    // within (2 + 2^-8) 2^-8 |q||g| of the exact one (2.01 2^-8 taken); KP exact products +
+    // the start value summed in fp32 (2u per add allowed), ||g||^2 itself to KP u
+    const float es = 2.01f * 3.90625e-03f;  // 2.01 * 2^-8
+    if constexpr (METRIC == EF_METRIC_L2) {
+      const float gm = sqrtf(gmax2);
+      delta = 2.f * (2.f * es * qn * gm + (kpv + 4) * 2.f * u * 1.01f * (2.02f * qn * gm + gmax2) +
+                     kpv * u * gmax2 + 4.f * u * fabsf(b1)) + 1e-30f;
+    } else {
+      delta = 2.f * ((es + (kpv + 8) * 2.f * u) * 1.01f * qn) + 1e-30f;
+    }
+  } else if constexpr (S3 == 1) {
+    // split-bf16 chain: dropped terms (lo.lo', hi.e', lo.e', e.q) <= 3.02 * 2^-16 |q||g| per
+    // element, 3 KP exact products + the start value summed in fp32 (2u per add allowed, in
+    // case the matrix core's adds do not round to nearest), ||g||^2 itself to KP u
+    const float es = 3.05f * 1.5258789e-05f;  // 3.05 * 2^-16
+    if constexpr (METRIC == EF_METRIC_L2) {
+      const float gm = sqrtf(gmax2);
+      delta = 2.f * (2.f * es * qn * gm + (3 * kpv + 4) * 2.f * u * 1.01f * (2.02f * qn * gm + gmax2) +
+                     kpv * u * gmax2 + 4.f * u * fabsf(b1)) + 1e-30f;
+    } else {
+      delta = 2.f * ((es + (3 * kpv + 8) * 2.f * u) * 1.01f * qn) + 1e-30f;
+    }
+  } else if constexpr (METRIC == EF_METRIC_L2) {
+    const float gm = sqrtf(gmax2);
+    delta = 2.f * ((kpv + 4) * u * 1.01f * (2.f * qn * gm + gmax2) + 4.f * u * fabsf(b1));
+  } else {
+    delta = 2.f * ((kpv + 8) * u * 1.01f * qn) + 1e-30f;
+  }
+  return delta * 2.f;  // safety factor
 }
 
 // ---- work items -----------------------------------------------------------------------

@@ -5,7 +5,7 @@ Drop-in for the PCA / recognition hot path of saladbkp/face-detection-recognizat
 hand-written gfx950 HIP kernels in ``_lib/libeigenface.so`` (no CPU fallback).
 """
 from ._native import EigenfaceError, NativeLibraryError, LIB_PATH  # noqa: F401
-from .engine import Engine, FitResult, decode_keys, device_count, merge_matches_host  # noqa: F401
+from .engine import Engine, FitResult, decode_keys, device_count, merge_matches_host, merge_topk_host  # noqa: F401
 from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_face_to_eigenspace  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
@@ -15,6 +15,7 @@ from .pca import (  # noqa: F401
     load_gallery_cache,
     manual_pca,
     recognize_face,
+    recognize_face_candidates_with_model,
     recognize_face_dual_model,
     recognize_face_with_model,
     recognize_faces,
@@ -25,7 +26,8 @@ from .pca import (  # noqa: F401
 __all__ = [
     "Engine", "FitResult", "decode_keys", "device_count", "EigenfacePCA", "get_engine",
     "invalidate_uploads", "set_resident_check", "manual_pca", "recognize_face", "recognize_face_with_model", "recognize_faces",
-    "recognize_face_dual_model", "recognize_faces_dual_model", "merge_matches_host", "EigenfaceError",
+    "recognize_face_dual_model", "recognize_faces_dual_model", "merge_matches_host", "merge_topk_host",
+    "recognize_face_candidates_with_model", "EigenfaceError",
     "NativeLibraryError", "LIB_PATH", "save_gallery_cache", "load_gallery_cache", "ManualPCA",
     "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity",
 ]

@@ -35,6 +35,8 @@ EF_OPT_JPEG_PART_FILES = 8
 EF_OPT_FIT_CHEBYSHEV = 9
 EF_OPT_HOST_THREADS = 10
 EF_OPT_SEARCH_PREFIX = 11
+EF_OPT_SEARCH_TOPK_CAND = 12
+EF_TOPK_MAX = 64  # most ranks of a top-m search
 EF_E_NUMERIC = -5
 
 
@@ -115,6 +117,11 @@ _SIGS = {
     "ef_timing_get": ([vp, i32, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
     "ef_timing_reset": ([vp], C.c_int),
     "ef_search_stats": ([vp, C.POINTER(i64)], C.c_int),
+    "ef_search_topk": ([vp, vp, i64, i32, i32, vp, u32], C.c_int),
+    "ef_recognize_topk": ([vp, vp, i32, i64, i32, i32, vp, vp, u32], C.c_int),
+    "ef_search_topk_matches": ([vp, vp, i64, i32, i32, vp, u32], C.c_int),
+    "ef_matches_merge_topk": ([vp, vp, i32, i64, i32, vp, vp, u32], C.c_int),
+    "ef_search_topk_stats": ([vp, C.POINTER(i64)], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -167,6 +167,44 @@ class ShardedGallery:
         b = int(Q.shape[0])
         return self._gather_merge(self._local(Q, metric), b, keys)
 
+    def search_topk_keys(self, Q, m, metric="l2", keys=None):
+        """Global packed keys (b, m) of the m best rows per probe over every shard: each
+        rank's top-m records (Engine.search_topk_matches), one all-gather, and the top-m
+        merge (ef_matches_merge_topk) on the device or, under gloo, on the host.  Equal to a
+        single engine's answer unless more than m rows sit in the best row's tie window."""
+        import torch
+        import torch.distributed as dist
+
+        m = int(m)
+        if self._direct:
+            return self.engine.search_topk_keys(Q, m, metric, keys=keys)
+        if self.engine is None or not self._local_is_engine:
+            raise RuntimeError("search_topk_keys needs the rank's Engine")
+        b = int(Q.shape[0])
+        rec = self.engine.search_topk_matches(Q, m, metric)
+        rec = rec if isinstance(rec, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(rec).view(np.int64).reshape(b, m, 3).copy())
+        if self.world == 1:
+            parts = rec
+        else:
+            parts = torch.empty((self.world, b, m, 3), dtype=torch.int64, device=rec.device)
+            if rec.is_cuda and not _device_collectives(self.group):  # gloo: gather on host
+                chunks = [torch.empty((b, m, 3), dtype=torch.int64) for _ in range(self.world)]
+                dist.all_gather(chunks, rec.cpu(), group=self.group)
+                parts.copy_(torch.stack(chunks))
+            elif rec.is_cuda:  # RCCL over xGMI, stream-ordered on torch's current stream
+                dist.all_gather_into_tensor(parts, rec, group=self.group)
+            else:
+                dist.all_gather(list(parts.unbind(0)), rec, group=self.group)
+        if parts.is_cuda:
+            return self.engine.merge_topk(parts, b, m, keys)
+        from .engine import merge_topk_host
+        out = torch.from_numpy(merge_topk_host(parts.numpy(), b, m))
+        if keys is not None:
+            keys.copy_(out)
+            return keys
+        return out
+
     def _allgather_rows(self, loc, out):
         """out[(world*c), k] <- concat over ranks of loc[c, k] (rank order)."""
         import torch

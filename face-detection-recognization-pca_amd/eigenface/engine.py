@@ -41,7 +41,7 @@ _OPTIONS = {"fit_max_iters": N.EF_OPT_FIT_MAX_ITERS, "fit_fp32_coarse": N.EF_OPT
             "haar_ordered": N.EF_OPT_HAAR_ORDERED, "jpeg_chunk_bits": N.EF_OPT_JPEG_CHUNK_BITS,
             "search_split_bf16": N.EF_OPT_SEARCH_SPLIT_BF16, "jpeg_part_files": N.EF_OPT_JPEG_PART_FILES,
             "fit_chebyshev": N.EF_OPT_FIT_CHEBYSHEV, "host_threads": N.EF_OPT_HOST_THREADS,
-            "search_prefix": N.EF_OPT_SEARCH_PREFIX}
+            "search_prefix": N.EF_OPT_SEARCH_PREFIX, "search_topk_cand": N.EF_OPT_SEARCH_TOPK_CAND}
 
 
 def host_cpu_share():
@@ -235,7 +235,7 @@ class Engine:
         """Context tunable (include/eigenface.h EF_OPT_*): "fit_max_iters",
         "fit_fp32_coarse", "cov_slab_bytes", "tm_int64_sums", "haar_ordered", "jpeg_chunk_bits",
         "search_split_bf16", "jpeg_part_files", "fit_chebyshev", "host_threads" (process-wide),
-        "search_prefix" or the code."""
+        "search_prefix", "search_topk_cand" or the code."""
         self._chk(self._lib.ef_set_option(self._h, _option(option), int(value)))
 
     def get_option(self, option):
@@ -690,6 +690,126 @@ class Engine:
                                                      N.EF_MEM_DEVICE))
         return keys
 
+    # ------------------------------------------------------------- top-m search
+    def _topk_m(self, m):
+        m = int(m)
+        if not 1 <= m <= N.EF_TOPK_MAX:
+            raise ValueError(f"m must be 1 .. {N.EF_TOPK_MAX}, got {m}")
+        return m
+
+    def _topk(self, X, m, metric, out, kind):
+        """The three top-m calls: kind "keys" (ef_search_topk), "matches"
+        (ef_search_topk_matches) or "recognize" (ef_recognize_topk)."""
+        mt = _metric(metric)
+        m = self._topk_m(m)
+        if self.gallery_k is None:
+            raise RuntimeError("no gallery: call set_gallery first")
+        pixels = kind == "recognize"
+        if pixels and self.model_k is None:
+            raise RuntimeError("recognize needs a model and a gallery")
+        if _is_dev(X):
+            import torch
+            if pixels:
+                x, xp, dtype = self._dev_pixels(X)
+            else:
+                x, xp = _dev(X, torch.float32)
+                if x.ndim != 2 or x.shape[1] != self.gallery_k:
+                    raise ValueError(f"Q must be (b, {self.gallery_k}), got {tuple(x.shape)}")
+            b = x.shape[0]
+            shape = (b, m, 3) if kind == "matches" else (b, m)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.int64, device=x.device)
+            self._dev_out(out, shape, torch.int64, "out" if kind == "matches" else "keys")
+            with self._torch_order(x, out):
+                if kind == "keys":
+                    self._chk(self._lib.ef_search_topk(self._h, xp, b, m, mt, out.data_ptr(), N.EF_MEM_DEVICE))
+                elif kind == "matches":
+                    self._chk(self._lib.ef_search_topk_matches(self._h, xp, b, m, mt, out.data_ptr(), N.EF_MEM_DEVICE))
+                else:
+                    self._chk(self._lib.ef_recognize_topk(self._h, xp, dtype, b, m, mt, out.data_ptr(), None,
+                                                          N.EF_MEM_DEVICE))
+            return out
+        if pixels:
+            x = np.asarray(X)
+            dtype = N.EF_U8 if x.dtype == np.uint8 else N.EF_F32
+            x, xp = _host(x, np.uint8 if dtype == N.EF_U8 else np.float32)
+            want = self.model_d
+        else:
+            x, xp = _host(X, np.float32)
+            want = self.gallery_k
+        # the C side reads b * want elements from the host pointer
+        if x.ndim != 2 or x.shape[1] != want:
+            raise ValueError(f"{'P' if pixels else 'Q'} must be (b, {want}), got {x.shape}")
+        b = x.shape[0]
+        res = np.empty((b, m), dtype=N.MATCH_DTYPE if kind == "matches" else np.int64)
+        if kind == "keys":
+            self._chk(self._lib.ef_search_topk(self._h, xp, b, m, mt, res.ctypes.data, 0))
+        elif kind == "matches":
+            self._chk(self._lib.ef_search_topk_matches(self._h, xp, b, m, mt, res.ctypes.data, 0))
+        else:
+            self._chk(self._lib.ef_recognize_topk(self._h, xp, dtype, b, m, mt, res.ctypes.data, None, 0))
+        return res
+
+    def search_topk_keys(self, Q, m, metric="l2", keys=None):
+        """ef_search_topk: packed keys (b, m) int64 of the m best gallery rows per probe, best
+        first (rank 0 is search_keys' key; EF_KEY_NONE past the gallery's rows).  Host arrays
+        in, a host array out; a device tensor in, a device tensor out (stream-ordered)."""
+        return self._topk(Q, m, metric, keys, "keys")
+
+    def search_topk(self, Q, m, metric="l2"):
+        """(idx int64 (b, m), best float32 (b, m)) of the m best rows per probe: L2 -> squared
+        distance, cosine -> similarity; (-1, NaN) past the gallery's rows."""
+        keys = self.search_topk_keys(Q, m, metric)
+        return _decode_topk(keys, metric)
+
+    def recognize_topk_keys(self, P, m, metric="l2", keys=None):
+        """ef_recognize_topk: projection + top-m search, packed keys (b, m)."""
+        return self._topk(P, m, metric, keys, "recognize")
+
+    def recognize_topk(self, P, m, metric="l2"):
+        """Project probes P (uint8 / float32 pixels) and return (idx (b, m), best (b, m))."""
+        return _decode_topk(self.recognize_topk_keys(P, m, metric), metric)
+
+    def search_topk_matches(self, Q, m, metric="l2", out=None):
+        """ef_search_topk_matches: the (fp64 score, scale, key) records of the m best rows per
+        probe: a (b, m) array of N.MATCH_DTYPE on the host, a (b, m, 3) int64 tensor for
+        device input."""
+        return self._topk(Q, m, metric, out, "matches")
+
+    def merge_topk(self, parts, b, m, keys=None):
+        """Device merge (ef_matches_merge_topk, EF_MEM_DEVICE) of gathered top-m records:
+        ``parts`` is an int64 tensor of nparts * b * m records of 3 words (part-major, any
+        shape ending in 3) -> int64 keys (b, m)."""
+        import torch
+        b, m = int(b), self._topk_m(m)
+        if not (isinstance(parts, torch.Tensor) and parts.is_cuda):
+            raise TypeError("parts must be a device tensor (use merge_topk_host for host records)")
+        if parts.dtype != torch.int64 or parts.ndim < 2 or parts.shape[-1] != 3 or not parts.is_contiguous():
+            raise ValueError(f"parts must be a contiguous int64 tensor of records (.., 3), got "
+                             f"{parts.dtype} {tuple(parts.shape)}")
+        nrec = parts.numel() // 3
+        if b < 0 or (b and nrec % (b * m)) or (b == 0 and nrec):
+            raise ValueError(f"parts has {nrec} records, not a multiple of b * m = {b * m}")
+        nparts = nrec // (b * m) if b else 0
+        if keys is None:
+            keys = torch.empty((b, m), dtype=torch.int64, device=parts.device)
+        elif not (keys.dtype == torch.int64 and tuple(keys.shape) == (b, m) and keys.is_contiguous()
+                  and keys.device == parts.device):
+            raise ValueError(f"keys must be a contiguous int64 tensor of shape ({b}, {m}) on {parts.device}")
+        if b:
+            with self._torch_order(parts, keys):
+                self._chk(self._lib.ef_matches_merge_topk(self._h, parts.data_ptr(), nparts, b, m, keys.data_ptr(),
+                                                          None, N.EF_MEM_DEVICE))
+        return keys
+
+    def topk_stats(self):
+        """(probes, probes whose first candidate list overflowed, probes resolved by the full
+        fp64 sweep, candidate rows re-scored in fp64) of the most recent top-m search
+        (ef_search_topk_stats); synchronises the stream."""
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.ef_search_topk_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
     def recognize(self, P, metric="l2", return_features=False):
         """Project probes P (uint8/float32 pixels) and return (idx, best[, feats])."""
         p = np.asarray(P)
@@ -875,6 +995,39 @@ def decode_keys(keys, metric="l2"):
     best = np.empty(b, dtype=np.float32)
     N.lib().ef_keys_decode(k.ctypes.data, b, _metric(metric), best.ctypes.data, idx.ctypes.data)
     return idx, best
+
+
+def _decode_topk(keys, metric):
+    """(idx (b, m), best (b, m)) of top-m keys (device tensor or host array)."""
+    if _is_dev(keys):
+        keys = keys.cpu().numpy()
+    idx, best = decode_keys(np.ascontiguousarray(keys).reshape(-1), metric)
+    return idx.reshape(keys.shape), best.reshape(keys.shape)
+
+
+def merge_topk_host(parts, b, m):
+    """Host merge (ef_matches_merge_topk without a context; no GPU needed) of nparts * b * m
+    top-m records, part-major: an array of N.MATCH_DTYPE (any shape) or its int64 view
+    (.., 3) -> int64 keys (b, m)."""
+    b, m = int(b), int(m)
+    p = np.ascontiguousarray(parts)
+    if p.dtype != np.dtype(N.MATCH_DTYPE):
+        p = np.ascontiguousarray(p, dtype=np.int64)
+        if p.ndim < 2 or p.shape[-1] != 3:
+            raise ValueError(f"parts must be int64 records (.., 3) or MATCH_DTYPE records, got {p.shape}")
+        p = p.reshape(-1, 3).view(N.MATCH_DTYPE)
+    p = p.reshape(-1)
+    if not 1 <= m <= N.EF_TOPK_MAX:
+        raise ValueError(f"m must be 1 .. {N.EF_TOPK_MAX}, got {m}")
+    if b < 0 or (b and p.shape[0] % (b * m)) or (b == 0 and p.shape[0]):
+        raise ValueError(f"{p.shape[0]} records is not a multiple of b * m = {b * m}")
+    nparts = p.shape[0] // (b * m) if b else 0
+    keys = np.empty((b, m), dtype=np.int64)
+    if b:
+        rc = N.lib().ef_matches_merge_topk(None, p.ctypes.data, nparts, b, m, keys.ctypes.data, None, 0)
+        if rc != N.EF_OK:
+            raise N.EigenfaceError(rc, "ef_matches_merge_topk failed")
+    return keys
 
 
 def merge_matches_host(parts, b):

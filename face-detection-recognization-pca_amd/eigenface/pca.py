@@ -155,6 +155,21 @@ class EigenfacePCA:
             idx = np.where(best >= threshold, idx, -1)
         return idx, best
 
+    def recognize_topk(self, P, m, metric="cosine", threshold=None):
+        """Batched ranked recognise: (idx (b, m), score (b, m)), best first (rank 0 is
+        ``recognize``'s answer); slots past the gallery's rows are -1 / NaN.  With
+        ``threshold`` (cosine only) idx is -1 where score < threshold."""
+        eng = get_engine(self.device)
+        self._ensure_model(eng)
+        if self._gallery_token is None:
+            self.set_gallery()
+        elif eng.gallery_owner is not self._gallery_token:  # replaced by someone else: re-upload
+            eng.set_gallery(np.asarray(self._gallery_src, dtype=np.float32), owner=self._gallery_token)
+        idx, best = eng.recognize_topk(P, m, metric)
+        if threshold is not None:
+            idx = np.where(best >= threshold, idx, -1)
+        return idx, best
+
 
 def save_gallery_cache(path, features):
     """Gallery features as a raw float32 ``.npy`` file (SURVEY §5 checkpoint/resume: the 1M
@@ -295,6 +310,23 @@ def recognize_face_with_model(face_features, model_data, threshold=0.7, device=0
                 break
         return pid, name, sim
     return -1, "unknown", sim
+
+
+def recognize_face_candidates_with_model(face_features, model_data, top=5, device=0):
+    """The ranked shortlist behind ``recognize_face_with_model``: ``[(person_id, name,
+    similarity), ...]`` of the ``top`` most similar rows of ``model_data['face_features']``
+    (cosine, best first, no threshold), labelled via ``face_labels`` / ``person_id_map``.
+    Shorter when the gallery has fewer rows."""
+    eng = _gallery_engine(model_data["face_features"], device)
+    idx, best = eng.search_topk(np.asarray(face_features, dtype=np.float32).reshape(1, -1), int(top), "cosine")
+    names = {v: nm for nm, v in reversed(list(model_data["person_id_map"].items()))}  # first name wins
+    out = []
+    for i, sim in zip(idx[0], best[0]):
+        if i < 0:
+            break
+        pid = model_data["face_labels"][int(i)]
+        out.append((pid, names.get(pid, "unknown"), float(sim)))
+    return out
 
 
 def recognize_face(face_vector, model_data, similarity_threshold=0.7, device=0):

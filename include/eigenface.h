@@ -227,6 +227,46 @@ int ef_recognize_matches(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b,
 int ef_matches_merge(ef_ctx* ctx, const ef_match* parts, int32_t nparts, int64_t b, int64_t* keys_out,
                      ef_match* merged_out, uint32_t flags);
 
+/* ------------------------------------------------------ top-m search (ranked list)
+ * The m best gallery rows per probe, 1 <= m <= 64, best first, with the guarantees of
+ * ef_search: fp64-exact order, first-index ties, no score matrix in memory.  Per probe the
+ * result is m slots (keys[b][m], probe-major):
+ *   - rank 0 is exactly what ef_search returns for that probe: the lowest index among the
+ *     rows whose fp64 score is within 1e-12 * (|min| + scale) of the minimum;
+ *   - ranks 1 .. m-1 are the remaining rows in pure (fp64 score, row index) lexicographic
+ *     order; the fp64 score is the one the key is built from, deterministic per (probe, row);
+ *   - rows are distinct, so exact duplicates come out in ascending index;
+ *   - scores are non-decreasing from rank 1 on; rank 0 may exceed rank 1 by at most the
+ *     tie window;
+ *   - when fewer than m rows exist (an empty gallery included) the trailing slots are
+ *     EF_KEY_NONE, as records {+inf, 0, EF_KEY_NONE};
+ *   - a key is pack((float)fp64 score, global row), as for ef_search.
+ * The scan arithmetic follows EF_OPT_SEARCH_SPLIT_BF16 (3, the single-bf16 screen, counts
+ * as 1 here); the prefix scan never engages.  EF_E_INVALID for m outside 1 .. 64 or
+ * EF_OPT_SEARCH_TOPK_CAND below m.  With a communicator of more than one rank attached the
+ * three search calls return EF_E_STATE: search each shard on its own context
+ * (ef_search_topk_matches) and merge the records with ef_matches_merge_topk.  (API v7) */
+int ef_search_topk(ef_ctx* ctx, const float* Q, int64_t b, int32_t m, int32_t metric, int64_t* keys /* [b][m] */,
+                   uint32_t flags);
+int ef_recognize_topk(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, int32_t m, int32_t metric,
+                      int64_t* keys /* [b][m] */, float* feats, uint32_t flags);
+int ef_search_topk_matches(ef_ctx* ctx, const float* Q, int64_t b, int32_t m, int32_t metric,
+                           ef_match* out /* [b][m] */, uint32_t flags);
+/* parts: nparts x b x m records (part-major) -> keys_out[b][m] (and merged_out[b][m],
+ * optional), by the rule above applied to a probe's nparts * m records: rank 0 is the lowest
+ * global index among the records within 1e-12 * (|min| + max scale) of the minimum
+ * (ef_matches_merge's rule), the rest follow in (score, global index) order; EF_KEY_NONE
+ * records are skipped and missing ranks padded.  The result equals the single-engine one
+ * unless more than m rows sit inside the best row's tie window (a shard then reports only m
+ * of them).  Host pointers: computed on the host, ctx may be NULL; EF_MEM_DEVICE: device
+ * pointers, stream-ordered on ctx's stream. */
+int ef_matches_merge_topk(ef_ctx* ctx, const ef_match* parts, int32_t nparts, int64_t b, int32_t m,
+                          int64_t* keys_out, ef_match* merged_out, uint32_t flags);
+/* Counters of the most recent top-m search on this context: {probes, probes whose first
+ * candidate list overflowed EF_OPT_SEARCH_TOPK_CAND, probes resolved by the full fp64 sweep,
+ * candidate rows re-scored in fp64}.  Synchronises the context's stream. */
+int ef_search_topk_stats(ef_ctx* ctx, int64_t out[4]);
+
 /* ------------------------------------------------------------- multi-GPU (RCCL)
  * Row-sharded gallery across the ranks of one job, one process per GPU:
  * rank r sets its shard with ef_gallery_set(..., global_offset = first global row).
@@ -280,6 +320,11 @@ int ef_comm_info(const ef_ctx* ctx, int32_t* nranks, int32_t* rank);
                                       (K1 = 32 at padded k = 128 and >= 65536 rows, else off);
                                       16 / 32 / 64: that K1 at any size (must be < the padded k of
                                       the gallery in place) */
+#define EF_OPT_SEARCH_TOPK_CAND 12 /* top-m search: candidate rows kept per probe for the fp64
+                                      resolution [1024], 16 .. 4096 and at least the m of the call;
+                                      scratch is (padded probes) x this x 4 B.  A probe with more
+                                      rows inside its cut gets a tighter cut and a second round,
+                                      then a full fp64 sweep; results never depend on it */
 int ef_set_option(ef_ctx* ctx, int32_t option, int64_t value);
 int ef_get_option(const ef_ctx* ctx, int32_t option, int64_t* value);
 
