@@ -187,6 +187,7 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
     return set_err(c, EF_E_INVALID, "search: probe buffer shorter than the batch");
   const std::vector<SearchPiece> pieces = search_pieces(b, c->g_kp);
   const int k1 = prefix_k1(c, metric);
+  const bool split1 = c->opt_search_prefix_split != 0;  // the prefix scan's arithmetic
   std::vector<SearchPlan> plans, plans1;  // plans1: the prefix scan's (k1 > 0)
   int64_t bpad_max = 0;
   size_t parts = 0;
@@ -196,7 +197,7 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
     bpad_max = std::max(bpad_max, p.bpad);
     parts = std::max(parts, (size_t)plans.back().nchunks * (size_t)p.bpad);
     if (k1 > 0) {
-      plans1.push_back(search_plan(p.bpad, c->n_gallery, k1, false, prefix_tile_rows(k1)));
+      plans1.push_back(search_plan(p.bpad, c->n_gallery, k1, false, prefix_tile_rows(k1, split1)));
       parts = std::max(parts, (size_t)plans1.back().nchunks * (size_t)p.bpad);
     }
   }
@@ -229,15 +230,16 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
     G3 = static_cast<const float*>(c->G3.p);
   }
   if (k1 > 0) {
-    if (!c->g1_valid || c->g1_k1 != k1) {
+    if (!c->g1_valid || c->g1_k1 != k1 || c->g1_split != split1) {
       EF_TRY(ensure(c, c->G1, (size_t)c->n_gallery * k1 * sizeof(float)));
       EF_TRY(ensure(c, c->gnorm1, (size_t)c->n_gallery * 2 * sizeof(float)));
       EF_HIP(c,
              launch_prefix_gallery(c->stream, static_cast<const float*>(c->G.p), c->n_gallery, c->g_kp, k1,
-                                   static_cast<float*>(c->G1.p), static_cast<float*>(c->gnorm1.p)),
+                                   split1, static_cast<float*>(c->G1.p), static_cast<float*>(c->gnorm1.p)),
              "prefix gallery");
       c->g1_valid = true;
       c->g1_k1 = k1;
+      c->g1_split = split1;
     }
     if (!c->prefix_host.p) EF_HIP(c, pinned_alloc(c->prefix_host, 16), "pinned counters");
     EF_HIP(c, event_get(c->prefix_ev), "event");
@@ -255,7 +257,7 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
       EF_HIP(c,
              launch_search_prefix(c->stream, c->g_kp, k1, plans[i], plans1[i], static_cast<const float*>(c->q_pad.p) + p.off * c->g_kp,
                                   p.bpad, p.b, static_cast<const float*>(c->G.p), aux, static_cast<const float*>(c->G1.p),
-                                  static_cast<const float*>(c->gnorm1.p), c->n_gallery, c->g_offset, c->gmax2_host, ws,
+                                  static_cast<const float*>(c->gnorm1.p), split1, c->n_gallery, c->g_offset, c->gmax2_host, ws,
                                   pw, keys_dev + p.off, c),
              "prefix search");
     }
@@ -997,6 +999,13 @@ int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
       c->prefix_ev_pending = false;  // a new setting starts with a clean guard
       c->prefix_skip_left = 0;
       return EF_OK;
+    case EF_OPT_SEARCH_PREFIX_SPLIT:
+      if (value != 0 && value != 1) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_PREFIX_SPLIT must be 0 or 1");
+      c->opt_search_prefix_split = value;
+      c->g1_valid = false;           // the compact copy is kept in one arithmetic's layout
+      c->prefix_ev_pending = false;  // a new setting starts with a clean guard
+      c->prefix_skip_left = 0;
+      return EF_OK;
     case EF_OPT_SEARCH_TOPK_CAND:
       if (value < 16 || value > 4096) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_TOPK_CAND must be 16 .. 4096");
       c->opt_search_topk_cand = value;
@@ -1025,6 +1034,7 @@ int ef_get_option(const ef_ctx* c, int32_t option, int64_t* value) {
     case EF_OPT_HOST_THREADS: *value = host_threads(); return EF_OK;
     case EF_OPT_SEARCH_PREFIX: *value = c->opt_search_prefix; return EF_OK;
     case EF_OPT_SEARCH_TOPK_CAND: *value = c->opt_search_topk_cand; return EF_OK;
+    case EF_OPT_SEARCH_PREFIX_SPLIT: *value = c->opt_search_prefix_split; return EF_OK;
     default: return EF_E_INVALID;
   }
 }

@@ -259,10 +259,12 @@ struct ef_ctx {
   // prefix scan (EF_OPT_SEARCH_PREFIX): compact copy of the first g1_k1 components of every
   // row with their squared norms, built on the first eligible search like G3
   int64_t opt_search_prefix = 1;
-  ef::DevBuf G1;      // float[n][g1_k1]
-  ef::DevBuf gnorm1;  // float[2][n]: ||g[:K1]||^2, then the aux kernel's unused 1/||.|| output
+  int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32
+  ef::DevBuf G1;      // float[n][g1_k1], or the same bytes as split-bf16 rows (g1_split)
+  ef::DevBuf gnorm1;  // float[2][n]: fp32 ||g[:K1]||^2, then the aux kernel's unused 1/||.|| output
   bool g1_valid = false;
   int g1_k1 = 0;
+  bool g1_split = false;  // what G1 holds; only the copy the chosen arithmetic reads is kept
   ef::DevBuf prefix_ws;  // per-call scratch of the prefix path (ef::PrefixWs carve-out)
   // counters of the last prefix search, copied to pinned host memory behind the search
   // ([0] probes sent to the full-k scan); the next search reads them once prefix_ev has passed
@@ -348,7 +350,8 @@ void timer_commit(ef_ctx* c, TimerEvt* t);
 // tile_rows: gallery rows per tile when not the kernel family's own (the prefix scan)
 // min_chunks (the top-m search): at least round_up(min_chunks, 8) gallery chunks
 SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows = 0, int min_chunks = 0);
-int prefix_tile_rows(int k1);  // rows per tile of the prefix scan at prefix length k1
+// rows per tile of the prefix scan at prefix length k1 (split: the split-bf16 scan)
+int prefix_tile_rows(int k1, bool split);
 std::vector<SearchPiece> search_pieces(int64_t b, int kp);
 // G3: split-bf16 copy of G (EF_OPT_SEARCH_SPLIT_BF16) or null for the fp32 kernels; Q3: scratch
 // [bpad][kp] for the split probes (kp > 128 with G3 only)
@@ -358,13 +361,17 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl
 // Prefix search (EF_OPT_SEARCH_PREFIX; L2, fp32 scan, k1 < kp <= 128): the scan over the
 // compact prefix copy (G1, gnorm1), the proof per probe, and the full-k pipeline of
 // launch_search on the unproven probes.  Same keys / match records as launch_search.
+// split (EF_OPT_SEARCH_PREFIX_SPLIT): G1 holds split-bf16 rows and the scan runs the split
+// chain; pl1 is planned with prefix_tile_rows(k1, split).
 hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan& pl, const SearchPlan& pl1,
                                 const float* qpad, int64_t bpad,
                                 int64_t b, const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
-                                int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
-                                long long* keys, ef_ctx* c);
-// G1[n][k1] <- G[n][kp][:k1], gnorm1[n] = ||G1 row||^2 (gnorm1 holds 2 n floats)
-hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, float* G1, float* gnorm1);
+                                bool split, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
+                                const PrefixWs& pw, long long* keys, ef_ctx* c);
+// G1[n][k1] <- G[n][kp][:k1], gnorm1[n] = ||G1 row||^2 in fp32 (gnorm1 holds 2 n floats);
+// split: G1's rows are then rewritten as split-bf16 rows (launch_split_rows, same bytes)
+hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, bool split, float* G1,
+                                 float* gnorm1);
 hipError_t launch_split_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);
 // single-bf16 copy for the bf16 screen (EF_OPT_SEARCH_SPLIT_BF16 = 3), kp % 64 == 0
 hipError_t launch_hi_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);

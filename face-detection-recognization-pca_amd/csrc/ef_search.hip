@@ -42,8 +42,9 @@
 // records equal the fp32 path's bit for bit whenever both resolve
 // (tests/test_gpu_search_split.py; at the full C3 size, tests/test_gpu_c3_full.py).
 //
-// Prefix scan (EF_OPT_SEARCH_PREFIX; L2, fp32 scan): search_kernel<K1> over a compact copy
-// of the rows' first K1 components gives a lower bound of every distance;
+// Prefix scan (EF_OPT_SEARCH_PREFIX; L2, EF_OPT_SEARCH_SPLIT_BF16 = 0): search_kernel<K1> over
+// a compact copy of the rows' first K1 components, in split-bf16 arithmetic by default
+// (EF_OPT_SEARCH_PREFIX_SPLIT) or in fp32, gives a lower bound of every distance;
 // reduce_prefix_kernel proves the winner from it where it can, and only the unproven probes
 // go through passes 1-3 at full k (launch_search_prefix).
 //
@@ -57,6 +58,9 @@
 namespace ef {
 
 constexpr int TG = 64;  // gallery rows per LDS tile (two 32-row MFMA blocks)
+// rows per tile of the prefix scans at K1 <= 32: fp32, and split bf16 (profiles/r11: 256 rows
+// measured 0.847 ms per C3 step against 0.872 at 128 and 0.909 at 64)
+constexpr int kPrefixTile = 128, kPrefixSplitTile = 256;
 
 // round-to-nearest-even fp32 -> bf16 bits (finite inputs) and back
 __device__ __forceinline__ unsigned bf16_bits(float x) {
@@ -83,6 +87,8 @@ __device__ __forceinline__ void split8(const float* x, bf16x8& hi, bf16x8& lo) {
 // TGT: gallery rows per LDS tile, TGT / 32 independent accumulator chains per wave.  64
 // everywhere but the prefix scan at K1 <= 32, whose tiles hold so few MFMAs that the
 // per-tile costs (barrier, DMA issue and wait, first LDS reads) show; 128 rows halve them.
+// The split-bf16 prefix scan (S3) has a quarter of the fp32 scan's MFMA cycles per tile and
+// takes 256 rows, two groups of four chains (64 KiB of LDS, still two workgroups per CU).
 template <int KP, int METRIC, bool COLLECT, bool S3 = false, bool CNT = false, int TGT = TG>
 __global__ __launch_bounds__(512, 4) void search_kernel(
     const float* __restrict__ qpad, const float* __restrict__ G, const float* __restrict__ aux, int64_t n,
@@ -96,7 +102,9 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   constexpr int PPW = (NI + NW - 1) / NW;                              // pieces per wave
   constexpr int RP = 64 / CPR;                                         // rows per piece
   static_assert((NI % NW == 0 || NI < NW) && RP * CPR == 64 && TG == 64, "tile must be whole 1-KiB pieces");
-  static_assert(TGT == 64 || (TGT == 128 && KP <= 32 && !S3), "128-row tiles: the fp32 scan at KP <= 32");
+  static_assert(TGT == 64 || (KP <= 32 && !COLLECT && TGT == (S3 ? kPrefixSplitTile : kPrefixTile)),
+                "larger tiles: the prefix scans at KP <= 32");
+  constexpr int NBG = 4;  // S3 at TGT > 64: blocks run at once (4 x 16 accumulators fit 128 VGPRs)
   // KP = 128 (the k = 128 headline shape): no swizzle.  LDS piece p (1 KiB + 16 B pad)
   // holds row p of the tile's first 32-row block and row 32 + p of the second, so the
   // lane reading row c32 of either block uses one base (c32 * 1040 B) plus immediate
@@ -336,7 +344,7 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
     int swz = PAD ? 0 : c32 & (SW - 1);  // rows c32 and 32 + c32 share (row & (SW-1)), SW <= 16
     // opaque per tile: stops hipcc hoisting all KH/4 swizzled addresses out of the loop
     if constexpr (!PAD) asm volatile("" : "+v"(swz));
-    if constexpr (TGT != 64) {
+    if constexpr (TGT != 64 && !S3) {
       // NB blocks at once: NB independent accumulator chains sharing the B operand, block
       // bi = rows 32 bi + c32 (the same swizzle: 32 is a multiple of SW)
       const float* arow = tileG + c32 * KP;
@@ -376,6 +384,57 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
       }
 #pragma unroll
       for (int bi = 0; bi < NB; ++bi) consume(acc[bi], tbase + 32 * bi);  // in row order (tie rule)
+      dma_wait_all();
+      __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
+      continue;
+    }
+    if constexpr (TGT != 64 && S3) {
+      // Split-bf16 chains, NBG blocks at once (their accumulators share the probe fragments;
+      // block bi = rows 32 bi + c32, the same swizzle: 32 is a multiple of SW), the tile's
+      // groups of NBG blocks one after the other, in row order
+      const float* arow = tileG + c32 * KP;
+#pragma unroll
+      for (int g0 = 0; g0 < NB; g0 += NBG) {
+        f32x16 acc[NBG];
+#pragma unroll
+        for (int bi = 0; bi < NBG; ++bi) acc[bi] = acc_init(tileA + 32 * (g0 + bi));
+        // fragment i: chunks 2i (hi) and 2i + 1 (lo) of this lane half's k range
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+          const int c0 = h * (CPR / 2) + 2 * i;
+          const int ch = c0 ^ swz, cl = (c0 + 1) ^ swz;
+          bf16x8 ah[NBG], al[NBG];
+#pragma unroll
+          for (int bi = 0; bi < NBG; ++bi) {
+            ah[bi] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + bi) * 32 * KP + ch * 4));
+            al[bi] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + bi) * 32 * KP + cl * 4));
+          }
+#pragma unroll
+          for (int bi = 0; bi < NBG; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[bi], qh[i], acc[bi], 0, 0, 0);
+#pragma unroll
+          for (int bi = 0; bi < NBG; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[bi], ql[i], acc[bi], 0, 0, 0);
+#pragma unroll
+          for (int bi = 0; bi < NBG; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[bi], qh[i], acc[bi], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);  // bound the A prefetch depth
+        }
+#pragma unroll
+        for (int bi = 0; bi < NBG; ++bi) {
+          if constexpr (METRIC != EF_METRIC_L2) {  // cosine: -(q.g) * (1/||g||)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const float4 x = *reinterpret_cast<const float4*>(tileA + 32 * (g0 + bi) + 8 * q + 4 * h);
+              acc[bi][4 * q] *= x.x; acc[bi][4 * q + 1] *= x.y; acc[bi][4 * q + 2] *= x.z; acc[bi][4 * q + 3] *= x.w;
+            }
+          }
+          if (tail) {  // uniform: only the last tile has rows past n
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (tbase + 32 * (g0 + bi) + (r & 3) + 8 * (r >> 2) + 4 * h >= n) acc[bi][r] = INF;
+          }
+        }
+#pragma unroll
+        for (int bi = 0; bi < NBG; ++bi) consume(acc[bi], tbase + 32 * (g0 + bi));  // in row order (tie rule)
+      }
       dma_wait_all();
       __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
       continue;
@@ -839,7 +898,18 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
 // adds 1e-12 (Dw + ||q||^2 + gmax2) on the same side; |r2| <= ||q||^2 + gmax2 + 2 ||q|| gm.
 // A NaN anywhere makes the comparison false.  Unproven probes are appended to `list`
 // (count at ws.amb_count[1]) for the full-k pipeline.
-template <int KP, int K1>
+//
+// S3 = 1 (EF_OPT_SEARCH_PREFIX_SPLIT, the default): the scan ran the split-bf16 chain
+// hi.hi' + hi.lo' + lo.hi' over the split copy of the prefix, started from the same fp32
+// ||g[:K1]||^2.  The argument is unchanged with e1 the split chain's bound at chain length
+// K1: the dropped terms (3.05 2^-16 per element product, summed by Cauchy-Schwarz to
+// 2 ||q|| gm), 3 K1 + 4 fp32 adds at 2u each and the K1 u gmax2 of the fp32 norm
+// (scan_delta<L2, 1>, ef_search_common.hpp, which returns 4 e1); ||q|| and gmax2 of the full
+// rows again bound the prefix's.  delta1 = 2 scan_delta<L2, 1>(K1, ..) = 8 e1, so 7 e1 of
+// slack cover the test's own rounding as above.  The fp32 form keeps delta1 =
+// scan_delta<L2, 0>(K1, ..) = 4 e1, the value it always had.  Nothing else depends on the
+// arithmetic: Dw, q1, tol, the key and the record come from the fp32 rows in fp64.
+template <int KP, int K1, int S3>
 __global__ __launch_bounds__(256) void reduce_prefix_kernel(const float* __restrict__ qpad, int64_t b, int64_t bpad,
                                                             int nchunks, const float* __restrict__ G,
                                                             int64_t g_offset, float gmax2, SearchWs ws,
@@ -885,9 +955,7 @@ __global__ __launch_bounds__(256) void reduce_prefix_kernel(const float* __restr
     qq64 += __shfl_xor(qq64, off);
     q1 += __shfl_xor(q1, off);
   }
-  const float u = 5.9604645e-08f;  // 2^-24
-  const float qn = sqrtf((float)qq64), gm = sqrtf(gmax2);
-  const float delta1 = 2.f * (2.f * ((K1 + 4) * u * 1.01f * (2.f * qn * gm + gmax2) + 4.f * u * fabsf(b1)));
+  const float delta1 = (S3 ? 2.f : 1.f) * scan_delta<EF_METRIC_L2, S3>(K1, sqrtf((float)qq64), gmax2, b1);
   const double scale = qq64 + (double)gmax2;
   const double tol = 1e-12 * (fabs(dw) + scale);
   if (lane == 0) {
@@ -968,8 +1036,9 @@ __global__ void gallery_aux_kernel(const float* __restrict__ G, int64_t n, int k
 }
 
 // Split-bf16 copy of the gallery (S3 search): per 8 fp32 elements, 16 B of hi = bf16(x)
-// then 16 B of lo = bf16(x - hi); same row bytes as the fp32 gallery.
-__global__ void split_rows_kernel(const float* __restrict__ G, int64_t groups, uint4* __restrict__ out) {
+// then 16 B of lo = bf16(x - hi); same row bytes as the fp32 gallery.  out may be G itself
+// (the prefix copy is split in place): a thread reads its 32 B before it writes them.
+__global__ void split_rows_kernel(const float* G, int64_t groups, uint4* out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= groups) return;
   const float4 a = reinterpret_cast<const float4*>(G)[2 * i];
@@ -1018,7 +1087,7 @@ __global__ __launch_bounds__(256) void max_kernel(const float* __restrict__ x, i
 }
 
 // ------------------------------------------------------------------------ launchers
-int prefix_tile_rows(int k1) { return k1 <= 32 ? 128 : TG; }
+int prefix_tile_rows(int k1, bool split) { return k1 <= 32 ? (split ? kPrefixSplitTile : kPrefixTile) : TG; }
 
 SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows, int min_chunks) {
   SearchPlan pl;
@@ -1251,17 +1320,19 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl
 #undef EF_SEARCH_CASE
 }
 
-// Prefix search.  pl1 = search_plan(bpad, n, K1, false, prefix_tile_rows(K1)) plans the
+// Prefix search.  pl1 = search_plan(bpad, n, K1, false, prefix_tile_rows(K1, S3)) plans the
 // prefix scan, pl the second run (the plain plan of KP).
 //   1. Q1 <- the probes' first K1 columns; search_kernel<K1> over (Q1, G1, gnorm1): the
 //      timed main launch, a K1 / KP share of the full scan's MFMAs, in 128-row tiles at
-//      K1 <= 32 (prefix_tile_rows; profiles/r08).
+//      K1 <= 32 (prefix_tile_rows; profiles/r08).  S3 (EF_OPT_SEARCH_PREFIX_SPLIT): G1 holds
+//      split-bf16 rows, the kernel splits Q1 in registers and runs the split chain, 3 bf16
+//      MFMAs of 32 cycles per 16 k against 8 fp32 ones of 64, in 256-row tiles (profiles/r11).
 //   2. reduce_prefix_kernel: proven probes get their key / match record, the others are listed.
 //   3. The listed probes' rows are gathered into qpad2 and go through search_t's sequence
 //      (main scan, reduce, COLLECT, resolve) with the device count in place of b; the grids
 //      are sized for bpad and the work past the count returns at once, so the host never
 //      learns the count.  Their keys / records are scattered back by the list.
-template <int KP, int K1>
+template <int KP, int K1, bool S3>
 static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const SearchPlan& pl1, const float* qpad, int64_t bpad, int64_t b,
                                   const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
                                   int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
@@ -1273,7 +1344,7 @@ static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const Sea
                      reinterpret_cast<const float4*>(qpad), bpad, KP / 4, K1 / 4, reinterpret_cast<float4*>(pw.q1));
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_SEARCH, &tev);
-  hipLaunchKernelGGL((search_kernel<K1, M, false, false, false, (K1 <= 32 ? 128 : TG)>),
+  hipLaunchKernelGGL((search_kernel<K1, M, false, S3, false, (K1 <= 32 ? (S3 ? kPrefixSplitTile : kPrefixTile) : TG)>),
                      dim3((unsigned)(pl1.nchunks * pl1.n_ptiles)), block, 0, s, pw.q1, G1, gnorm1, n, pl1.n_ptiles,
                      pl1.tiles_per_chunk, bpad, ws);
   timer_end(c, &tev);
@@ -1281,7 +1352,7 @@ static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const Sea
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(ws.amb_count, 0, 2 * sizeof(int), s);  // [0] queued for fp64, [1] unproven
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((reduce_prefix_kernel<KP, K1>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl1.nchunks, G, g_offset,
+  hipLaunchKernelGGL((reduce_prefix_kernel<KP, K1, S3 ? 1 : 0>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl1.nchunks, G, g_offset,
                      gmax2, ws, keys, pw.list);
   hipLaunchKernelGGL(prefix_gather_kernel, dim3((unsigned)((bpad * (KP / 4) + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(qpad), pw.list, ws.amb_count + 1, bpad, KP / 4,
@@ -1304,11 +1375,12 @@ static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const Sea
 hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan& pl, const SearchPlan& pl1,
                                 const float* qpad, int64_t bpad,
                                 int64_t b, const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
-                                int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
-                                long long* keys, ef_ctx* c) {
+                                bool split, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
+                                const PrefixWs& pw, long long* keys, ef_ctx* c) {
 #define EF_PREFIX_CASE(KPV, K1V)                                                                                  \
   if (kp == KPV && k1 == K1V)                                                                                     \
-    return search_prefix_t<KPV, K1V>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, n, g_offset, gmax2, ws, pw, keys, c);
+    return split ? search_prefix_t<KPV, K1V, true>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, n, g_offset, gmax2, ws, pw, keys, c) \
+                 : search_prefix_t<KPV, K1V, false>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, n, g_offset, gmax2, ws, pw, keys, c);
   EF_PREFIX_CASE(128, 64)
   EF_PREFIX_CASE(128, 32)
   EF_PREFIX_CASE(128, 16)
@@ -1319,11 +1391,14 @@ hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan&
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, float* G1, float* gnorm1) {
+hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, bool split, float* G1,
+                                 float* gnorm1) {
   hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((n * (k1 / 4) + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(G), n, kp / 4, k1 / 4, reinterpret_cast<float4*>(G1));
   // the norms as gallery_aux_kernel computes gnorm2 (its 1/||g|| output goes to the spare half)
   hipLaunchKernelGGL(gallery_aux_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, G1, n, k1, gnorm1, gnorm1 + n);
+  // the split scan reads (hi, lo) rows: split the copy in place, after its fp32 norms are taken
+  if (split) return launch_split_rows(s, G1, n, k1, G1);
   return hipGetLastError();
 }
 

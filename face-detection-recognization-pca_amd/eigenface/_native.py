@@ -36,6 +36,7 @@ EF_OPT_FIT_CHEBYSHEV = 9
 EF_OPT_HOST_THREADS = 10
 EF_OPT_SEARCH_PREFIX = 11
 EF_OPT_SEARCH_TOPK_CAND = 12
+EF_OPT_SEARCH_PREFIX_SPLIT = 13
 EF_TOPK_MAX = 64  # most ranks of a top-m search
 EF_E_NUMERIC = -5
 

@@ -325,6 +325,12 @@ int ef_comm_info(const ef_ctx* ctx, int32_t* nranks, int32_t* rank);
                                       scratch is (padded probes) x this x 4 B.  A probe with more
                                       rows inside its cut gets a tighter cut and a second round,
                                       then a full fp64 sweep; results never depend on it */
+#define EF_OPT_SEARCH_PREFIX_SPLIT 13 /* arithmetic of the EF_OPT_SEARCH_PREFIX scan.  1 [default]:
+                                      split-bf16 operands on bf16 MFMA (hi.hi' + hi.lo' + lo.hi')
+                                      over a split copy of the prefix, proven with the split
+                                      chain's wider bound; 0: the fp32 scan.  Results are the same;
+                                      the compact copy (n x K1 x 4 B + 8 n B either way) is rebuilt
+                                      on the next search after a change */
 int ef_set_option(ef_ctx* ctx, int32_t option, int64_t value);
 int ef_get_option(const ef_ctx* ctx, int32_t option, int64_t* value);
 
