@@ -205,6 +205,36 @@ inline PrefixWs carve_prefix_ws(Carve& cv, size_t bpad, int k1, int kp) {
                   cv.take<long long>(bpad), cv.take<ef_match>(bpad)};
 }
 
+// ---- model bank (ef_bank.hip) ---------------------------------------------------------
+// One resident (mean, W, gallery) triple.  W is padded to kpw = round_up(kp, 128) columns (the
+// grouped projection works in 128-column tiles), the gallery to kp as ef_gallery_set pads it.
+struct BankSlot {
+  int k = 0, kp = 0, kpw = 0;
+  int64_t n = 0;
+  DevBuf mean;    // float[d]
+  DevBuf W;       // float[d][kpw]
+  DevBuf G;       // float[n][kp]
+  DevBuf gnorm2;  // float[n]
+  DevBuf ginv;    // float[n]
+  DevBuf gmax2;   // float bits, max ||g||^2 (read on the device)
+};
+// The slots, their device tables (rebuilt on the first recognize after a change) and the
+// per-call scratch.  A slot is built completely before it is appended.
+struct Bank {
+  int64_t d = 0;
+  std::vector<BankSlot> slots;
+  int64_t total_k = 0, total_kp = 0, total_kpw = 0, total_rows = 0, total_slices = 0;
+  int kp_max = 0, search_lds = 0;  // widest slot; dynamic LDS bytes of the search launch
+  bool tables_valid = false;
+  DevBuf proj_items;  // BankProjItem[column tiles]
+  DevBuf slot_tab;    // BankSlotDev[slots]
+  DevBuf part;        // float[nsplit][bpad][total_kpw] partial slabs
+  DevBuf q;           // per slot float[bpad][kp], slot m at bpad * sum_{j<m} kp_j
+  DevBuf ws;          // search scratch (per row slice and probe)
+  DevBuf out;         // staging of a host call's results
+  DevBuf p_stage;     // probe pixels staged from host
+};
+
 struct TmState;    // template-localiser state (ef_image.hip)
 struct HaarState;  // Haar cascade state (ef_haar.hip)
 
@@ -289,6 +319,8 @@ struct ef_ctx {
   ef::DevBuf p_stage;   // probe pixels staged from host
   ef::DevBuf proj_part; // float[nsplit][bpad][kpw]
   ef::DevBuf feats_dev; // float[b][k] staging for host output
+
+  ef::Bank bank;  // model bank (ef_bank_*): independent of the model and gallery above
 
   std::vector<ef::DevBuf> fit_pool;  // ef_fit workspaces, reused across calls (ef_trim frees)
 

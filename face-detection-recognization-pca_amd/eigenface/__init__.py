@@ -7,6 +7,7 @@ hand-written gfx950 HIP kernels in ``_lib/libeigenface.so`` (no CPU fallback).
 from ._native import EigenfaceError, NativeLibraryError, LIB_PATH  # noqa: F401
 from .engine import Engine, FitResult, decode_keys, device_count, merge_matches_host, merge_topk_host  # noqa: F401
 from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_face_to_eigenspace  # noqa: F401
+from .bank import ModelBank, best_over_models  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
     get_engine,
@@ -29,5 +30,5 @@ __all__ = [
     "recognize_face_dual_model", "recognize_faces_dual_model", "merge_matches_host", "merge_topk_host",
     "recognize_face_candidates_with_model", "EigenfaceError",
     "NativeLibraryError", "LIB_PATH", "save_gallery_cache", "load_gallery_cache", "ManualPCA",
-    "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity",
+    "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity", "ModelBank", "best_over_models",
 ]

@@ -140,6 +140,8 @@ class Engine:
         # compare their token with these instead of assuming nobody else replaced it.
         self.model_owner = None
         self.gallery_owner = None
+        self.bank_owner = None  # the ModelBank whose slots the bank holds, if one filled it
+        self._bank_k = []
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -818,6 +820,113 @@ class Engine:
         keys = self.recognize_keys(p, metric, feats=feats)
         idx, best = decode_keys(keys, metric)
         return (idx, best, feats) if return_features else (idx, best)
+
+    # ------------------------------------------------------------------ model bank
+    def bank_clear(self):
+        """Drop every slot of the model bank and free its memory (ef_bank_clear)."""
+        self._chk(self._lib.ef_bank_clear(self._h))
+        self._bank_k = []
+        self.bank_owner = None
+
+    def bank_add(self, mean, W, G) -> int:
+        """Append one (mean[d], W[d, k], gallery G[n, k]) triple to the model bank; returns its
+        slot.  NumPy arrays or torch device tensors (all three alike); n may be 0."""
+        if _is_dev(W):
+            import torch
+            m, mp = _dev(mean, torch.float32)
+            w, wp = _dev(W, torch.float32)
+            g, gp = _dev(G, torch.float32)
+            flags = N.EF_MEM_DEVICE
+        else:
+            m, mp = _host(mean, np.float32)
+            w, wp = _host(W, np.float32)
+            g, gp = _host(G, np.float32)
+            flags = 0
+        if w.ndim != 2 or m.ndim != 1 or m.shape[0] != w.shape[0]:
+            raise ValueError("mean must be (d,) and W (d, k)")
+        if g.ndim != 2 or g.shape[1] != w.shape[1]:
+            raise ValueError(f"G must be (n, {w.shape[1]}), got {tuple(g.shape)}")
+        slot = C.c_int32(-1)
+        self._chk(self._lib.ef_bank_add(self._h, mp, wp, int(w.shape[0]), int(w.shape[1]), gp if g.shape[0] else None,
+                                        int(g.shape[0]), flags, C.byref(slot)))
+        self._bank_k = self.bank_slot_widths() + [int(w.shape[1])]
+        self.bank_owner = None
+        return int(slot.value)
+
+    def bank_info(self):
+        """(slots, d, sum of k, sum of gallery rows) of the model bank; zeros when empty."""
+        n, d, tk, tr = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.ef_bank_info(self._h, C.byref(n), C.byref(d), C.byref(tk), C.byref(tr)))
+        return int(n.value), int(d.value), int(tk.value), int(tr.value)
+
+    def bank_recognize_raw(self, P, metric="cosine", matches=False, features=False):
+        """ef_bank_recognize on at most EF_BANK_MAX_PROBES probes: (keys[b, M] int64,
+        records[b, M] or None, best_slot[b] int32, feats[b, sum k] or None) — NumPy for host
+        pixels (N.MATCH_DTYPE records), torch tensors for device pixels ((b, M, 3) int64
+        records; stream-ordered, not synchronised)."""
+        mt = _metric(metric)
+        M, d, tk, _ = self.bank_info()
+        if M == 0:  # the library reports the state error
+            self._chk(self._lib.ef_bank_recognize(self._h, None, N.EF_U8, 0, mt, None, None, None, None, 0))
+        if _is_dev(P):
+            import torch
+            if P.dtype not in (torch.uint8, torch.float32):
+                raise TypeError(f"probe pixels must be uint8 or float32, got {P.dtype}")
+            if P.ndim != 2 or P.shape[1] != d:
+                raise ValueError(f"P must be (b, {d}), got {tuple(P.shape)}")
+            p, pp = _dev(P, P.dtype)
+            b = p.shape[0]
+            keys = torch.empty((b, M), dtype=torch.int64, device=p.device)
+            rec = torch.empty((b, M, 3), dtype=torch.int64, device=p.device) if matches else None
+            best = torch.empty(b, dtype=torch.int32, device=p.device)
+            feats = torch.empty((b, tk), dtype=torch.float32, device=p.device) if features else None
+            with self._torch_order(p, keys, rec, best, feats):
+                self._chk(self._lib.ef_bank_recognize(
+                    self._h, pp, N.EF_U8 if P.dtype == torch.uint8 else N.EF_F32, b, mt, keys.data_ptr(),
+                    rec.data_ptr() if matches else None, best.data_ptr(), feats.data_ptr() if features else None,
+                    N.EF_MEM_DEVICE))
+            return keys, rec, best, feats
+        p = np.asarray(P)
+        dtype = N.EF_U8 if p.dtype == np.uint8 else N.EF_F32
+        p, pp = _host(p, np.uint8 if dtype == N.EF_U8 else np.float32)
+        if p.ndim != 2 or p.shape[1] != d:
+            raise ValueError(f"P must be (b, {d}), got {p.shape}")
+        b = p.shape[0]
+        keys = np.empty((b, M), dtype=np.int64)
+        rec = np.empty((b, M), dtype=N.MATCH_DTYPE) if matches else None
+        best = np.empty(b, dtype=np.int32)
+        feats = np.empty((b, tk), dtype=np.float32) if features else None
+        self._chk(self._lib.ef_bank_recognize(self._h, pp, dtype, b, mt, keys.ctypes.data,
+                                              rec.ctypes.data if matches else None, best.ctypes.data,
+                                              feats.ctypes.data if features else None, 0))
+        return keys, rec, best, feats
+
+    def bank_recognize(self, P, metric="cosine", return_features=False):
+        """Project the probes through every model of the bank and search every gallery:
+        (idx[b, M] int64, score[b, M] float32, best_slot[b] int32[, feats]) as NumPy arrays —
+        idx / score per slot as :meth:`search` gives them (idx -1, score NaN for an empty
+        gallery), best_slot the reference's choice over models (-1: none), feats a list of M
+        (b, k_m) arrays.  Batches over EF_BANK_MAX_PROBES probes run in chunks."""
+        b = int(P.shape[0])
+        chunk = N.EF_BANK_MAX_PROBES
+        parts = [self.bank_recognize_raw(P[o:o + chunk], metric, features=return_features)
+                 for o in range(0, max(b, 1), chunk)]
+        if _is_dev(P):
+            parts = [tuple(None if t is None else t.cpu().numpy() for t in part) for part in parts]
+        keys = np.concatenate([part[0] for part in parts])
+        best = np.concatenate([part[2] for part in parts])
+        idx, score = decode_keys(keys.reshape(-1), metric)
+        out = (idx.reshape(keys.shape), score.reshape(keys.shape), best)
+        if not return_features:
+            return out
+        f = np.concatenate([part[3] for part in parts])
+        ks = self.bank_slot_widths()
+        offs = np.concatenate([[0], np.cumsum(ks)])
+        return out + ([np.ascontiguousarray(f[:, offs[m]:offs[m + 1]]) for m in range(len(ks))],)
+
+    def bank_slot_widths(self):
+        """k of every slot added through this Engine since the last bank_clear."""
+        return list(getattr(self, "_bank_k", []))
 
     # ---------------------------------------------------------------------- images
     PREPROCESS_CHUNK = 65535

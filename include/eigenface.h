@@ -267,6 +267,65 @@ int ef_matches_merge_topk(ef_ctx* ctx, const ef_match* parts, int32_t nparts, in
  * candidate rows re-scored in fp64}.  Synchronises the context's stream. */
 int ef_search_topk_stats(ef_ctx* ctx, int64_t out[4]);
 
+/* ------------------------------------------------------------------ model bank
+ * Added after API v7 without a version bump (purely additive): detect the entry points by
+ * symbol (dlsym / hasattr), not by ef_api_version().
+ *
+ * Replaces the per-model loop of recognize_face_all_models (scan-template-v4.py:289-319),
+ * where every person has a scaler + PCA (folded into mean, W) and a small gallery of their
+ * own.  A bank holds any number of (mean, W, gallery) triples resident together on one
+ * context, beside and independent of the context's single model (ef_model_set) and gallery
+ * (ef_gallery_set).  One ef_bank_recognize call projects a batch of probes through every
+ * model and searches every gallery; the number of kernel launches does not depend on the
+ * number of models.
+ *
+ * ef_bank_add appends a slot (slots are numbered in order of addition, *slot_out optional):
+ *   mean[d], W[d*k] as ef_model_set, G[n*k] as ef_gallery_set (n >= 0; an empty gallery
+ *   answers EF_KEY_NONE), 1 <= k <= 65536, host pointers or device pointers with
+ *   EF_MEM_DEVICE.  The first slot fixes d.  EF_E_INVALID for another d, EF_MODEL_BF16 or a
+ *   slot beyond EF_BANK_MAX_MODELS.  A failed add (EF_E_NOMEM included) leaves the bank as it
+ *   was.  Synchronous on return in both forms.
+ * ef_bank_clear drops every slot and frees the bank's memory (ef_destroy does too).
+ * ef_bank_info: slots, d, sum of k, sum of gallery rows (each output optional; zeros when empty).
+ *
+ * ef_bank_recognize: P[b*d] pixels (EF_U8 or EF_F32), b <= EF_BANK_MAX_PROBES, M = slots:
+ *   keys[b][M]      per (probe, slot) the key ef_search would return for that slot's gallery
+ *                   given that slot's features of the probe (global_offset 0): the fp64 score
+ *                   of every row, the lowest row among those within 1e-12 * (|min| + scale) of
+ *                   the minimum, key = pack((float)score, row); EF_KEY_NONE for an empty slot
+ *   matches[b][M]   optional: the records ef_search_matches would return (scale: L2
+ *                   |q|^2 + the slot's max |g|^2, COSINE 1)
+ *   best_slot[b]    optional: the reference's choice over models on the decoded fp32 scores.
+ *                   COSINE: start from 0.0, slots in order, a slot wins only with a strictly
+ *                   greater similarity (scan-template-v4.py:293-309); L2: the same walk on
+ *                   the negated distance from -inf (the first smallest distance).  -1 when no
+ *                   slot wins; empty slots never win
+ *   feats[b][sum k] optional: slot m's k_m columns start at column sum_{j<m} k_j.  The
+ *                   features are deterministic and within ef_project's error bound, but not
+ *                   bit-identical to ef_project's (another fp32 summation order)
+ * b = 0 is EF_OK; EF_E_STATE for an empty bank or with a communicator of more than one rank
+ * attached.  Host pointers: synchronous.  EF_MEM_DEVICE: every array is a device pointer,
+ * stream-ordered on the ctx's stream, no host synchronisation (the first call after the bank
+ * changed uploads its tables and waits for that once).
+ *
+ * ef_bank_schedule (host only, no ctx, no GPU): the grouped projection's plan for b probes of
+ * d pixels through n_models models of widths k[]: one K-split count for all work items
+ * (*nsplit, 1 .. 64) of *pix_per_split pixels each (a multiple of 32), *n_workgroups =
+ * ceil(b / 128) x (sum of 128-column tiles) x nsplit, and *scratch_bytes of partial slabs
+ * and padded feature blocks.  Each output is optional. */
+#define EF_BANK_MAX_MODELS 4096
+#define EF_BANK_MAX_PROBES 4096 /* per ef_bank_recognize call */
+int ef_bank_clear(ef_ctx* ctx);
+int ef_bank_add(ef_ctx* ctx, const float* mean, const float* W, int64_t d, int32_t k, const float* G, int64_t n,
+                uint32_t flags, int32_t* slot_out);
+int ef_bank_info(const ef_ctx* ctx, int32_t* n_models, int64_t* d, int64_t* total_k, int64_t* total_rows);
+int ef_bank_recognize(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, int32_t metric,
+                      int64_t* keys /* [b][M] */, ef_match* matches /* [b][M], optional */,
+                      int32_t* best_slot /* [b], optional */, float* feats /* [b][sum k], optional */,
+                      uint32_t flags);
+int ef_bank_schedule(int64_t b, int64_t d, const int32_t* k, int32_t n_models, int32_t* nsplit,
+                     int64_t* pix_per_split, int64_t* n_workgroups, int64_t* scratch_bytes);
+
 /* ------------------------------------------------------------- multi-GPU (RCCL)
  * Row-sharded gallery across the ranks of one job, one process per GPU:
  * rank r sets its shard with ef_gallery_set(..., global_offset = first global row).
