@@ -123,7 +123,7 @@ void timer_end(ef_ctx* c, TimerEvt* t) {
   t->kernel = -1;
 }
 
-// The pieces search_local launches for b probes of kp floats: whole 256-probe tiles, at
+// The pieces a search launches for b probes of kp floats: whole 256-probe tiles, at
 // most as many per piece as keep a probe row's byte offset below 2^31 (the kernels' 32-bit
 // offsets).  Piece i covers probes [off, off + b) and is launched with bpad =
 // round_up(b, 256) rows, and its plan is built from that same bpad — never from the
@@ -141,6 +141,27 @@ std::vector<SearchPiece> search_pieces(int64_t b, int kp) {
   return v;
 }
 
+SearchSchedule search_schedule(int64_t b, int64_t n, int kp, int variant, int k1, bool split1, int m, int cap) {
+  SearchSchedule sc;
+  sc.pieces = search_pieces(b, kp);
+  for (const SearchPiece& p : sc.pieces) {
+    sc.plans.push_back(search_plan(p.bpad, n, kp, variant != 0, 0, m));
+    sc.bpad_max = std::max(sc.bpad_max, p.bpad);
+    sc.parts = std::max(sc.parts, (size_t)sc.plans.back().nchunks * (size_t)p.bpad);
+    if (k1 > 0) {
+      sc.plans1.push_back(search_plan(p.bpad, n, k1, false, prefix_tile_rows(k1, split1)));
+      sc.parts = std::max(sc.parts, (size_t)sc.plans1.back().nchunks * (size_t)p.bpad);
+    }
+  }
+  Carve ws, pw;
+  carve_search_ws(ws, sc.parts, (size_t)sc.bpad_max);
+  if (m > 0) carve_topk_ws(ws, (size_t)sc.bpad_max, (size_t)cap);
+  if (k1 > 0) carve_prefix_ws(pw, (size_t)sc.bpad_max, k1, kp);
+  sc.ws_bytes = ws.total;
+  sc.prefix_bytes = pw.total;
+  return sc;
+}
+
 // EF_OPT_SEARCH_PREFIX auto: the prefix length and the smallest gallery it engages for at
 // padded k = 128 (smaller galleries are launch-bound)
 constexpr int kPrefixAutoK1 = 32;
@@ -151,133 +172,131 @@ constexpr int kPrefixGuardSkips = 16;  // searches kept off the prefix scan afte
 // the last prefix search whose counters have arrived (never waited for) sent more than half
 // of its probe tiles to the full-k scan, this search and the next 15 skip the prefix scan —
 // it would cost its own pass on top of most of a full one.  Results do not depend on it.
-static int prefix_k1(ef_ctx* c, int metric) {
-  if (metric != EF_METRIC_L2 || c->opt_search_split_bf16 != 0 || c->g_kp > 128 || c->opt_search_prefix == 0) return 0;
+static int prefix_k1(ef_ctx* c, int metric, int variant) {
+  const int kp = c->gal.kp;
+  GalleryDerived& d = c->der;
+  if (metric != EF_METRIC_L2 || variant != 0 || kp > 128 || c->opt_search_prefix == 0) return 0;
   int k1 = (int)c->opt_search_prefix;
-  if (k1 == 1) k1 = c->g_kp == 128 && c->n_gallery >= kPrefixAutoMinRows ? kPrefixAutoK1 : 0;
-  if (k1 <= 0 || k1 >= c->g_kp) return 0;
-  if (c->prefix_ev_pending) {
+  if (k1 == 1) k1 = kp == 128 && c->gal.n >= kPrefixAutoMinRows ? kPrefixAutoK1 : 0;
+  if (k1 <= 0 || k1 >= kp) return 0;
+  if (d.ev_pending) {
     const hipError_t q = hipEventQuery(c->prefix_ev);
     (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure of a later launch
     if (q == hipSuccess) {
-      c->prefix_ev_pending = false;
+      d.ev_pending = false;
       const int64_t fb_tiles = round_up(*static_cast<const int*>(c->prefix_host.p), kSearchProbeTile) / kSearchProbeTile;
-      if (2 * fb_tiles > c->prefix_ev_tiles) c->prefix_skip_left = kPrefixGuardSkips;
+      if (2 * fb_tiles > d.ev_tiles) d.skip_left = kPrefixGuardSkips;
     }
   }
-  if (c->prefix_skip_left > 0) {
-    --c->prefix_skip_left;
+  if (d.skip_left > 0) {
+    --d.skip_left;
     c->stats_skipped = true;
     return 0;
   }
   return k1;
 }
 
-// Search the probes already in ctx->q_pad (at least round_up(b, 256) rows, kp = ctx->g_kp)
+// The derived copies a search of (variant, k1) reads, built on the first search that needs
+// them and kept until GalleryDerived::reset(): G3 in the variant's layout with the scratch Q3
+// of the probes' copy (wide k), and the prefix copy (G1, gnorm1) in the arithmetic of split1.
+// The only place that builds them and the only one that fills a SplitScan, so no launcher is
+// handed a variant whose copy was not built.
+static int search_copies(ef_ctx* c, int variant, int k1, bool split1, int64_t bpad_max, SplitScan* sp) {
+  const Gallery& g = c->gal;
+  GalleryDerived& d = c->der;
+  const float* G = static_cast<const float*>(g.G.p);
+  *sp = SplitScan{};
+  if (variant) {
+    if (g.kp > 128) {
+      EF_TRY(ensure(c, c->q3, (size_t)bpad_max * g.kp * sizeof(float)));
+      sp->Q3 = static_cast<float*>(c->q3.p);
+    }
+    const int layout = split_layout(variant);
+    if (d.g3_layout != layout) {
+      d.g3_layout = 0;
+      EF_TRY(ensure(c, d.G3, (size_t)g.n * g.kp * sizeof(float)));
+      EF_HIP(c,
+             layout == 3 ? launch_hi_rows(c->stream, G, g.n, g.kp, d.G3.p)
+                         : launch_split_rows(c->stream, G, g.n, g.kp, d.G3.p),
+             "split gallery");
+      d.g3_layout = layout;
+    }
+    sp->variant = variant;
+    sp->G3 = static_cast<const float*>(d.G3.p);
+  }
+  if (k1 > 0 && (d.g1_k1 != k1 || d.g1_split != split1)) {
+    d.g1_k1 = 0;
+    EF_TRY(ensure(c, d.G1, (size_t)g.n * k1 * sizeof(float)));
+    EF_TRY(ensure(c, d.gnorm1, (size_t)g.n * 2 * sizeof(float)));
+    EF_HIP(c,
+           launch_prefix_gallery(c->stream, G, g.n, g.kp, k1, split1, static_cast<float*>(d.G1.p),
+                                 static_cast<float*>(d.gnorm1.p)),
+           "prefix gallery");
+    d.g1_k1 = k1;
+    d.g1_split = split1;
+  }
+  return EF_OK;
+}
+
+// Search the probes already in ctx->q_pad (at least round_up(b, 256) rows, kp = the gallery's)
 // of this rank's gallery: keys_dev[b] and, when match_dev is non-null, the fp64 match
-// records, piece by piece (search_pieces).
-static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long* keys_dev, ef_match* match_dev) {
+// records, piece by piece as search_schedule plans them.
+static int search_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long* keys_dev, ef_match* match_dev) {
+  const Gallery& g = c->gal;
   c->stats_probes = b;
   c->stats_prefix = c->stats_skipped = false;
-  if (c->n_gallery == 0) {
+  if (g.n == 0) {
     EF_HIP(c, launch_keys_none(c->stream, keys_dev, b, match_dev), "keys");
     return EF_OK;
   }
   if (bpad < round_up(b, kSearchProbeTile))
     return set_err(c, EF_E_INVALID, "search: probe buffer shorter than the batch");
-  const std::vector<SearchPiece> pieces = search_pieces(b, c->g_kp);
-  const int k1 = prefix_k1(c, metric);
+  const int variant = split_variant(c->opt_search_split_bf16, g.kp, false);
+  const int k1 = prefix_k1(c, metric, variant);
   const bool split1 = c->opt_search_prefix_split != 0;  // the prefix scan's arithmetic
-  std::vector<SearchPlan> plans, plans1;  // plans1: the prefix scan's (k1 > 0)
-  int64_t bpad_max = 0;
-  size_t parts = 0;
-  for (const SearchPiece& p : pieces) {
-    // a shorter last piece's plan may have more chunks
-    plans.push_back(search_plan(p.bpad, c->n_gallery, c->g_kp, c->opt_search_split_bf16 != 0));
-    bpad_max = std::max(bpad_max, p.bpad);
-    parts = std::max(parts, (size_t)plans.back().nchunks * (size_t)p.bpad);
-    if (k1 > 0) {
-      plans1.push_back(search_plan(p.bpad, c->n_gallery, k1, false, prefix_tile_rows(k1, split1)));
-      parts = std::max(parts, (size_t)plans1.back().nchunks * (size_t)p.bpad);
-    }
-  }
-  // workspace carve-out, sized for the largest piece
-  Carve size_ws, cv;
-  carve_search_ws(size_ws, parts, (size_t)bpad_max);
-  EF_TRY(ensure(c, c->search_ws, size_ws.total));
-  cv.base = c->search_ws.p;
-  SearchWs ws = carve_search_ws(cv, parts, (size_t)bpad_max);
-  const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? c->gnorm2.p : c->ginv.p);
-  const float* G3 = nullptr;
-  float* Q3 = nullptr;
-  if (c->opt_search_split_bf16) {  // split-bf16 scan
-    if (c->g_kp > 128) {
-      EF_TRY(ensure(c, c->q3, (size_t)bpad_max * c->g_kp * sizeof(float)));
-      Q3 = static_cast<float*>(c->q3.p);
-    }
-    // the bf16 screen (3) runs on single-bf16 rows (wide kernels, k > 128); every other split
-    // scan on the split (hi + lo) rows
-    const int layout = c->opt_search_split_bf16 == 3 && c->g_kp > 128 ? 3 : 1;
-    if (!c->g3_valid || c->g3_layout != layout) {
-      EF_TRY(ensure(c, c->G3, (size_t)c->n_gallery * c->g_kp * sizeof(float)));
-      const float* Gp = static_cast<const float*>(c->G.p);
-      EF_HIP(c, layout == 3 ? launch_hi_rows(c->stream, Gp, c->n_gallery, c->g_kp, c->G3.p)
-                            : launch_split_rows(c->stream, Gp, c->n_gallery, c->g_kp, c->G3.p),
-             "split gallery");
-      c->g3_valid = true;
-      c->g3_layout = layout;
-    }
-    G3 = static_cast<const float*>(c->G3.p);
-  }
+  const SearchSchedule sc = search_schedule(b, g.n, g.kp, variant, k1, split1, 0, 0);
+  EF_TRY(ensure(c, c->search_ws, sc.ws_bytes));
+  Carve cv{c->search_ws.p};
+  SearchWs ws = carve_search_ws(cv, sc.parts, (size_t)sc.bpad_max);
+  SplitScan sp;
+  EF_TRY(search_copies(c, variant, k1, split1, sc.bpad_max, &sp));
+  PrefixWs pw{};
   if (k1 > 0) {
-    if (!c->g1_valid || c->g1_k1 != k1 || c->g1_split != split1) {
-      EF_TRY(ensure(c, c->G1, (size_t)c->n_gallery * k1 * sizeof(float)));
-      EF_TRY(ensure(c, c->gnorm1, (size_t)c->n_gallery * 2 * sizeof(float)));
-      EF_HIP(c,
-             launch_prefix_gallery(c->stream, static_cast<const float*>(c->G.p), c->n_gallery, c->g_kp, k1,
-                                   split1, static_cast<float*>(c->G1.p), static_cast<float*>(c->gnorm1.p)),
-             "prefix gallery");
-      c->g1_valid = true;
-      c->g1_k1 = k1;
-      c->g1_split = split1;
-    }
     if (!c->prefix_host.p) EF_HIP(c, pinned_alloc(c->prefix_host, 16), "pinned counters");
     EF_HIP(c, event_get(c->prefix_ev), "event");
-    Carve size_pw, cvp;
-    carve_prefix_ws(size_pw, (size_t)bpad_max, k1, c->g_kp);
-    EF_TRY(ensure(c, c->prefix_ws, size_pw.total));
-    cvp.base = c->prefix_ws.p;
-    const PrefixWs pw = carve_prefix_ws(cvp, (size_t)bpad_max, k1, c->g_kp);
+    EF_TRY(ensure(c, c->prefix_ws, sc.prefix_bytes));
+    Carve cvp{c->prefix_ws.p};
+    pw = carve_prefix_ws(cvp, (size_t)sc.bpad_max, k1, g.kp);
     EF_HIP(c, hipMemsetAsync(ws.amb_count + 2, 0, sizeof(int), c->stream), "zero counters");
-    int64_t tiles = 0;
-    for (size_t i = 0; i < pieces.size(); ++i) {
-      const SearchPiece& p = pieces[i];
-      ws.match = match_dev ? match_dev + p.off : nullptr;
-      tiles += p.bpad / kSearchProbeTile;
+  }
+  const float* G = static_cast<const float*>(g.G.p);
+  const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? g.gnorm2.p : g.ginv.p);
+  int64_t tiles = 0;
+  for (size_t i = 0; i < sc.pieces.size(); ++i) {
+    const SearchPiece& p = sc.pieces[i];
+    const float* q = static_cast<const float*>(c->q_pad.p) + p.off * g.kp;
+    ws.match = match_dev ? match_dev + p.off : nullptr;
+    tiles += p.bpad / kSearchProbeTile;
+    if (k1 > 0)
       EF_HIP(c,
-             launch_search_prefix(c->stream, c->g_kp, k1, plans[i], plans1[i], static_cast<const float*>(c->q_pad.p) + p.off * c->g_kp,
-                                  p.bpad, p.b, static_cast<const float*>(c->G.p), aux, static_cast<const float*>(c->G1.p),
-                                  static_cast<const float*>(c->gnorm1.p), split1, c->n_gallery, c->g_offset, c->gmax2_host, ws,
-                                  pw, keys_dev + p.off, c),
+             launch_search_prefix(c->stream, g.kp, k1, sc.plans[i], sc.plans1[i], q, p.bpad, p.b, G, aux,
+                                  static_cast<const float*>(c->der.G1.p), static_cast<const float*>(c->der.gnorm1.p),
+                                  split1, g.n, c->g_offset, c->gmax2_host, ws, pw, keys_dev + p.off, c),
              "prefix search");
-    }
+    else
+      EF_HIP(c,
+             launch_search(c->stream, g.kp, metric, sp, sc.plans[i], q, p.bpad, p.b, G, aux, g.n, c->g_offset,
+                           c->gmax2_host, ws, keys_dev + p.off, c),
+             "search");
+  }
+  if (k1 > 0) {
     // the counters follow the search to the host; nobody waits for them here
     EF_HIP(c, hipMemcpyAsync(c->prefix_host.p, ws.amb_count + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream),
            "D2H prefix counters");
     EF_HIP(c, hipEventRecord(c->prefix_ev, c->stream), "event record");
-    c->prefix_ev_pending = true;
-    c->prefix_ev_tiles = tiles;
+    c->der.ev_pending = true;
+    c->der.ev_tiles = tiles;
     c->stats_prefix = true;
-    return EF_OK;
-  }
-  for (size_t i = 0; i < pieces.size(); ++i) {
-    const SearchPiece& p = pieces[i];
-    ws.match = match_dev ? match_dev + p.off : nullptr;
-    EF_HIP(c,
-           launch_search(c->stream, c->g_kp, metric, plans[i], static_cast<const float*>(c->q_pad.p) + p.off * c->g_kp,
-                         Q3, p.bpad, p.b, static_cast<const float*>(c->G.p), G3, aux, c->n_gallery, c->g_offset,
-                         c->gmax2_host, ws, keys_dev + p.off, c),
-           "search");
   }
   return EF_OK;
 }
@@ -286,12 +305,12 @@ static int search_local(ef_ctx* c, int64_t bpad, int64_t b, int metric, long lon
 // every rank's match records (ef_comm.hip).  match_dev (optional) receives the records
 // of the (global) winners.
 static int search_qpad(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long* keys_dev, ef_match* match_dev) {
-  if (!c->comm || c->comm_size == 1) return search_local(c, bpad, b, metric, keys_dev, match_dev);
+  if (!c->comm || c->comm_size == 1) return search_run(c, bpad, b, metric, keys_dev, match_dev);
   EF_TRY(ensure(c, c->match_local, (size_t)b * sizeof(ef_match)));
   EF_TRY(ensure(c, c->match_all, (size_t)b * c->comm_size * sizeof(ef_match)));
   ef_match* loc = static_cast<ef_match*>(c->match_local.p);
   ef_match* all = static_cast<ef_match*>(c->match_all.p);
-  EF_TRY(search_local(c, bpad, b, metric, keys_dev, loc));
+  EF_TRY(search_run(c, bpad, b, metric, keys_dev, loc));
   EF_TRY(comm_allgather(c, loc, all, (size_t)b * sizeof(ef_match)));
   EF_HIP(c, launch_matches_merge(c->stream, all, c->comm_size, b, keys_dev, match_dev), "matches merge");
   return EF_OK;
@@ -361,58 +380,62 @@ static int project_for_search(ef_ctx* c, const void* Pd, int dtype, int64_t b, f
   return EF_OK;
 }
 
-static int stage_probes(ef_ctx* c, const void* P, int dtype, int64_t b, uint32_t flags, const void** Pd) {
+int stage_probes(ef_ctx* c, const void* P, int dtype, int64_t b, int64_t d, uint32_t flags, DevBuf& stage,
+                 const void** Pd) {
   if (flags & EF_MEM_DEVICE) {
     *Pd = P;
     return EF_OK;
   }
-  const size_t bytes = (size_t)b * c->d * (dtype == EF_U8 ? 1 : 4);
-  EF_TRY(ensure(c, c->p_stage, bytes));
-  EF_HIP(c, hipMemcpyAsync(c->p_stage.p, P, bytes, hipMemcpyHostToDevice, c->stream), "H2D probes");
-  *Pd = c->p_stage.p;
+  const size_t bytes = (size_t)b * d * (dtype == EF_U8 ? 1 : 4);
+  EF_TRY(ensure(c, stage, bytes));
+  EF_HIP(c, hipMemcpyAsync(stage.p, P, bytes, hipMemcpyHostToDevice, c->stream), "H2D probes");
+  *Pd = stage.p;
   return EF_OK;
 }
 
-// Where one call's keys, match records and features (each optional) are written: the caller's
-// own pointers with EF_MEM_DEVICE, else the context's staging buffers, which fetch() copies
-// to the caller's host pointers before it synchronises.
-struct Results {
-  bool dev;
-  int64_t b;
-  int64_t* keys;  // as the caller gave them
-  ef_match* match;
-  float* feats;
-  long long* kdev = nullptr;  // where the kernels write
-  ef_match* mdev = nullptr;
-  float* fdev = nullptr;
+int Results::stage_feats(ef_ctx* c) {
+  if (!feats) return EF_OK;
+  fdev = feats;
+  if (dev) return EF_OK;
+  EF_TRY(ensure(c, c->feats_dev, (size_t)(b * fk) * sizeof(float)));
+  fdev = static_cast<float*>(c->feats_dev.p);
+  return EF_OK;
+}
 
-  int stage_feats(ef_ctx* c) {  // needs the model's k
-    if (!feats) return EF_OK;
-    fdev = feats;
-    if (dev) return EF_OK;
-    EF_TRY(ensure(c, c->feats_dev, (size_t)b * c->k * sizeof(float)));
-    fdev = static_cast<float*>(c->feats_dev.p);
-    return EF_OK;
+int Results::stage_keys(ef_ctx* c, int64_t bpad) {
+  const size_t kbytes = (size_t)bpad * rec * sizeof(long long);
+  EF_TRY(ensure(c, c->keys, kbytes + (size_t)b * rec * sizeof(ef_match)));
+  kdev = (dev && keys) ? reinterpret_cast<long long*>(keys) : static_cast<long long*>(c->keys.p);
+  if (match) mdev = dev ? match : reinterpret_cast<ef_match*>(static_cast<char*>(c->keys.p) + kbytes);
+  return EF_OK;
+}
+
+int Results::fetch(ef_ctx* c) const {
+  if (dev) return EF_OK;  // stream-ordered; the caller synchronises
+  auto d2h = [&](void* dst, const void* src, size_t bytes) {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  EF_HIP(c, d2h(keys, kdev, (size_t)b * rec * sizeof(long long)), "D2H keys");
+  EF_HIP(c, d2h(match, mdev, (size_t)b * rec * sizeof(ef_match)), "D2H matches");
+  EF_HIP(c, d2h(feats, fdev, (size_t)(b * fk) * sizeof(float)), "D2H features");
+  EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  return EF_OK;
+}
+
+// b probe features Q[b][k of the gallery] (host, or device with dev) into ctx->q_pad, padded
+// to bpad rows of the gallery's kp
+static int stage_queries(ef_ctx* c, const float* Q, int64_t b, bool dev, int64_t bpad) {
+  const Gallery& g = c->gal;
+  EF_TRY(ensure(c, c->q_pad, (size_t)bpad * g.kp * sizeof(float)));
+  if (!dev) {
+    const size_t bytes = (size_t)b * g.k * sizeof(float);
+    EF_TRY(ensure(c, c->p_stage, bytes));
+    EF_HIP(c, hipMemcpyAsync(c->p_stage.p, Q, bytes, hipMemcpyHostToDevice, c->stream), "H2D queries");
+    Q = static_cast<const float*>(c->p_stage.p);
   }
-  // keys are always produced (bpad of them, then the records, in ctx->keys when staged)
-  int stage_keys(ef_ctx* c, int64_t bpad) {
-    EF_TRY(ensure(c, c->keys, (size_t)bpad * sizeof(long long) + (size_t)b * sizeof(ef_match)));
-    kdev = (dev && keys) ? reinterpret_cast<long long*>(keys) : static_cast<long long*>(c->keys.p);
-    if (match) mdev = dev ? match : reinterpret_cast<ef_match*>(static_cast<char*>(c->keys.p) + bpad * sizeof(long long));
-    return EF_OK;
-  }
-  int fetch(ef_ctx* c) const {
-    if (dev) return EF_OK;  // stream-ordered; the caller synchronises
-    auto d2h = [&](void* dst, const void* src, size_t bytes) {
-      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    EF_HIP(c, d2h(keys, kdev, (size_t)b * sizeof(long long)), "D2H keys");
-    EF_HIP(c, d2h(match, mdev, (size_t)b * sizeof(ef_match)), "D2H matches");
-    EF_HIP(c, d2h(feats, fdev, (size_t)b * c->k * sizeof(float)), "D2H features");
-    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
-    return EF_OK;
-  }
-};
+  EF_HIP(c, launch_pad_rows(c->stream, Q, b, g.k, bpad, static_cast<float*>(c->q_pad.p), g.kp), "pad queries");
+  return EF_OK;
+}
 
 namespace {
 class HostPool {
@@ -486,6 +509,66 @@ void host_parallel(int n, const std::function<void(int)>& fn) {
   pool->run(n, fn);
 }
 
+// dst[rows][kp] <- src[rows][k] (host, or device with EF_MEM_DEVICE) on c->stream.  A host
+// source that needs padding is staged unpadded in `staging`: the caller keeps it alive until
+// it has synchronised.  direct: rows that need no padding (k == kp) are copied without the
+// kernel, as the gallery's always were; W always goes through it.
+static int load_padded(ef_ctx* c, const float* src, int64_t rows, int k, int kp, uint32_t flags, bool direct,
+                       DevBuf& dst, DevBuf& staging, const char* what, const char* what_pad) {
+  const bool dev = flags & EF_MEM_DEVICE;
+  const size_t bytes = (size_t)rows * k * sizeof(float);
+  EF_TRY(ensure(c, dst, (size_t)rows * kp * sizeof(float)));
+  if (direct && k == kp) {
+    EF_HIP(c, hipMemcpyAsync(dst.p, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream), what);
+    return EF_OK;
+  }
+  if (!dev) {
+    EF_TRY(ensure(c, staging, bytes));
+    EF_HIP(c, hipMemcpyAsync(staging.p, src, bytes, hipMemcpyHostToDevice, c->stream), what);
+    src = static_cast<const float*>(staging.p);
+  }
+  EF_HIP(c, launch_pad_rows(c->stream, src, rows, k, rows, static_cast<float*>(dst.p), kp), what_pad);
+  return EF_OK;
+}
+
+int weights_load(ef_ctx* c, DevBuf& mean_dst, DevBuf& W_dst, const float* mean, const float* W, int64_t d, int k,
+                 int kpw, uint32_t flags, DevBuf& staging) {
+  EF_TRY(ensure(c, mean_dst, (size_t)d * sizeof(float)));
+  EF_HIP(c,
+         hipMemcpyAsync(mean_dst.p, mean, (size_t)d * sizeof(float),
+                        (flags & EF_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
+         "copy mean");
+  return load_padded(c, W, d, k, kpw, flags, false, W_dst, staging, "copy W", "pad W");
+}
+
+int gallery_load(ef_ctx* c, Gallery& g, const float* G, int64_t n, int k, uint32_t flags, DevBuf& staging,
+                 float* gmax2_host) {
+  const int kp = feature_pad(k);
+  g.n = 0;  // empty until the last step has succeeded
+  if (n > 0) {
+    EF_TRY(ensure(c, g.gnorm2, (size_t)n * sizeof(float)));
+    EF_TRY(ensure(c, g.ginv, (size_t)n * sizeof(float)));
+    EF_TRY(ensure(c, g.gmax2, 16));
+    EF_TRY(load_padded(c, G, n, k, kp, flags, true, g.G, staging, "copy gallery", "pad gallery"));
+    if (gmax2_host && k != kp) {
+      EF_HIP(c, hipStreamSynchronize(c->stream), "pad gallery");
+      release(staging);  // as large as the gallery itself
+    }
+    EF_HIP(c,
+           launch_gallery_aux(c->stream, static_cast<const float*>(g.G.p), n, kp, static_cast<float*>(g.gnorm2.p),
+                              static_cast<float*>(g.ginv.p), static_cast<unsigned*>(g.gmax2.p)),
+           "gallery norms");
+    if (gmax2_host) {
+      EF_HIP(c, hipMemcpyAsync(gmax2_host, g.gmax2.p, sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H gmax2");
+      EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+    }
+  }
+  g.n = n;
+  g.k = k;
+  g.kp = kp;
+  return EF_OK;
+}
+
 hipError_t allow_dynamic_lds(const void* fn, int bytes) {
   static std::mutex mu;
   static std::set<std::pair<const void*, int>> done;  // (kernel, device)
@@ -518,10 +601,11 @@ int ef_search_schedule(int64_t b, int32_t k, int64_t n, int32_t split_bf16, int6
   if (b < 0 || k < 1 || k > 65536 || n < 1 || !n_pieces || max_pieces < 0 || (max_pieces > 0 && !pieces_out))
     return EF_E_INVALID;
   const int kp = feature_pad(k);
-  const std::vector<SearchPiece> pieces = search_pieces(b, kp);
+  const SearchSchedule sc = search_schedule(b, n, kp, split_bf16 != 0, 0, false, 0, 0);  // what search_run launches
+  const std::vector<SearchPiece>& pieces = sc.pieces;
   *n_pieces = (int32_t)pieces.size();
   for (size_t i = 0; i < pieces.size() && (int64_t)i < max_pieces; ++i) {
-    const SearchPlan pl = search_plan(pieces[i].bpad, n, kp, split_bf16 != 0);
+    const SearchPlan& pl = sc.plans[i];
     int64_t* o = pieces_out + 6 * i;
     o[0] = pieces[i].off;
     o[1] = pieces[i].b;
@@ -615,19 +699,9 @@ int ef_model_set(ef_ctx* c, const float* mean, const float* W, int64_t d, int32_
   const bool bf16 = (flags & EF_MODEL_BF16) != 0;
   const int kpw = bf16 ? (kp + 127) / 128 * 128 : proj_pad(kp);  // bf16 kernel: 128-column tiles
   c->d = 0;  // no model until the last step has succeeded (never old dimensions over new buffers)
-  EF_TRY(ensure(c, c->mean, (size_t)d * sizeof(float)));
-  EF_TRY(ensure(c, c->W, (size_t)d * kpw * sizeof(float)));
-  const hipMemcpyKind kind = (flags & EF_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  EF_HIP(c, hipMemcpyAsync(c->mean.p, mean, (size_t)d * sizeof(float), kind, c->stream), "copy mean");
   {
-    const float* wsrc = W;
-    DevBuf tmp;  // freed at the end of this block, after the synchronise (or by a hipFree that waits)
-    if (!(flags & EF_MEM_DEVICE)) {
-      EF_TRY(ensure(c, tmp, (size_t)d * k * sizeof(float)));
-      EF_HIP(c, hipMemcpyAsync(tmp.p, W, (size_t)d * k * sizeof(float), hipMemcpyHostToDevice, c->stream), "copy W");
-      wsrc = static_cast<const float*>(tmp.p);
-    }
-    EF_HIP(c, launch_pad_rows(c->stream, wsrc, d, k, d, static_cast<float*>(c->W.p), kpw), "pad W");
+    DevBuf staging;  // freed at the end of this block, after the synchronise (or by a hipFree that waits)
+    EF_TRY(weights_load(c, c->mean, c->W, mean, W, d, k, kpw, flags, staging));
     EF_HIP(c, hipStreamSynchronize(c->stream), "pad W");
   }
   c->mean_u8_ok = c->w16f_ok = false;
@@ -681,8 +755,8 @@ int ef_project(ef_ctx* c, const void* P, int32_t dtype, int64_t b, float* F, uin
   (void)hipSetDevice(c->device);
   const int64_t bpad = round_up(b, kSearchProbeTile);
   const void* Pd = nullptr;
-  EF_TRY(stage_probes(c, P, dtype, b, flags, &Pd));
-  Results r{(flags & EF_MEM_DEVICE) != 0, b, nullptr, nullptr, F};
+  EF_TRY(stage_probes(c, P, dtype, b, c->d, flags, c->p_stage, &Pd));
+  Results r{(flags & EF_MEM_DEVICE) != 0, b, 1, c->k, nullptr, nullptr, F};
   EF_TRY(r.stage_feats(c));
   EF_TRY(project_dev(c, Pd, dtype, b, bpad, r.fdev, &c->q_pad));
   return r.fetch(c);
@@ -695,228 +769,104 @@ int ef_gallery_set(ef_ctx* c, const float* G, int64_t n, int32_t k, int64_t offs
   const int kp = feature_pad(k);
   if (kp < 0) return set_err(c, EF_E_INVALID, "ef_gallery_set: k > 65536 is not supported");
   (void)hipSetDevice(c->device);
-  c->n_gallery = 0;
-  c->g3_valid = false;
-  c->g1_valid = false;
-  c->prefix_ev_pending = false;  // the guard's history belongs to the gallery it was seen on
-  c->prefix_skip_left = 0;
-  if (n > 0) {
-    EF_TRY(ensure(c, c->G, (size_t)n * kp * sizeof(float)));
-    EF_TRY(ensure(c, c->gnorm2, (size_t)n * sizeof(float)));
-    EF_TRY(ensure(c, c->ginv, (size_t)n * sizeof(float)));
-    EF_TRY(ensure(c, c->gmax2, 16));
-    const hipMemcpyKind kind = (flags & EF_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (k == kp) {
-      EF_HIP(c, hipMemcpyAsync(c->G.p, G, (size_t)n * k * sizeof(float), kind, c->stream), "copy gallery");
-    } else {
-      const float* src = G;
-      DevBuf tmp;  // freed at the end of this block, after the synchronise (or by a hipFree that waits)
-      if (!(flags & EF_MEM_DEVICE)) {
-        EF_TRY(ensure(c, tmp, (size_t)n * k * sizeof(float)));
-        EF_HIP(c, hipMemcpyAsync(tmp.p, G, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice, c->stream),
-               "copy gallery");
-        src = static_cast<const float*>(tmp.p);
-      }
-      EF_HIP(c, launch_pad_rows(c->stream, src, n, k, n, static_cast<float*>(c->G.p), kp), "pad gallery");
-      EF_HIP(c, hipStreamSynchronize(c->stream), "pad gallery");
-    }
-    EF_HIP(c,
-           launch_gallery_aux(c->stream, static_cast<const float*>(c->G.p), n, kp,
-                              static_cast<float*>(c->gnorm2.p), static_cast<float*>(c->ginv.p),
-                              static_cast<unsigned*>(c->gmax2.p)),
-           "gallery norms");
-    EF_HIP(c, hipMemcpyAsync(&c->gmax2_host, c->gmax2.p, sizeof(float), hipMemcpyDeviceToHost, c->stream),
-           "D2H gmax2");
-    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
-  }
-  c->n_gallery = n;
+  c->der.reset();  // the copies and the guard's history belong to the gallery they were made from
+  DevBuf staging;
+  EF_TRY(gallery_load(c, c->gal, G, n, k, flags, staging, &c->gmax2_host));
   c->g_offset = offset;
-  c->g_k = k;
-  c->g_kp = kp;
   return EF_OK;
 }
 
-// ef_search / ef_search_matches: keys (and/or match records) of b probe features.
-static int search_impl(ef_ctx* c, const float* Q, int64_t b, int32_t metric, int64_t* keys, ef_match* match,
-                       uint32_t flags, const char* fn) {
-  if (!c) return EF_E_INVALID;
-  if (c->g_k == 0) return set_err(c, EF_E_STATE, std::string(fn) + ": no gallery (call ef_gallery_set)");
-  if (!Q || (!keys && !match) || b < 0 || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE))
-    return set_err(c, EF_E_INVALID, std::string(fn) + ": bad arguments");
-  if (b == 0) return EF_OK;
-  (void)hipSetDevice(c->device);
-  const bool dev = flags & EF_MEM_DEVICE;
-  const int64_t bpad = round_up(b, kSearchProbeTile);
-  EF_TRY(ensure(c, c->q_pad, (size_t)bpad * c->g_kp * sizeof(float)));
-  const float* qsrc = Q;
-  if (!dev) {
-    EF_TRY(ensure(c, c->p_stage, (size_t)b * c->g_k * sizeof(float)));
-    EF_HIP(c, hipMemcpyAsync(c->p_stage.p, Q, (size_t)b * c->g_k * sizeof(float), hipMemcpyHostToDevice, c->stream),
-           "H2D queries");
-    qsrc = static_cast<const float*>(c->p_stage.p);
-  }
-  EF_HIP(c, launch_pad_rows(c->stream, qsrc, b, c->g_k, bpad, static_cast<float*>(c->q_pad.p), c->g_kp),
-         "pad queries");
-  Results r{dev, b, keys, match, nullptr};
-  EF_TRY(r.stage_keys(c, bpad));
-  EF_TRY(search_qpad(c, bpad, b, metric, r.kdev, r.mdev));
-  return r.fetch(c);
-}
-
-static int recognize_impl(ef_ctx* c, const void* P, int32_t dtype, int64_t b, int32_t metric, int64_t* keys,
-                          ef_match* match, float* feats, uint32_t flags, const char* fn) {
-  if (!c) return EF_E_INVALID;
-  const std::string f(fn);
-  if (c->d == 0) return set_err(c, EF_E_STATE, f + ": no model (call ef_model_set)");
-  if (c->g_k == 0) return set_err(c, EF_E_STATE, f + ": no gallery (call ef_gallery_set)");
-  if (c->g_k != c->k) return set_err(c, EF_E_INVALID, f + ": gallery k != model k");
-  if (!P || (!keys && !match) || b < 0 || (dtype != EF_U8 && dtype != EF_F32) ||
-      (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE))
-    return set_err(c, EF_E_INVALID, f + ": bad arguments");
-  if (b == 0) return EF_OK;
-  (void)hipSetDevice(c->device);
-  const bool dev = flags & EF_MEM_DEVICE;
-  const void* Pd = nullptr;
-  EF_TRY(stage_probes(c, P, dtype, b, flags, &Pd));
-  Results r{dev, b, keys, match, feats};
-  EF_TRY(r.stage_feats(c));
-  int64_t bpad = 0;
-  EF_TRY(project_for_search(c, Pd, dtype, b, r.fdev, &bpad));
-  EF_TRY(r.stage_keys(c, bpad));
-  EF_TRY(search_qpad(c, bpad, b, metric, r.kdev, r.mdev));
-  return r.fetch(c);
-}
-
-// Top-m search of the probes in ctx->q_pad (search_local's contract): keys_dev[b][m] and,
+// Top-m search of the probes in ctx->q_pad (search_run's contract): keys_dev[b][m] and,
 // when match_dev is non-null, match_dev[b][m].  The split scans of EF_OPT_SEARCH_SPLIT_BF16
 // apply (3, the single-bf16 screen, counts as 1); the prefix scan never does.
-static int search_topk_local(ef_ctx* c, int64_t bpad, int64_t b, int m, int metric, long long* keys_dev,
-                             ef_match* match_dev) {
+static int search_topk_run(ef_ctx* c, int64_t bpad, int64_t b, int m, int metric, long long* keys_dev,
+                           ef_match* match_dev) {
+  const Gallery& g = c->gal;
   const int cap = (int)c->opt_search_topk_cand;
   if (cap < m) return set_err(c, EF_E_INVALID, "top-m search: EF_OPT_SEARCH_TOPK_CAND is below m");
   EF_TRY(ensure(c, c->topk_counters, 4 * sizeof(unsigned long long)));
   unsigned long long* counters = static_cast<unsigned long long*>(c->topk_counters.p);
   EF_HIP(c, hipMemsetAsync(counters, 0, 4 * sizeof(unsigned long long), c->stream), "zero counters");
   c->topk_probes = b;
-  if (c->n_gallery == 0) {
+  if (g.n == 0) {
     EF_HIP(c, launch_keys_none(c->stream, keys_dev, b * m, match_dev), "keys");
     return EF_OK;
   }
   if (bpad < round_up(b, kSearchProbeTile))
     return set_err(c, EF_E_INVALID, "top-m search: probe buffer shorter than the batch");
-  const int split = c->opt_search_split_bf16 == 0 ? 0 : c->opt_search_split_bf16 == 2 ? 2 : 1;
-  const std::vector<SearchPiece> pieces = search_pieces(b, c->g_kp);
-  std::vector<SearchPlan> plans;
-  int64_t bpad_max = 0;
-  size_t parts = 0;
-  for (const SearchPiece& p : pieces) {
-    plans.push_back(search_plan(p.bpad, c->n_gallery, c->g_kp, split != 0, 0, m));
-    bpad_max = std::max(bpad_max, p.bpad);
-    parts = std::max(parts, (size_t)plans.back().nchunks * (size_t)p.bpad);
-  }
-  Carve size_ws, cv;
-  carve_search_ws(size_ws, parts, (size_t)bpad_max);
-  carve_topk_ws(size_ws, (size_t)bpad_max, (size_t)cap);
-  EF_TRY(ensure(c, c->search_ws, size_ws.total));
-  cv.base = c->search_ws.p;
-  const SearchWs ws = carve_search_ws(cv, parts, (size_t)bpad_max);
-  const TopkWs tw = carve_topk_ws(cv, (size_t)bpad_max, (size_t)cap);
-  const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? c->gnorm2.p : c->ginv.p);
-  const float* G3 = nullptr;
-  float* Q3 = nullptr;
-  if (split) {
-    if (c->g_kp > 128) {
-      EF_TRY(ensure(c, c->q3, (size_t)bpad_max * c->g_kp * sizeof(float)));
-      Q3 = static_cast<float*>(c->q3.p);
-    }
-    if (!c->g3_valid || c->g3_layout != 1) {  // the split (hi + lo) rows, also under option 3
-      EF_TRY(ensure(c, c->G3, (size_t)c->n_gallery * c->g_kp * sizeof(float)));
-      EF_HIP(c, launch_split_rows(c->stream, static_cast<const float*>(c->G.p), c->n_gallery, c->g_kp, c->G3.p),
-             "split gallery");
-      c->g3_valid = true;
-      c->g3_layout = 1;
-    }
-    G3 = static_cast<const float*>(c->G3.p);
-  }
-  for (size_t i = 0; i < pieces.size(); ++i) {
-    const SearchPiece& p = pieces[i];
+  const int variant = split_variant(c->opt_search_split_bf16, g.kp, true);
+  const SearchSchedule sc = search_schedule(b, g.n, g.kp, variant, 0, false, m, cap);
+  EF_TRY(ensure(c, c->search_ws, sc.ws_bytes));
+  Carve cv{c->search_ws.p};
+  const SearchWs ws = carve_search_ws(cv, sc.parts, (size_t)sc.bpad_max);
+  const TopkWs tw = carve_topk_ws(cv, (size_t)sc.bpad_max, (size_t)cap);
+  SplitScan sp;
+  EF_TRY(search_copies(c, variant, 0, false, sc.bpad_max, &sp));
+  const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? g.gnorm2.p : g.ginv.p);
+  for (size_t i = 0; i < sc.pieces.size(); ++i) {
+    const SearchPiece& p = sc.pieces[i];
     EF_HIP(c,
-           launch_search_topk(c->stream, c->g_kp, metric, split, m, plans[i],
-                              static_cast<const float*>(c->q_pad.p) + p.off * c->g_kp, Q3, p.bpad, p.b,
-                              static_cast<const float*>(c->G.p), G3, aux, c->n_gallery, c->g_offset, c->gmax2_host,
-                              ws, tw, cap, counters, keys_dev + p.off * m, match_dev ? match_dev + p.off * m : nullptr),
+           launch_search_topk(c->stream, g.kp, metric, sp, m, sc.plans[i],
+                              static_cast<const float*>(c->q_pad.p) + p.off * g.kp, p.bpad, p.b,
+                              static_cast<const float*>(g.G.p), aux, g.n, c->g_offset, c->gmax2_host, ws, tw, cap,
+                              counters, keys_dev + p.off * m, match_dev ? match_dev + p.off * m : nullptr),
            "top-m search");
   }
   return EF_OK;
 }
 
-// ef_search_topk / ef_search_topk_matches / ef_recognize_topk: X is the probe features, or
-// (pixels) the probe pixels to project first.
-static int topk_impl(ef_ctx* c, const void* X, bool pixels, int32_t dtype, int64_t b, int32_t m, int32_t metric,
-                     int64_t* keys, ef_match* match, float* feats, uint32_t flags, const char* fn) {
+// Every search entry point: keys and / or match records (and, pixels, the features) of b
+// probes.  X is the probe features, or (pixels) the probe pixels to project first; m = 0 is the
+// top-1 search (one key per probe, across the communicator when one is attached), m >= 1 the
+// top-m search.
+static int query_impl(ef_ctx* c, const void* X, bool pixels, int32_t dtype, int64_t b, int32_t m, bool topm,
+                      int32_t metric, int64_t* keys, ef_match* match, float* feats, uint32_t flags, const char* fn) {
   if (!c) return EF_E_INVALID;
   const std::string f(fn);
   if (pixels && c->d == 0) return set_err(c, EF_E_STATE, f + ": no model (call ef_model_set)");
-  if (c->g_k == 0) return set_err(c, EF_E_STATE, f + ": no gallery (call ef_gallery_set)");
-  if (pixels && c->g_k != c->k) return set_err(c, EF_E_INVALID, f + ": gallery k != model k");
-  if (m < 1 || m > 64) return set_err(c, EF_E_INVALID, f + ": m must be 1 .. 64");
+  if (c->gal.k == 0) return set_err(c, EF_E_STATE, f + ": no gallery (call ef_gallery_set)");
+  if (pixels && c->gal.k != c->k) return set_err(c, EF_E_INVALID, f + ": gallery k != model k");
+  if (topm && (m < 1 || m > 64)) return set_err(c, EF_E_INVALID, f + ": m must be 1 .. 64");
   if (!X || (!keys && !match) || b < 0 || (pixels && dtype != EF_U8 && dtype != EF_F32) ||
       (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE))
     return set_err(c, EF_E_INVALID, f + ": bad arguments");
-  if (c->opt_search_topk_cand < m) return set_err(c, EF_E_INVALID, f + ": EF_OPT_SEARCH_TOPK_CAND is below m");
-  if (c->comm && c->comm_size > 1)
+  if (topm && c->opt_search_topk_cand < m) return set_err(c, EF_E_INVALID, f + ": EF_OPT_SEARCH_TOPK_CAND is below m");
+  if (topm && c->comm && c->comm_size > 1)
     return set_err(c, EF_E_STATE, f + ": no top-m search over a communicator; search each shard for its records "
                                       "(ef_search_topk_matches on a context without one) and merge them with "
                                       "ef_matches_merge_topk");
   if (b == 0) return EF_OK;
   (void)hipSetDevice(c->device);
-  const bool dev = flags & EF_MEM_DEVICE;
-  Results r{dev, b, nullptr, nullptr, feats};  // the features' staging; keys and records below
+  Results r{(flags & EF_MEM_DEVICE) != 0, b, topm ? m : 1, c->k, keys, match, feats};
   int64_t bpad = round_up(b, kSearchProbeTile);
   if (pixels) {
     const void* Pd = nullptr;
-    EF_TRY(stage_probes(c, X, dtype, b, flags, &Pd));
+    EF_TRY(stage_probes(c, X, dtype, b, c->d, flags, c->p_stage, &Pd));
     EF_TRY(r.stage_feats(c));
     EF_TRY(project_for_search(c, Pd, dtype, b, r.fdev, &bpad));
   } else {
-    EF_TRY(ensure(c, c->q_pad, (size_t)bpad * c->g_kp * sizeof(float)));
-    const float* qsrc = static_cast<const float*>(X);
-    if (!dev) {
-      EF_TRY(ensure(c, c->p_stage, (size_t)b * c->g_k * sizeof(float)));
-      EF_HIP(c, hipMemcpyAsync(c->p_stage.p, X, (size_t)b * c->g_k * sizeof(float), hipMemcpyHostToDevice, c->stream),
-             "H2D queries");
-      qsrc = static_cast<const float*>(c->p_stage.p);
-    }
-    EF_HIP(c, launch_pad_rows(c->stream, qsrc, b, c->g_k, bpad, static_cast<float*>(c->q_pad.p), c->g_kp),
-           "pad queries");
+    EF_TRY(stage_queries(c, static_cast<const float*>(X), b, r.dev, bpad));
   }
-  const size_t nk = (size_t)b * m;
-  EF_TRY(ensure(c, c->keys, nk * (sizeof(long long) + sizeof(ef_match))));
-  long long* kdev = (dev && keys) ? reinterpret_cast<long long*>(keys) : static_cast<long long*>(c->keys.p);
-  ef_match* mdev = !match ? nullptr : dev ? match : reinterpret_cast<ef_match*>(static_cast<long long*>(c->keys.p) + nk);
-  EF_TRY(search_topk_local(c, bpad, b, m, metric, kdev, mdev));
-  if (!dev) {
-    if (keys) EF_HIP(c, hipMemcpyAsync(keys, kdev, nk * sizeof(long long), hipMemcpyDeviceToHost, c->stream), "D2H keys");
-    if (match) EF_HIP(c, hipMemcpyAsync(match, mdev, nk * sizeof(ef_match), hipMemcpyDeviceToHost, c->stream), "D2H matches");
-  }
-  return r.fetch(c);  // the features, then the synchronise of a host call
+  EF_TRY(r.stage_keys(c, bpad));
+  EF_TRY(topm ? search_topk_run(c, bpad, b, m, metric, r.kdev, r.mdev) : search_qpad(c, bpad, b, metric, r.kdev, r.mdev));
+  return r.fetch(c);
 }
 
 int ef_search_topk(ef_ctx* c, const float* Q, int64_t b, int32_t m, int32_t metric, int64_t* keys, uint32_t flags) {
   if (c && !keys) return set_err(c, EF_E_INVALID, "ef_search_topk: bad arguments");
-  return topk_impl(c, Q, false, EF_F32, b, m, metric, keys, nullptr, nullptr, flags, "ef_search_topk");
+  return query_impl(c, Q, false, EF_F32, b, m, true, metric, keys, nullptr, nullptr, flags, "ef_search_topk");
 }
 
 int ef_search_topk_matches(ef_ctx* c, const float* Q, int64_t b, int32_t m, int32_t metric, ef_match* out,
                            uint32_t flags) {
   if (c && !out) return set_err(c, EF_E_INVALID, "ef_search_topk_matches: bad arguments");
-  return topk_impl(c, Q, false, EF_F32, b, m, metric, nullptr, out, nullptr, flags, "ef_search_topk_matches");
+  return query_impl(c, Q, false, EF_F32, b, m, true, metric, nullptr, out, nullptr, flags, "ef_search_topk_matches");
 }
 
 int ef_recognize_topk(ef_ctx* c, const void* P, int32_t dtype, int64_t b, int32_t m, int32_t metric, int64_t* keys,
                       float* feats, uint32_t flags) {
   if (c && !keys) return set_err(c, EF_E_INVALID, "ef_recognize_topk: bad arguments");
-  return topk_impl(c, P, true, dtype, b, m, metric, keys, nullptr, feats, flags, "ef_recognize_topk");
+  return query_impl(c, P, true, dtype, b, m, true, metric, keys, nullptr, feats, flags, "ef_recognize_topk");
 }
 
 int ef_search_topk_stats(ef_ctx* c, int64_t out[4]) {
@@ -933,24 +883,24 @@ int ef_search_topk_stats(ef_ctx* c, int64_t out[4]) {
 
 int ef_search(ef_ctx* c, const float* Q, int64_t b, int32_t metric, int64_t* keys, uint32_t flags) {
   if (c && !keys) return set_err(c, EF_E_INVALID, "ef_search: bad arguments");
-  return search_impl(c, Q, b, metric, keys, nullptr, flags, "ef_search");
+  return query_impl(c, Q, false, EF_F32, b, 0, false, metric, keys, nullptr, nullptr, flags, "ef_search");
 }
 
 int ef_search_matches(ef_ctx* c, const float* Q, int64_t b, int32_t metric, ef_match* out, uint32_t flags) {
   if (c && !out) return set_err(c, EF_E_INVALID, "ef_search_matches: bad arguments");
-  return search_impl(c, Q, b, metric, nullptr, out, flags, "ef_search_matches");
+  return query_impl(c, Q, false, EF_F32, b, 0, false, metric, nullptr, out, nullptr, flags, "ef_search_matches");
 }
 
 int ef_recognize(ef_ctx* c, const void* P, int32_t dtype, int64_t b, int32_t metric, int64_t* keys, float* feats,
                  uint32_t flags) {
   if (c && !keys) return set_err(c, EF_E_INVALID, "ef_recognize: bad arguments");
-  return recognize_impl(c, P, dtype, b, metric, keys, nullptr, feats, flags, "ef_recognize");
+  return query_impl(c, P, true, dtype, b, 0, false, metric, keys, nullptr, feats, flags, "ef_recognize");
 }
 
 int ef_recognize_matches(ef_ctx* c, const void* P, int32_t dtype, int64_t b, int32_t metric, ef_match* out,
                          float* feats, uint32_t flags) {
   if (c && !out) return set_err(c, EF_E_INVALID, "ef_recognize_matches: bad arguments");
-  return recognize_impl(c, P, dtype, b, metric, nullptr, out, feats, flags, "ef_recognize_matches");
+  return query_impl(c, P, true, dtype, b, 0, false, metric, nullptr, out, feats, flags, "ef_recognize_matches");
 }
 
 int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
@@ -993,18 +943,15 @@ int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
     case EF_OPT_SEARCH_PREFIX:
       if (value != 0 && value != 1 && value != 16 && value != 32 && value != 64)
         return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_PREFIX must be 0, 1, 16, 32 or 64");
-      if (value >= 16 && c->g_kp > 0 && value >= c->g_kp)
+      if (value >= 16 && c->gal.kp > 0 && value >= c->gal.kp)
         return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_PREFIX: the prefix must be shorter than the gallery's padded k");
       c->opt_search_prefix = value;
-      c->prefix_ev_pending = false;  // a new setting starts with a clean guard
-      c->prefix_skip_left = 0;
+      c->der.reset();  // a new setting starts with a clean guard
       return EF_OK;
     case EF_OPT_SEARCH_PREFIX_SPLIT:
       if (value != 0 && value != 1) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_PREFIX_SPLIT must be 0 or 1");
       c->opt_search_prefix_split = value;
-      c->g1_valid = false;           // the compact copy is kept in one arithmetic's layout
-      c->prefix_ev_pending = false;  // a new setting starts with a clean guard
-      c->prefix_skip_left = 0;
+      c->der.reset();  // a clean guard; the compact copy is rebuilt in the new arithmetic's layout
       return EF_OK;
     case EF_OPT_SEARCH_TOPK_CAND:
       if (value < 16 || value > 4096) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_TOPK_CAND must be 16 .. 4096");

@@ -299,7 +299,8 @@ static int bank_tables(ef_ctx* c) {
   std::vector<BankSlotDev> tab;
   int64_t kp_off = 0, k_off = 0, pcol = 0, slice_off = 0;
   int lds_bytes = 0, kp_max = 0;
-  for (const BankSlot& s : bk.slots) {
+  for (const BankSlot& slot : bk.slots) {
+    const Gallery& s = slot.g;
     BankSlotDev t{};
     t.G = static_cast<const float*>(s.G.p);
     t.gmax2 = static_cast<const float*>(s.gmax2.p);
@@ -315,13 +316,13 @@ static int bank_tables(ef_ctx* c) {
     t.slice_off = slice_off;
     if (t.lds) lds_bytes = std::max(lds_bytes, (t.pt + 4) * s.kp * 4);
     kp_max = std::max(kp_max, s.kp);
-    for (int col = 0; col < s.kpw; col += 128)
-      items.push_back(BankProjItem{static_cast<const float*>(s.mean.p), static_cast<const float*>(s.W.p), s.kpw, col,
+    for (int col = 0; col < slot.kpw; col += 128)
+      items.push_back(BankProjItem{static_cast<const float*>(slot.mean.p), static_cast<const float*>(slot.W.p), slot.kpw, col,
                                    pcol + col});
     tab.push_back(t);
     kp_off += s.kp;
     k_off += s.k;
-    pcol += s.kpw;
+    pcol += slot.kpw;
     slice_off += t.nslices;
   }
   EF_TRY(ensure(c, bk.proj_items, items.size() * sizeof(BankProjItem)));
@@ -432,45 +433,11 @@ int ef_bank_add(ef_ctx* c, const float* mean, const float* W, int64_t d, int32_t
   if (!bk.slots.empty() && d != bk.d) return set_err(c, EF_E_INVALID, "ef_bank_add: d differs from the bank's");
   if (bk.slots.size() >= EF_BANK_MAX_MODELS) return set_err(c, EF_E_INVALID, "ef_bank_add: the bank is full");
   (void)hipSetDevice(c->device);
-  const bool dev = flags & EF_MEM_DEVICE;
-  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   BankSlot s;  // built here, appended only when complete: a failure below frees it and changes nothing
-  s.k = k;
-  s.kp = kp;
   s.kpw = (kp + 127) / 128 * 128;
-  s.n = n;
-  EF_TRY(ensure(c, s.mean, (size_t)d * sizeof(float)));
-  EF_TRY(ensure(c, s.W, (size_t)d * s.kpw * sizeof(float)));
   DevBuf tmp_w, tmp_g;  // host sources staged unpadded; freed after the synchronise below
-  EF_HIP(c, hipMemcpyAsync(s.mean.p, mean, (size_t)d * sizeof(float), kind, c->stream), "copy mean");
-  const float* wsrc = W;
-  if (!dev) {
-    EF_TRY(ensure(c, tmp_w, (size_t)d * k * sizeof(float)));
-    EF_HIP(c, hipMemcpyAsync(tmp_w.p, W, (size_t)d * k * sizeof(float), hipMemcpyHostToDevice, c->stream), "copy W");
-    wsrc = static_cast<const float*>(tmp_w.p);
-  }
-  EF_HIP(c, launch_pad_rows(c->stream, wsrc, d, k, d, static_cast<float*>(s.W.p), s.kpw), "pad W");
-  if (n > 0) {
-    EF_TRY(ensure(c, s.G, (size_t)n * kp * sizeof(float)));
-    EF_TRY(ensure(c, s.gnorm2, (size_t)n * sizeof(float)));
-    EF_TRY(ensure(c, s.ginv, (size_t)n * sizeof(float)));
-    EF_TRY(ensure(c, s.gmax2, 16));
-    const float* gsrc = G;
-    if (!dev && k != kp) {
-      EF_TRY(ensure(c, tmp_g, (size_t)n * k * sizeof(float)));
-      EF_HIP(c, hipMemcpyAsync(tmp_g.p, G, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice, c->stream),
-             "copy gallery");
-      gsrc = static_cast<const float*>(tmp_g.p);
-    }
-    if (k == kp)
-      EF_HIP(c, hipMemcpyAsync(s.G.p, G, (size_t)n * k * sizeof(float), kind, c->stream), "copy gallery");
-    else
-      EF_HIP(c, launch_pad_rows(c->stream, gsrc, n, k, n, static_cast<float*>(s.G.p), kp), "pad gallery");
-    EF_HIP(c,
-           launch_gallery_aux(c->stream, static_cast<const float*>(s.G.p), n, kp, static_cast<float*>(s.gnorm2.p),
-                              static_cast<float*>(s.ginv.p), static_cast<unsigned*>(s.gmax2.p)),
-           "gallery norms");
-  }
+  EF_TRY(weights_load(c, s.mean, s.W, mean, W, d, k, s.kpw, flags, tmp_w));
+  EF_TRY(gallery_load(c, s.g, G, n, k, flags, tmp_g, nullptr));
   EF_HIP(c, hipStreamSynchronize(c->stream), "ef_bank_add");
   try {
     bk.slots.push_back(std::move(s));
@@ -505,31 +472,21 @@ int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int3
   const int64_t bpad = round_up(b, BM);
   const int64_t coltiles = bk.total_kpw / 128;
 
-  const void* Pd = P;
-  if (!dev) {
-    const size_t bytes = (size_t)b * bk.d * (p_dtype == EF_U8 ? 1 : 4);
-    EF_TRY(ensure(c, bk.p_stage, bytes));
-    EF_HIP(c, hipMemcpyAsync(bk.p_stage.p, P, bytes, hipMemcpyHostToDevice, c->stream), "H2D probes");
-    Pd = bk.p_stage.p;
-  }
-  // where the kernels write: the caller's device pointers, or the staging block of a host call
-  long long* kdev = reinterpret_cast<long long*>(keys);
-  ef_match* mdev = matches;
+  const void* Pd = nullptr;
+  EF_TRY(stage_probes(c, P, p_dtype, b, bk.d, flags, bk.p_stage, &Pd));
+  // where the kernels write: the caller's device pointers, or the staging of a host call; the
+  // best slots are this call's own extension of it
+  Results r{dev, b, (int)M, bk.total_k, keys, matches, feats};
+  EF_TRY(r.stage_feats(c));
+  EF_TRY(r.stage_keys(c, b));
   int* sdev = best_slot;
-  float* fdev = feats;
-  if (!dev) {
-    Carve size_out, cv;
-    auto carve = [&](Carve& x) {
-      kdev = x.take<long long>((size_t)(b * M));
-      mdev = matches ? x.take<ef_match>((size_t)(b * M)) : nullptr;
-      sdev = best_slot ? x.take<int>((size_t)b) : nullptr;
-      fdev = feats ? x.take<float>((size_t)(b * bk.total_k)) : nullptr;
-    };
-    carve(size_out);
-    EF_TRY(ensure(c, bk.out, size_out.total));
-    cv.base = bk.out.p;
-    carve(cv);
+  if (!dev && best_slot) {
+    EF_TRY(ensure(c, bk.out, (size_t)b * sizeof(int)));
+    sdev = static_cast<int*>(bk.out.p);
   }
+  long long* kdev = r.kdev;
+  ef_match* mdev = r.mdev;
+  float* fdev = r.fdev;
 
   int ns = 0;
   int64_t pps = 0, nwg = 0;
@@ -563,7 +520,8 @@ int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int3
   for (;; pt_cap /= 2) {
     int64_t items = 0;
     items_max = 1;
-    for (const BankSlot& s : bk.slots) {
+    for (const BankSlot& slot : bk.slots) {
+      const Gallery& s = slot.g;
       int lds = 0;
       const int pt = std::min(bank_search_pt(s.kp, &lds), pt_cap);
       const int64_t rows = bank_slice_rows(s.n, M);
@@ -594,16 +552,9 @@ int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int3
                        metric, sdev);
   EF_HIP(c, hipGetLastError(), "bank merge");
   timer_end(c, &t);
-  if (dev) return EF_OK;  // stream-ordered; the caller synchronises
-  auto d2h = [&](void* dst, const void* src, size_t bytes) {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-  };
-  EF_HIP(c, d2h(keys, kdev, (size_t)(b * M) * sizeof(long long)), "D2H keys");
-  EF_HIP(c, d2h(matches, mdev, (size_t)(b * M) * sizeof(ef_match)), "D2H matches");
-  EF_HIP(c, d2h(best_slot, sdev, (size_t)b * sizeof(int)), "D2H best slot");
-  EF_HIP(c, d2h(feats, fdev, (size_t)(b * bk.total_k) * sizeof(float)), "D2H features");
-  EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
-  return EF_OK;
+  if (!dev && best_slot)
+    EF_HIP(c, hipMemcpyAsync(best_slot, sdev, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H best slot");
+  return r.fetch(c);
 }
 
 }  // extern "C"

@@ -84,6 +84,27 @@ struct SearchPiece {
   int64_t off, b, bpad;
 };
 
+// ---- the scan's arithmetic ----------------------------------------------------------
+// The one numbering of the scan variants, as every launcher takes it:
+//   0  fp32 kernels on the gallery itself
+//   1  split bf16 (hi + lo rows), the 16x16x32 kernels
+//   2  split bf16, the 32x32x16 kernels (at padded k < 128 the same kernel as 1)
+//   3  single-bf16 screen: wide k (kp > 128) only, counts as 1 below that and in the top-m search
+// split_variant resolves EF_OPT_SEARCH_SPLIT_BF16 to it once per search, on the host; the copy
+// of the gallery a variant reads has layout 3 (single-bf16 rows) for 3 and 1 (split rows) else.
+inline int split_variant(int64_t opt, int kp, bool topm) {
+  if (opt == 3) return kp > 128 && !topm ? 3 : 1;
+  return (int)opt;
+}
+inline int split_layout(int variant) { return variant == 3 ? 3 : 1; }
+// A resolved variant with the copies that match it: G3 the gallery copy in split_layout(variant)
+// (null for 0), Q3 the scratch [bpad][kp] for the probes' copy (variant != 0 at kp > 128 only).
+struct SplitScan {
+  int variant = 0;
+  const float* G3 = nullptr;
+  float* Q3 = nullptr;
+};
+
 // ---- error propagation --------------------------------------------------------------
 #define EF_TRY(expr)              \
   do {                            \
@@ -205,18 +226,65 @@ inline PrefixWs carve_prefix_ws(Carve& cv, size_t bpad, int k1, int kp) {
                   cv.take<long long>(bpad), cv.take<ef_match>(bpad)};
 }
 
+// ---- the plan of one search (host only: no HIP call) --------------------------------
+// What a search of b probes against n rows of padded width kp launches: the pieces
+// (search_pieces), every piece's plan built from that piece's own bpad (a shorter last piece's
+// plan may have more chunks), the prefix scan's plans when k1 > 0 (split1: its split-bf16
+// arithmetic), and the workspace they share, sized for the largest piece.  m > 0 plans the
+// top-m search (at least m chunks, and cap candidate rows per probe in the TopkWs).
+// ef_search_schedule reports it, search_run and search_topk_run launch it.
+struct SearchSchedule {
+  std::vector<SearchPiece> pieces;
+  std::vector<SearchPlan> plans, plans1;  // per piece; plans1 empty unless k1 > 0
+  size_t parts = 0;                        // largest nchunks x bpad over the pieces and both plans
+  int64_t bpad_max = 0;
+  size_t ws_bytes = 0;      // carve_search_ws(parts, bpad_max) and, m > 0, carve_topk_ws(bpad_max, cap)
+  size_t prefix_bytes = 0;  // carve_prefix_ws(bpad_max, k1, kp), k1 > 0
+};
+SearchSchedule search_schedule(int64_t b, int64_t n, int kp, int variant, int k1, bool split1, int m, int cap);
+
+// ---- resident gallery -----------------------------------------------------------------
+// Rows padded to kp = feature_pad(k) with their norms; the context holds one, a bank slot one.
+struct Gallery {
+  int64_t n = 0;
+  int k = 0, kp = 0;
+  DevBuf G;       // float[n][kp]
+  DevBuf gnorm2;  // float[n]  ||g||^2
+  DevBuf ginv;    // float[n]  1/||g|| (0 for a zero row)
+  DevBuf gmax2;   // uint (float bits) max ||g||^2
+};
+// What the context derives from its gallery on the first search that needs it, and the prefix
+// guard's history, which belongs to the gallery and settings it was seen on.  reset() forgets
+// all of it (the buffers stay allocated for the next build).  ef_gallery_set calls it, and so do
+// the setters of EF_OPT_SEARCH_PREFIX and EF_OPT_SEARCH_PREFIX_SPLIT: after either the next search
+// rebuilds the copies it reads (one pass over the gallery each), not only a clean guard.
+struct GalleryDerived {
+  DevBuf G3;          // copy of G for the split scans (same bytes)
+  int g3_layout = 0;  // what G3 holds: 0 nothing, 1 split (hi + lo) rows, 3 single-bf16 rows
+  // prefix scan (EF_OPT_SEARCH_PREFIX): compact copy of the first g1_k1 components of every row
+  DevBuf G1;      // float[n][g1_k1], or the same bytes as split-bf16 rows (g1_split)
+  DevBuf gnorm1;  // float[2][n]: fp32 ||g[:K1]||^2, then the aux kernel's unused 1/||.|| output
+  int g1_k1 = 0;  // 0: no copy
+  bool g1_split = false;  // only the copy the chosen arithmetic reads is kept
+  // the guard: counters of the last prefix search arrive in pinned memory behind ev
+  bool ev_pending = false;
+  int64_t ev_tiles = 0;  // probe tiles of the search ev belongs to
+  int skip_left = 0;     // searches the guard still keeps off the prefix scan
+  void reset() {
+    g3_layout = g1_k1 = 0;
+    ev_pending = false;
+    skip_left = 0;
+  }
+};
+
 // ---- model bank (ef_bank.hip) ---------------------------------------------------------
 // One resident (mean, W, gallery) triple.  W is padded to kpw = round_up(kp, 128) columns (the
 // grouped projection works in 128-column tiles), the gallery to kp as ef_gallery_set pads it.
 struct BankSlot {
-  int k = 0, kp = 0, kpw = 0;
-  int64_t n = 0;
-  DevBuf mean;    // float[d]
-  DevBuf W;       // float[d][kpw]
-  DevBuf G;       // float[n][kp]
-  DevBuf gnorm2;  // float[n]
-  DevBuf ginv;    // float[n]
-  DevBuf gmax2;   // float bits, max ||g||^2 (read on the device)
+  int kpw = 0;
+  DevBuf mean;  // float[d]
+  DevBuf W;     // float[d][kpw]
+  Gallery g;    // k, kp and the rows; gmax2 is read on the device
 };
 // The slots, their device tables (rebuilt on the first recognize after a change) and the
 // per-call scratch.  A slot is built completely before it is appended.
@@ -231,7 +299,7 @@ struct Bank {
   DevBuf part;        // float[nsplit][bpad][total_kpw] partial slabs
   DevBuf q;           // per slot float[bpad][kp], slot m at bpad * sum_{j<m} kp_j
   DevBuf ws;          // search scratch (per row slice and probe)
-  DevBuf out;         // staging of a host call's results
+  DevBuf out;         // staging of a host call's best slots (the rest: ef::Results)
   DevBuf p_stage;     // probe pixels staged from host
 };
 
@@ -255,8 +323,7 @@ struct ef_ctx {
   int64_t opt_tm_int64 = 0;
   int64_t opt_haar_ordered = 0;
   int64_t opt_jpeg_chunk_bits = 0;
-  int64_t opt_search_split_bf16 = 0;
-  int g3_layout = 0;  // what G3 holds: 1 split (hi + lo) rows, 3 single-bf16 rows
+  int64_t opt_search_split_bf16 = 0;  // resolved per search by ef::split_variant
   int64_t opt_jpeg_part_files = 8192;
   int64_t opt_fit_chebyshev = 1;
   hipStream_t stream = nullptr;  // own_stream or the caller's (ef_set_stream): not owned
@@ -277,31 +344,16 @@ struct ef_ctx {
   ef::DevBuf corr;     // float[kpw] (mean - round(mean)).W
 
   // gallery
-  int64_t n_gallery = 0, g_offset = 0;
-  int g_k = 0, g_kp = 0;
-  ef::DevBuf G;      // float[n][g_kp]
-  ef::DevBuf gnorm2; // float[n]  ||g||^2
-  ef::DevBuf ginv;   // float[n]  1/||g|| (0 for a zero row)
-  ef::DevBuf gmax2;  // uint (float bits) max ||g||^2
-  ef::DevBuf G3;     // split-bf16 copy of G (same bytes), built on the first split search
-  bool g3_valid = false;
+  ef::Gallery gal;       // gal.k == 0: none set yet
+  int64_t g_offset = 0;  // global index of row 0
   float gmax2_host = 0.f;
-  // prefix scan (EF_OPT_SEARCH_PREFIX): compact copy of the first g1_k1 components of every
-  // row with their squared norms, built on the first eligible search like G3
+  ef::GalleryDerived der;  // the split and prefix copies and the prefix guard (search_copies)
   int64_t opt_search_prefix = 1;
   int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32
-  ef::DevBuf G1;      // float[n][g1_k1], or the same bytes as split-bf16 rows (g1_split)
-  ef::DevBuf gnorm1;  // float[2][n]: fp32 ||g[:K1]||^2, then the aux kernel's unused 1/||.|| output
-  bool g1_valid = false;
-  int g1_k1 = 0;
-  bool g1_split = false;  // what G1 holds; only the copy the chosen arithmetic reads is kept
   ef::DevBuf prefix_ws;  // per-call scratch of the prefix path (ef::PrefixWs carve-out)
   // counters of the last prefix search, copied to pinned host memory behind the search
   // ([0] probes sent to the full-k scan); the next search reads them once prefix_ev has passed
   ef::PinnedBuf prefix_host;  // int[4]
-  bool prefix_ev_pending = false;
-  int64_t prefix_ev_tiles = 0;  // probe tiles of the search prefix_ev belongs to
-  int prefix_skip_left = 0;     // searches the guard still keeps off the prefix scan
   // what ef_search_stats reports: {probes, used the prefix scan, guard skipped}
   int64_t stats_probes = 0;
   bool stats_prefix = false, stats_skipped = false;
@@ -385,11 +437,15 @@ SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows =
 // rows per tile of the prefix scan at prefix length k1 (split: the split-bf16 scan)
 int prefix_tile_rows(int k1, bool split);
 std::vector<SearchPiece> search_pieces(int64_t b, int kp);
-// G3: split-bf16 copy of G (EF_OPT_SEARCH_SPLIT_BF16) or null for the fp32 kernels; Q3: scratch
-// [bpad][kp] for the split probes (kp > 128 with G3 only)
-hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl, const float* qpad, float* Q3,
-                         int64_t bpad, int64_t b, const float* G, const float* G3, const float* aux, int64_t n,
-                         int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, ef_ctx* c);
+// Top-1 search of one piece.  sp: the scan's variant (0 fp32; 1 split 16x16x32; 2 split 32x32x16;
+// 3 single-bf16 screen, wide k only — split_variant above) with the copies that match it.  The
+// sequence: the probes' copy into sp.Q3 (variant != 0 at kp > 128), then the timed main scan,
+// the queue counter's memset, reduce_kernel, the COLLECT scan over the queue, resolve_kernel.
+// timer: the context whose EF_KERNEL_SEARCH timer brackets the main scan; nothing else is read
+// from it.
+hipError_t launch_search(hipStream_t s, int kp, int metric, const SplitScan& sp, const SearchPlan& pl,
+                         const float* qpad, int64_t bpad, int64_t b, const float* G, const float* aux, int64_t n,
+                         int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, ef_ctx* timer);
 // Prefix search (EF_OPT_SEARCH_PREFIX; L2, fp32 scan, k1 < kp <= 128): the scan over the
 // compact prefix copy (G1, gnorm1), the proof per probe, and the full-k pipeline of
 // launch_search on the unproven probes.  Same keys / match records as launch_search.
@@ -408,20 +464,27 @@ hipError_t launch_split_rows(hipStream_t s, const float* G, int64_t n, int kp, v
 // single-bf16 copy for the bf16 screen (EF_OPT_SEARCH_SPLIT_BF16 = 3), kp % 64 == 0
 hipError_t launch_hi_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);
 hipError_t launch_keys_none(hipStream_t s, long long* keys, int64_t b, ef_match* match);
-// One scan launch of launch_search's kernels for (kp, metric, split): the main pass (per-chunk
-// top-2 records into ws) or the COLLECT pass over ws's queue.  split: 0 the fp32 kernels on G,
-// 1 / 2 the split-bf16 ones on the split copy (kp > 128: q is the split probes too).
-hipError_t launch_search_scan(hipStream_t s, int kp, int metric, bool collect, int split, const SearchPlan& pl,
-                              const float* q, const float* G, const float* aux, int64_t n, int64_t bpad,
-                              const SearchWs& ws);
+// One scan launch, the only map from (kp, metric, variant, main or COLLECT, cnt) to a scan
+// kernel: search_kernel, search16_kernel (kp == 128 under variant 1) and, kp > 128, the wide
+// kernels; variant 3 counts as 1 at kp <= 128.  The main pass writes per-chunk top-2 records
+// into ws, the COLLECT pass sweeps ws's queue.  q / G: what the variant reads (the fp32 probes
+// and gallery for 0, else the copies; at kp <= 128 the kernels split the fp32 probes themselves).
+// cnt: the main pass over a device-side probe count (the prefix path's second run: fp32, L2,
+// 32 <= kp <= 128 only).
+hipError_t launch_search_scan(hipStream_t s, int kp, int metric, bool collect, int variant, bool cnt,
+                              const SearchPlan& pl, const float* q, const float* G, const float* aux, int64_t n,
+                              int64_t bpad, const SearchWs& ws);
+// *qs <- the probes a scan of sp reads: qpad itself, or (variant != 0 at kp > 128) their copy in
+// sp.Q3, launched here, in the layout of the gallery copy
+hipError_t launch_scan_probes(hipStream_t s, const SplitScan& sp, const float* qpad, int64_t bpad, int kp,
+                              const float** qs);
 // Top-m search of one piece (ef_search_topk.hip): keys[b][m] and, when match is non-null,
-// match[b][m].  split as launch_search_scan; G3 / Q3 as launch_search; cap = rows of tw.cand
-// per probe; counters[1..3] accumulate what ef_search_topk_stats reports.
-hipError_t launch_search_topk(hipStream_t s, int kp, int metric, int split, int m, const SearchPlan& pl,
-                              const float* qpad, float* Q3, int64_t bpad, int64_t b, const float* G, const float* G3,
-                              const float* aux, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
-                              const TopkWs& tw, int cap, unsigned long long* counters, long long* keys,
-                              ef_match* match);
+// match[b][m].  sp as launch_search (never variant 3); cap = rows of tw.cand per probe;
+// counters[1..3] accumulate what ef_search_topk_stats reports.
+hipError_t launch_search_topk(hipStream_t s, int kp, int metric, const SplitScan& sp, int m, const SearchPlan& pl,
+                              const float* qpad, int64_t bpad, int64_t b, const float* G, const float* aux,
+                              int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const TopkWs& tw, int cap,
+                              unsigned long long* counters, long long* keys, ef_match* match);
 // keys[b][m] (+ merged[b][m]) <- the top-m merge of parts x b x m records (ef_search_topk.hip)
 hipError_t launch_matches_merge_topk(hipStream_t s, const ef_match* parts, int nparts, int64_t b, int m,
                                      long long* keys, ef_match* merged);
@@ -449,6 +512,43 @@ void host_parallel(int n, const std::function<void(int)>& fn);
 int host_threads();  // EF_OPT_HOST_THREADS (the job's CPU share)
 // all-gather over the attached communicator on ctx->stream (bytes per rank)
 int comm_allgather(ef_ctx* c, const void* send, void* recv, size_t bytes_per_rank);
+// ---- one call's inputs and outputs (ef_api.hip) ----------------------------------------
+// Where one call's keys, match records and features (each optional) are written: the caller's
+// own pointers with EF_MEM_DEVICE, else the context's staging buffers (ctx->keys: bpad x rec
+// keys, then the records; ctx->feats_dev), which fetch() copies to the caller's host pointers
+// before it synchronises.  rec: keys / records per probe (1, the m of a top-m search, the
+// bank's slots); fk: feature floats per probe.
+struct Results {
+  bool dev;
+  int64_t b;
+  int rec;
+  int64_t fk;
+  int64_t* keys;  // as the caller gave them
+  ef_match* match;
+  float* feats;
+  long long* kdev = nullptr;  // where the kernels write
+  ef_match* mdev = nullptr;
+  float* fdev = nullptr;
+  int stage_feats(ef_ctx* c);
+  int stage_keys(ef_ctx* c, int64_t bpad);  // keys are always produced
+  int fetch(ef_ctx* c) const;
+};
+// *Pd <- b probes of d pixels on the device: P itself with EF_MEM_DEVICE, else its copy in stage
+int stage_probes(ef_ctx* c, const void* P, int dtype, int64_t b, int64_t d, uint32_t flags, DevBuf& stage,
+                 const void** Pd);
+
+// The two loaders of resident data (ef_api.hip), for the context and the bank alike.  Sources are
+// host pointers, or device ones with EF_MEM_DEVICE; a host source that needs padding is staged
+// unpadded in `staging`, which the caller keeps alive until it has synchronised c->stream.
+// weights_load: mean[d] and W[d][k] into mean_dst and W_dst[d][kpw]; queued, not synchronised.
+// gallery_load: G[n][k] into g's buffers, grown in place (never a second copy of the rows), with
+// the norms; g is empty (n == 0) until the last step has succeeded.  gmax2_host non-null (the
+// context): the load is synchronised and max ||g||^2 is on the host on return; null (a bank
+// slot): everything stays queued and max ||g||^2 stays on the device.
+int weights_load(ef_ctx* c, DevBuf& mean_dst, DevBuf& W_dst, const float* mean, const float* W, int64_t d, int k,
+                 int kpw, uint32_t flags, DevBuf& staging);
+int gallery_load(ef_ctx* c, Gallery& g, const float* G, int64_t n, int k, uint32_t flags, DevBuf& staging,
+                 float* gmax2_host);
 hipError_t launch_pad_rows(hipStream_t s, const float* src, int64_t rows, int k, int64_t rows_pad,
                            float* dst, int kp);
 hipError_t launch_gallery_aux(hipStream_t s, const float* G, int64_t n, int kp, float* gnorm2,

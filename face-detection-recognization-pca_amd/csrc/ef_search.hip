@@ -1147,118 +1147,26 @@ SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows, 
   return pl;
 }
 
-// Split-bf16 search (KP <= 128): S3 kernel on the split gallery G3 for the scan and the
-// collect pass; reduce / resolve re-score from the fp32 gallery G as in the fp32 path.
-// KP > 128: the wide kernel streams the probes too, so they are split into Q3 first.
-// KP = 0: k > 512, row length kp at run time (wide kernels only).
+// One scan launch (ef_internal.hpp): the only place a scan kernel of KP <= 128 is named.  The
+// CNT form exists for the fp32 L2 kernels of KP >= 32 alone (the prefix path's second run).
 template <int KP, int M>
-static hipError_t search_s3_t(hipStream_t s, const SearchPlan& pl, const float* qpad, float* Q3, int64_t bpad,
-                              int64_t b, const float* G, const float* G3, const float* aux, int64_t n,
-                              int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, TimerEvt* tev,
-                              ef_ctx* c, int kp) {
-  if constexpr (KP > 128 || KP == 0) {
-    if (!Q3) return hipErrorInvalidValue;
-    // 16x16x32 split kernel unless the 32x32x16 one (2) or the single-bf16 screen (3) is asked for
-    const int variant = c->opt_search_split_bf16 == 2 || c->opt_search_split_bf16 == 3 ? (int)c->opt_search_split_bf16 : 1;
-    hipError_t e = variant == 3 ? launch_hi_rows(s, qpad, bpad, kp, Q3) : launch_split_rows(s, qpad, bpad, kp, Q3);
-    if (e != hipSuccess) return e;
-    timer_begin(c, EF_KERNEL_SEARCH, tev);
-    e = launch_search_wide(s, kp, M, false, variant, pl, Q3, G3, aux, n, bpad, ws);
-    timer_end(c, tev);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws.amb_count, 0, sizeof(int), s);
-    if (e != hipSuccess) return e;
-    const dim3 pgrid((unsigned)((b + 3) / 4));
-    if (variant == 3)
-      hipLaunchKernelGGL((reduce_kernel<KP, M, 2>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl.nchunks, G, n,
-                         g_offset, gmax2, ws, keys, kp);
-    else
-      hipLaunchKernelGGL((reduce_kernel<KP, M, 1>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl.nchunks, G, n,
-                         g_offset, gmax2, ws, keys, kp);
-    e = launch_search_wide(s, kp, M, true, variant, pl, Q3, G3, aux, n, bpad, ws);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, dim3(256), 0, s, qpad, G, n, g_offset, gmax2, ws, keys, kp);
-    return hipGetLastError();
-  } else {
-    (void)Q3;
-    const dim3 grid((unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
-    // KP = 128: the 16 x 16 x 32 kernel unless the 32 x 32 x 16 one is asked for (option 2)
-    const bool k16 = KP == 128 && c->opt_search_split_bf16 != 2;
-    timer_begin(c, EF_KERNEL_SEARCH, tev);
-    if (k16)
-      hipLaunchKernelGGL((search16_kernel<M, false>), grid, block, 0, s, qpad, G3, aux, n, pl.n_ptiles,
-                         pl.tiles_per_chunk, bpad, ws);
-    else
-      hipLaunchKernelGGL((search_kernel<KP, M, false, true>), grid, block, 0, s, qpad, G3, aux, n, pl.n_ptiles,
-                         pl.tiles_per_chunk, bpad, ws);
-    timer_end(c, tev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws.amb_count, 0, sizeof(int), s);
-    if (e != hipSuccess) return e;
-    const dim3 pgrid((unsigned)((b + 3) / 4));
-    hipLaunchKernelGGL((reduce_kernel<KP, M, 1>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl.nchunks, G, n,
-                       g_offset, gmax2, ws, keys, kp);
-    if (k16)
-      hipLaunchKernelGGL((search16_kernel<M, true>), dim3((unsigned)pl.c_grid), block, 0, s, qpad, G3, aux, n,
-                         pl.c_chunks, pl.c_tpc, bpad, ws);
-    else
-      hipLaunchKernelGGL((search_kernel<KP, M, true, true>), dim3((unsigned)pl.c_grid), block, 0, s, qpad, G3,
-                         aux, n, pl.c_chunks, pl.c_tpc, bpad, ws);
-    hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, dim3(256), 0, s, qpad, G, n, g_offset, gmax2, ws, keys, kp);
-    return hipGetLastError();
-  }
-}
-
-template <int KP, int M>
-static hipError_t search_t(hipStream_t s, const SearchPlan& pl, const float* qpad, float* Q3, int64_t bpad,
-                           int64_t b, const float* G, const float* G3, const float* aux, int64_t n,
-                           int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, bool timed_main,
-                           TimerEvt* tev, ef_ctx* c, int kp) {
-  constexpr bool wide = KP > 128 || KP == 0;
-  if (G3) return search_s3_t<KP, M>(s, pl, qpad, Q3, bpad, b, G, G3, aux, n, g_offset, gmax2, ws, keys, tev, c, kp);
-  const dim3 grid((unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
-  if (timed_main) timer_begin(c, EF_KERNEL_SEARCH, tev);
-  if constexpr (wide) {
-    const hipError_t e = launch_search_wide(s, kp, M, false, 0, pl, qpad, G, aux, n, bpad, ws);
-    if (e != hipSuccess) return e;
-  } else {
-    hipLaunchKernelGGL((search_kernel<KP, M, false>), grid, block, 0, s, qpad, G, aux, n, pl.n_ptiles,
-                       pl.tiles_per_chunk, bpad, ws);
-  }
-  if (timed_main) timer_end(c, tev);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(ws.amb_count, 0, sizeof(int), s);
-  if (e != hipSuccess) return e;
-  const dim3 pgrid((unsigned)((b + 3) / 4));
-  hipLaunchKernelGGL((reduce_kernel<KP, M>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl.nchunks, G, n, g_offset,
-                     gmax2, ws, keys, kp);
-  // queued (fp32-ambiguous) probes: collect + fp64 resolve; both exit at once when none
-  if constexpr (wide) {
-    e = launch_search_wide(s, kp, M, true, 0, pl, qpad, G, aux, n, bpad, ws);
-    if (e != hipSuccess) return e;
-  } else {
-    hipLaunchKernelGGL((search_kernel<KP, M, true>), dim3((unsigned)pl.c_grid), block, 0, s, qpad, G, aux, n,
-                       pl.c_chunks, pl.c_tpc, bpad, ws);
-  }
-  hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, dim3(256), 0, s, qpad, G, n, g_offset, gmax2, ws, keys, kp);
-  return hipGetLastError();
-}
-
-// One scan launch for the top-m search (ef_search_topk.hip): launch_search's kernels, main
-// pass or COLLECT, without its reduce / resolve.
-template <int KP, int M>
-static hipError_t scan_t(hipStream_t s, bool collect, int split, const SearchPlan& pl, const float* q, const float* G,
-                         const float* aux, int64_t n, int64_t bpad, const SearchWs& ws) {
+static hipError_t scan_t(hipStream_t s, bool collect, int variant, bool cnt, const SearchPlan& pl, const float* q,
+                         const float* G, const float* aux, int64_t n, int64_t bpad, const SearchWs& ws) {
   const dim3 grid(collect ? (unsigned)pl.c_grid : (unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
   const int a = collect ? pl.c_chunks : pl.n_ptiles, t = collect ? pl.c_tpc : pl.tiles_per_chunk;
-  if (split && KP == 128 && split != 2) {
+  if (cnt) {
+    if constexpr (M == EF_METRIC_L2 && KP >= 32) {
+      if (collect || variant) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((search_kernel<KP, M, false, false, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  } else if (variant && KP == 128 && variant != 2) {
     if (collect)
       hipLaunchKernelGGL((search16_kernel<M, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
     else
       hipLaunchKernelGGL((search16_kernel<M, false>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
-  } else if (split) {
+  } else if (variant) {
     if (collect)
       hipLaunchKernelGGL((search_kernel<KP, M, true, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
     else
@@ -1271,14 +1179,15 @@ static hipError_t scan_t(hipStream_t s, bool collect, int split, const SearchPla
   return hipGetLastError();
 }
 
-hipError_t launch_search_scan(hipStream_t s, int kp, int metric, bool collect, int split, const SearchPlan& pl,
-                              const float* q, const float* G, const float* aux, int64_t n, int64_t bpad,
-                              const SearchWs& ws) {
-  if (kp > 128) return launch_search_wide(s, kp, metric, collect, split == 2 ? 2 : split ? 1 : 0, pl, q, G, aux, n, bpad, ws);
-#define EF_SCAN_CASE(KPV)                                                                              \
-  case KPV:                                                                                            \
-    return metric == EF_METRIC_L2 ? scan_t<KPV, EF_METRIC_L2>(s, collect, split, pl, q, G, aux, n, bpad, ws) \
-                                  : scan_t<KPV, EF_METRIC_COSINE>(s, collect, split, pl, q, G, aux, n, bpad, ws);
+hipError_t launch_search_scan(hipStream_t s, int kp, int metric, bool collect, int variant, bool cnt,
+                              const SearchPlan& pl, const float* q, const float* G, const float* aux, int64_t n,
+                              int64_t bpad, const SearchWs& ws) {
+  if (kp > 128)
+    return cnt ? hipErrorInvalidValue : launch_search_wide(s, kp, metric, collect, variant, pl, q, G, aux, n, bpad, ws);
+#define EF_SCAN_CASE(KPV)                                                                                          \
+  case KPV:                                                                                                        \
+    return metric == EF_METRIC_L2 ? scan_t<KPV, EF_METRIC_L2>(s, collect, variant, cnt, pl, q, G, aux, n, bpad, ws) \
+                                  : scan_t<KPV, EF_METRIC_COSINE>(s, collect, variant, cnt, pl, q, G, aux, n, bpad, ws);
   switch (kp) {
     EF_SCAN_CASE(16)
     EF_SCAN_CASE(32)
@@ -1290,32 +1199,79 @@ hipError_t launch_search_scan(hipStream_t s, int kp, int metric, bool collect, i
 #undef EF_SCAN_CASE
 }
 
-hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl, const float* qpad, float* Q3,
-                         int64_t bpad, int64_t b, const float* G, const float* G3, const float* aux, int64_t n,
-                         int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, ef_ctx* c) {
+hipError_t launch_scan_probes(hipStream_t s, const SplitScan& sp, const float* qpad, int64_t bpad, int kp,
+                              const float** qs) {
+  *qs = qpad;
+  if (!sp.variant || kp <= 128) return hipSuccess;
+  // the wide kernels stream the probes too, in the layout of the gallery copy
+  if (!sp.Q3) return hipErrorInvalidValue;
+  *qs = sp.Q3;
+  return sp.variant == 3 ? launch_hi_rows(s, qpad, bpad, kp, sp.Q3) : launch_split_rows(s, qpad, bpad, kp, sp.Q3);
+}
+
+// The top-1 sequence, the only copy: the main scan of (variant, cnt) over (qs, Gs), timed when
+// timer is given; the queue counter's memset (cnt: the caller zeroed it with its own counters);
+// reduce_kernel in the variant's flavour (1 split scores, 2 the screen's single-bf16 ones), which
+// queues the probes the scan's arithmetic cannot decide; the COLLECT scan over the queue;
+// resolve_kernel in fp64.  reduce / resolve re-score from the fp32 probes q and gallery G; the
+// last two exit at once when nothing is queued.  KP = 0: k > 512, row length kp at run time.
+template <int KP, int M>
+static hipError_t top1_t(hipStream_t s, int variant, bool cnt, const SearchPlan& pl, const float* q, const float* qs,
+                         const float* Gs, int64_t bpad, int64_t b, const float* G, const float* aux, int64_t n,
+                         int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, ef_ctx* timer, int kp) {
+  constexpr bool wide = KP > 128 || KP == 0;
+  if (!wide && variant == 3) variant = 1;
   TimerEvt tev;
-  tev.kernel = -1;
-#define EF_SEARCH_CASE(KPV)                                                                                 \
-  case KPV:                                                                                                 \
-    return metric == EF_METRIC_L2                                                                           \
-               ? search_t<KPV, EF_METRIC_L2>(s, pl, qpad, Q3, bpad, b, G, G3, aux, n, g_offset, gmax2, ws, keys, \
-                                             true, &tev, c, kp)                                                   \
-               : search_t<KPV, EF_METRIC_COSINE>(s, pl, qpad, Q3, bpad, b, G, G3, aux, n, g_offset, gmax2, ws, \
-                                                 keys, true, &tev, c, kp);
-  switch (kp) {
+  if (timer) timer_begin(timer, EF_KERNEL_SEARCH, &tev);
+  hipError_t e = launch_search_scan(s, kp, M, false, variant, cnt, pl, qs, Gs, aux, n, bpad, ws);
+  if (timer) timer_end(timer, &tev);
+  if (e != hipSuccess) return e;
+  if (!cnt && (e = hipMemsetAsync(ws.amb_count, 0, sizeof(int), s)) != hipSuccess) return e;
+  const dim3 pgrid((unsigned)((b + 3) / 4)), pblock(256);
+#define EF_REDUCE(...)                                                                                          \
+  hipLaunchKernelGGL((reduce_kernel<KP, M, __VA_ARGS__>), pgrid, pblock, 0, s, q, b, bpad, pl.nchunks, G, n, \
+                     g_offset, gmax2, ws, keys, kp)
+  if (cnt) {
+    if constexpr (!wide && M == EF_METRIC_L2 && KP >= 32) EF_REDUCE(0, true);
+  } else if (variant == 3) {
+    if constexpr (wide) EF_REDUCE(2);
+  } else if (variant) {
+    EF_REDUCE(1);
+  } else {
+    EF_REDUCE(0);
+  }
+#undef EF_REDUCE
+  if ((e = launch_search_scan(s, kp, M, true, variant, false, pl, qs, Gs, aux, n, bpad, ws)) != hipSuccess) return e;
+  hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, pblock, 0, s, q, G, n, g_offset, gmax2, ws, keys, kp);
+  return hipGetLastError();
+}
+
+hipError_t launch_search(hipStream_t s, int kp, int metric, const SplitScan& sp, const SearchPlan& pl,
+                         const float* qpad, int64_t bpad, int64_t b, const float* G, const float* aux, int64_t n,
+                         int64_t g_offset, float gmax2, const SearchWs& ws, long long* keys, ef_ctx* timer) {
+  if (sp.variant && !sp.G3) return hipErrorInvalidValue;
+  const float* qs = nullptr;
+  const hipError_t e = launch_scan_probes(s, sp, qpad, bpad, kp, &qs);
+  if (e != hipSuccess) return e;
+  const float* Gs = sp.variant ? sp.G3 : G;
+#define EF_SEARCH_CASE(KPV)                                                                                        \
+  case KPV:                                                                                                        \
+    return metric == EF_METRIC_L2                                                                                  \
+               ? top1_t<KPV, EF_METRIC_L2>(s, sp.variant, false, pl, qpad, qs, Gs, bpad, b, G, aux, n, g_offset, gmax2, \
+                                           ws, keys, timer, kp)                                                    \
+               : top1_t<KPV, EF_METRIC_COSINE>(s, sp.variant, false, pl, qpad, qs, Gs, bpad, b, G, aux, n, g_offset,  \
+                                               gmax2, ws, keys, timer, kp);
+  // k > 512 (a multiple of 128): the wide kernels with the row length at run time, KP = 0
+  switch (kp > 512 ? (kp % 128 == 0 ? 0 : -1) : kp > 0 ? kp : -1) {
     EF_SEARCH_CASE(16)
     EF_SEARCH_CASE(32)
     EF_SEARCH_CASE(64)
     EF_SEARCH_CASE(128)
     EF_SEARCH_CASE(256)
     EF_SEARCH_CASE(512)
-    default:  // k > 512 (a multiple of 128): the wide kernels with the row length at run time
-      if (kp <= 512 || kp % 128 != 0) return hipErrorInvalidValue;
-      return metric == EF_METRIC_L2
-                 ? search_t<0, EF_METRIC_L2>(s, pl, qpad, Q3, bpad, b, G, G3, aux, n, g_offset, gmax2, ws, keys, true,
-                                             &tev, c, kp)
-                 : search_t<0, EF_METRIC_COSINE>(s, pl, qpad, Q3, bpad, b, G, G3, aux, n, g_offset, gmax2, ws, keys,
-                                                 true, &tev, c, kp);
+    EF_SEARCH_CASE(0)
+    default:
+      return hipErrorInvalidValue;
   }
 #undef EF_SEARCH_CASE
 }
@@ -1328,8 +1284,8 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SearchPlan& pl
 //      split-bf16 rows, the kernel splits Q1 in registers and runs the split chain, 3 bf16
 //      MFMAs of 32 cycles per 16 k against 8 fp32 ones of 64, in 256-row tiles (profiles/r11).
 //   2. reduce_prefix_kernel: proven probes get their key / match record, the others are listed.
-//   3. The listed probes' rows are gathered into qpad2 and go through search_t's sequence
-//      (main scan, reduce, COLLECT, resolve) with the device count in place of b; the grids
+//   3. The listed probes' rows are gathered into qpad2 and go through top1_t's sequence
+//      in its cnt form (untimed, the device count in place of b, no memset of its own); the grids
 //      are sized for bpad and the work past the count returns at once, so the host never
 //      learns the count.  Their keys / records are scattered back by the list.
 template <int KP, int K1, bool S3>
@@ -1338,8 +1294,7 @@ static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const Sea
                                   int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
                                   long long* keys, ef_ctx* c) {
   constexpr int M = EF_METRIC_L2;
-  const dim3 grid((unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
-  const dim3 pgrid((unsigned)((b + 3) / 4));
+  const dim3 block(512), pgrid((unsigned)((b + 3) / 4));
   hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((bpad * (K1 / 4) + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(qpad), bpad, KP / 4, K1 / 4, reinterpret_cast<float4*>(pw.q1));
   TimerEvt tev;
@@ -1359,14 +1314,9 @@ static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const Sea
                      reinterpret_cast<float4*>(pw.qpad2));
   SearchWs w2 = ws;
   w2.match = ws.match ? pw.match2 : nullptr;
-  hipLaunchKernelGGL((search_kernel<KP, M, false, false, true>), grid, block, 0, s, pw.qpad2, G, gnorm2, n,
-                     pl.n_ptiles, pl.tiles_per_chunk, bpad, w2);
-  hipLaunchKernelGGL((reduce_kernel<KP, M, 0, true>), pgrid, dim3(256), 0, s, pw.qpad2, b, bpad, pl.nchunks, G, n,
-                     g_offset, gmax2, w2, pw.keys2, KP);
-  hipLaunchKernelGGL((search_kernel<KP, M, true>), dim3((unsigned)pl.c_grid), block, 0, s, pw.qpad2, G, gnorm2, n,
-                     pl.c_chunks, pl.c_tpc, bpad, w2);
-  hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, dim3(256), 0, s, pw.qpad2, G, n, g_offset, gmax2, w2, pw.keys2,
-                     KP);
+  e = top1_t<KP, M>(s, 0, true, pl, pw.qpad2, pw.qpad2, G, bpad, b, G, gnorm2, n, g_offset, gmax2, w2, pw.keys2,
+                    nullptr, KP);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(prefix_scatter_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, s, pw.list, ws.amb_count,
                      pw.keys2, w2.match, keys, ws.match);
   return hipGetLastError();

@@ -300,29 +300,25 @@ __global__ __launch_bounds__(256) void topk_sweep_kernel(const float* __restrict
 }
 
 template <int M>
-static hipError_t topk_t(hipStream_t s, int kp, int split, int m, const SearchPlan& pl, const float* qpad, float* Q3,
-                         int64_t bpad, int64_t b, const float* G, const float* G3, const float* aux, int64_t n,
-                         int64_t g_offset, float gmax2, const SearchWs& ws, const TopkWs& tw, int cap,
-                         unsigned long long* counters, long long* keys, ef_match* match) {
-  const float* qs = qpad;
-  const float* Gs = split ? G3 : G;
-  const int s3 = split ? 1 : 0;
+static hipError_t topk_t(hipStream_t s, int kp, const SplitScan& sp, int m, const SearchPlan& pl, const float* qpad,
+                         int64_t bpad, int64_t b, const float* G, const float* aux, int64_t n, int64_t g_offset,
+                         float gmax2, const SearchWs& ws, const TopkWs& tw, int cap, unsigned long long* counters,
+                         long long* keys, ef_match* match) {
+  const int split = sp.variant, s3 = split ? 1 : 0;
+  const float* Gs = split ? sp.G3 : G;
+  const float* qs = nullptr;
   hipError_t e;
-  if (split && kp > 128) {  // the wide split kernels stream split probes
-    if (!Q3) return hipErrorInvalidValue;
-    if ((e = launch_split_rows(s, qpad, bpad, kp, Q3)) != hipSuccess) return e;
-    qs = Q3;
-  }
+  if ((e = launch_scan_probes(s, sp, qpad, bpad, kp, &qs)) != hipSuccess) return e;
   SearchWs w1 = ws;
   w1.cand = tw.cand;
   w1.cand_cap = cap;
   w1.match = nullptr;
-  if ((e = launch_search_scan(s, kp, M, false, split, pl, qs, Gs, aux, n, bpad, w1)) != hipSuccess) return e;
+  if ((e = launch_search_scan(s, kp, M, false, split, false, pl, qs, Gs, aux, n, bpad, w1)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(tw.counts, 0, 4 * sizeof(int), s)) != hipSuccess) return e;
   const dim3 block(256), per_probe((unsigned)b);
   hipLaunchKernelGGL((topk_threshold_kernel<M>), dim3((unsigned)((b + 3) / 4)), block, 0, s, qpad, b, bpad, pl.nchunks,
                      kp, m, s3, gmax2, w1);
-  if ((e = launch_search_scan(s, kp, M, true, split, pl, qs, Gs, aux, n, bpad, w1)) != hipSuccess) return e;
+  if ((e = launch_search_scan(s, kp, M, true, split, false, pl, qs, Gs, aux, n, bpad, w1)) != hipSuccess) return e;
   hipLaunchKernelGGL((topk_resolve_kernel<M>), per_probe, block, 0, s, qpad, G, n, g_offset, gmax2, kp, m, s3,
                      w1.amb_count, w1.amb_list, w1.cand_cnt, tw.cand, cap,
                      TopkNext{tw.list2, tw.thr2, tw.cnt2, tw.counts}, counters, 1, keys, match);
@@ -332,7 +328,7 @@ static hipError_t topk_t(hipStream_t s, int kp, int split, int m, const SearchPl
   w2.amb_list = tw.list2;
   w2.thr = tw.thr2;
   w2.cand_cnt = tw.cnt2;
-  if ((e = launch_search_scan(s, kp, M, true, split, pl, qs, Gs, aux, n, bpad, w2)) != hipSuccess) return e;
+  if ((e = launch_search_scan(s, kp, M, true, split, false, pl, qs, Gs, aux, n, bpad, w2)) != hipSuccess) return e;
   hipLaunchKernelGGL((topk_resolve_kernel<M>), per_probe, block, 0, s, qpad, G, n, g_offset, gmax2, kp, m, s3,
                      tw.counts, tw.list2, tw.cnt2, tw.cand, cap, TopkNext{tw.list3, nullptr, nullptr, tw.counts + 1},
                      counters, 0, keys, match);
@@ -341,17 +337,18 @@ static hipError_t topk_t(hipStream_t s, int kp, int split, int m, const SearchPl
   return hipGetLastError();
 }
 
-hipError_t launch_search_topk(hipStream_t s, int kp, int metric, int split, int m, const SearchPlan& pl,
-                              const float* qpad, float* Q3, int64_t bpad, int64_t b, const float* G, const float* G3,
-                              const float* aux, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
-                              const TopkWs& tw, int cap, unsigned long long* counters, long long* keys,
-                              ef_match* match) {
-  if (m < 1 || m > 64 || cap < m || cap > kTopkCapMax || b < 1 || n < 1 || n > INT_MAX) return hipErrorInvalidValue;
+hipError_t launch_search_topk(hipStream_t s, int kp, int metric, const SplitScan& sp, int m, const SearchPlan& pl,
+                              const float* qpad, int64_t bpad, int64_t b, const float* G, const float* aux,
+                              int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const TopkWs& tw, int cap,
+                              unsigned long long* counters, long long* keys, ef_match* match) {
+  if (m < 1 || m > 64 || cap < m || cap > kTopkCapMax || b < 1 || n < 1 || n > INT_MAX || sp.variant == 3 ||
+      (sp.variant && !sp.G3))
+    return hipErrorInvalidValue;
   return metric == EF_METRIC_L2
-             ? topk_t<EF_METRIC_L2>(s, kp, split, m, pl, qpad, Q3, bpad, b, G, G3, aux, n, g_offset, gmax2, ws, tw,
-                                    cap, counters, keys, match)
-             : topk_t<EF_METRIC_COSINE>(s, kp, split, m, pl, qpad, Q3, bpad, b, G, G3, aux, n, g_offset, gmax2, ws,
-                                        tw, cap, counters, keys, match);
+             ? topk_t<EF_METRIC_L2>(s, kp, sp, m, pl, qpad, bpad, b, G, aux, n, g_offset, gmax2, ws, tw, cap, counters,
+                                    keys, match)
+             : topk_t<EF_METRIC_COSINE>(s, kp, sp, m, pl, qpad, bpad, b, G, aux, n, g_offset, gmax2, ws, tw, cap,
+                                        counters, keys, match);
 }
 
 // ------------------------------------------------------------------------------- merge

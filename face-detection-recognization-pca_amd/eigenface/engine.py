@@ -548,30 +548,60 @@ class Engine:
         self.gallery_n, self.gallery_k = int(n), int(k)
         self.gallery_owner = owner if owner is not None else object()
 
+    def _probes(self, X, pixels):
+        """The probes of a search call as the C side reads them: (array or tensor, pointer,
+        dtype code, b, on_device).  Features are float32 (b, gallery_k), pixels uint8 or float32
+        (b, model_d); host input is converted to a contiguous array, a device tensor is taken
+        as it is (made contiguous).  The C side reads b * width elements from the pointer, so a
+        narrower or 1-D input, which would be read past its end, is refused here."""
+        dev = _is_dev(X)
+        if pixels:
+            if dev:
+                x, xp, dtype = self._dev_pixels(X)
+            else:
+                x = np.asarray(X)
+                dtype = N.EF_U8 if x.dtype == np.uint8 else N.EF_F32
+                x, xp = _host(x, np.uint8 if dtype == N.EF_U8 else np.float32)
+            want, name = self.model_d, "P"
+        else:
+            if dev:
+                import torch
+                x, xp = _dev(X, torch.float32)
+            else:
+                x, xp = _host(X, np.float32)
+            dtype, want, name = N.EF_F32, self.gallery_k, "Q"
+        if x.ndim != 2 or x.shape[1] != want:
+            raise ValueError(f"{name} must be (b, {want}), got {tuple(x.shape)}")
+        return x, xp, dtype, x.shape[0], dev
+
+    def _result(self, x, dev, out, shape, records, what):
+        """The output of a call on probes x and its pointer: for device input the caller's
+        int64 tensor (validated) or a new one, records as (.., 3) int64; for host input a new
+        array of int64 keys or N.MATCH_DTYPE records."""
+        if not dev:
+            res = np.empty(shape, dtype=N.MATCH_DTYPE if records else np.int64)
+            return res, res.ctypes.data
+        import torch
+        if records:
+            shape = shape + (3,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=x.device)
+        self._dev_out(out, shape, torch.int64, what)
+        return out, out.data_ptr()
+
+    def _order(self, dev, *tensors):
+        return self._torch_order(*tensors) if dev else contextlib.nullcontext()
+
     def search_keys(self, Q, metric="l2", keys=None):
         """Packed keys (int64) of the best gallery row per probe."""
         mt = _metric(metric)
         if self.gallery_k is None:
             raise RuntimeError("no gallery: call set_gallery first")
-        if _is_dev(Q):
-            import torch
-            q, qp = _dev(Q, torch.float32)
-            if q.ndim != 2 or q.shape[1] != self.gallery_k:
-                raise ValueError(f"Q must be (b, {self.gallery_k}), got {tuple(q.shape)}")
-            b = q.shape[0]
-            if keys is None:
-                keys = torch.empty(b, dtype=torch.int64, device=q.device)
-            self._dev_out(keys, (b,), torch.int64, "keys")
-            with self._torch_order(q, keys):
-                self._chk(self._lib.ef_search(self._h, qp, b, mt, keys.data_ptr(), N.EF_MEM_DEVICE))
-            return keys
-        q, qp = _host(Q, np.float32)
-        if q.ndim != 2 or q.shape[1] != self.gallery_k:
-            raise ValueError(f"Q must be (b, {self.gallery_k}), got {q.shape}")
-        b = q.shape[0]
-        k = np.empty(b, dtype=np.int64)
-        self._chk(self._lib.ef_search(self._h, qp, b, mt, k.ctypes.data, 0))
-        return k
+        q, qp, _, b, dev = self._probes(Q, pixels=False)
+        keys, kp = self._result(q, dev, keys, (b,), False, "keys")
+        with self._order(dev, q, keys):
+            self._chk(self._lib.ef_search(self._h, qp, b, mt, kp, N.EF_MEM_DEVICE if dev else 0))
+        return keys
 
     def search(self, Q, metric="l2"):
         """Return (idx int64, best float32): L2 -> squared distance, cosine -> similarity."""
@@ -585,34 +615,20 @@ class Engine:
         mt = _metric(metric)
         if self.model_k is None or self.gallery_k is None:
             raise RuntimeError("recognize needs a model and a gallery")
-        if _is_dev(P):
-            import torch
-            p, pp, dtype = self._dev_pixels(P)
-            b = p.shape[0]
-            if keys is None:
-                keys = torch.empty(b, dtype=torch.int64, device=p.device)
-            self._dev_out(keys, (b,), torch.int64, "keys")
-            fp = None
-            if feats is not None:
-                fp = self._dev_out(feats, (b, self.model_k), torch.float32, "feats").data_ptr()
-            with self._torch_order(p, keys, feats):
-                self._chk(self._lib.ef_recognize(self._h, pp, dtype, b, mt, keys.data_ptr(), fp, N.EF_MEM_DEVICE))
-            return keys
-        p = np.asarray(P)
-        dtype = N.EF_U8 if p.dtype == np.uint8 else N.EF_F32
-        p, pp = _host(p, np.uint8 if dtype == N.EF_U8 else np.float32)
-        if p.ndim != 2 or p.shape[1] != self.model_d:
-            raise ValueError(f"P must be (b, {self.model_d}), got {p.shape}")
-        b = p.shape[0]
-        k = np.empty(b, dtype=np.int64)
+        p, pp, dtype, b, dev = self._probes(P, pixels=True)
+        keys, kp = self._result(p, dev, keys, (b,), False, "keys")
         fp = None
-        if feats is not None:
+        if dev and feats is not None:
+            import torch
+            fp = self._dev_out(feats, (b, self.model_k), torch.float32, "feats").data_ptr()
+        elif feats is not None:
             if not (isinstance(feats, np.ndarray) and feats.dtype == np.float32 and feats.shape == (b, self.model_k)
                     and feats.flags.c_contiguous):
                 raise ValueError(f"feats must be a contiguous float32 array of shape {(b, self.model_k)}")
             fp = feats.ctypes.data
-        self._chk(self._lib.ef_recognize(self._h, pp, dtype, b, mt, k.ctypes.data, fp, 0))
-        return k
+        with self._order(dev, p, keys, feats):
+            self._chk(self._lib.ef_recognize(self._h, pp, dtype, b, mt, kp, fp, N.EF_MEM_DEVICE if dev else 0))
+        return keys
 
     # ------------------------------------------------------- exact match records
     def search_matches(self, Q, metric="l2", out=None):
@@ -630,44 +646,15 @@ class Engine:
             raise RuntimeError("no gallery: call set_gallery first")
         if not search and self.model_k is None:
             raise RuntimeError("recognize needs a model and a gallery")
-        if _is_dev(X):
-            import torch
+        x, xp, dtype, b, dev = self._probes(X, pixels=not search)
+        out, op = self._result(x, dev, out, (b,), True, "out")
+        flags = N.EF_MEM_DEVICE if dev else 0
+        with self._order(dev, x, out):
             if search:
-                x, xp = _dev(X, torch.float32)
-                if x.ndim != 2 or x.shape[1] != self.gallery_k:
-                    raise ValueError(f"Q must be (b, {self.gallery_k}), got {tuple(x.shape)}")
+                self._chk(self._lib.ef_search_matches(self._h, xp, b, mt, op, flags))
             else:
-                x, xp, dtype = self._dev_pixels(X)
-            b = x.shape[0]
-            if out is None:
-                out = torch.empty((b, 3), dtype=torch.int64, device=x.device)
-            self._dev_out(out, (b, 3), torch.int64, "out")
-            with self._torch_order(x, out):
-                if search:
-                    self._chk(self._lib.ef_search_matches(self._h, xp, b, mt, out.data_ptr(), N.EF_MEM_DEVICE))
-                else:
-                    self._chk(self._lib.ef_recognize_matches(self._h, xp, dtype, b, mt, out.data_ptr(), None,
-                                                             N.EF_MEM_DEVICE))
-            return out
-        if search:
-            x, xp = _host(X, np.float32)
-            want = self.gallery_k
-        else:
-            x = np.asarray(X)
-            dtype = N.EF_U8 if x.dtype == np.uint8 else N.EF_F32
-            x, xp = _host(x, np.uint8 if dtype == N.EF_U8 else np.float32)
-            want = self.model_d
-        # the C side reads b * want elements from the host pointer: a narrower or 1-D
-        # input would be read past its end
-        if x.ndim != 2 or x.shape[1] != want:
-            raise ValueError(f"{'Q' if search else 'P'} must be (b, {want}), got {x.shape}")
-        b = x.shape[0]
-        res = np.empty(b, dtype=N.MATCH_DTYPE)
-        if search:
-            self._chk(self._lib.ef_search_matches(self._h, xp, b, mt, res.ctypes.data, 0))
-        else:
-            self._chk(self._lib.ef_recognize_matches(self._h, xp, dtype, b, mt, res.ctypes.data, None, 0))
-        return res
+                self._chk(self._lib.ef_recognize_matches(self._h, xp, dtype, b, mt, op, None, flags))
+        return out
 
     def merge_matches(self, parts, b, keys=None):
         """Device merge (ef_matches_merge, EF_MEM_DEVICE) of gathered records: ``parts`` is
@@ -710,48 +697,17 @@ class Engine:
         pixels = kind == "recognize"
         if pixels and self.model_k is None:
             raise RuntimeError("recognize needs a model and a gallery")
-        if _is_dev(X):
-            import torch
-            if pixels:
-                x, xp, dtype = self._dev_pixels(X)
+        x, xp, dtype, b, dev = self._probes(X, pixels)
+        out, op = self._result(x, dev, out, (b, m), kind == "matches", "out" if kind == "matches" else "keys")
+        flags = N.EF_MEM_DEVICE if dev else 0
+        with self._order(dev, x, out):
+            if kind == "keys":
+                self._chk(self._lib.ef_search_topk(self._h, xp, b, m, mt, op, flags))
+            elif kind == "matches":
+                self._chk(self._lib.ef_search_topk_matches(self._h, xp, b, m, mt, op, flags))
             else:
-                x, xp = _dev(X, torch.float32)
-                if x.ndim != 2 or x.shape[1] != self.gallery_k:
-                    raise ValueError(f"Q must be (b, {self.gallery_k}), got {tuple(x.shape)}")
-            b = x.shape[0]
-            shape = (b, m, 3) if kind == "matches" else (b, m)
-            if out is None:
-                out = torch.empty(shape, dtype=torch.int64, device=x.device)
-            self._dev_out(out, shape, torch.int64, "out" if kind == "matches" else "keys")
-            with self._torch_order(x, out):
-                if kind == "keys":
-                    self._chk(self._lib.ef_search_topk(self._h, xp, b, m, mt, out.data_ptr(), N.EF_MEM_DEVICE))
-                elif kind == "matches":
-                    self._chk(self._lib.ef_search_topk_matches(self._h, xp, b, m, mt, out.data_ptr(), N.EF_MEM_DEVICE))
-                else:
-                    self._chk(self._lib.ef_recognize_topk(self._h, xp, dtype, b, m, mt, out.data_ptr(), None,
-                                                          N.EF_MEM_DEVICE))
-            return out
-        if pixels:
-            x = np.asarray(X)
-            dtype = N.EF_U8 if x.dtype == np.uint8 else N.EF_F32
-            x, xp = _host(x, np.uint8 if dtype == N.EF_U8 else np.float32)
-            want = self.model_d
-        else:
-            x, xp = _host(X, np.float32)
-            want = self.gallery_k
-        # the C side reads b * want elements from the host pointer
-        if x.ndim != 2 or x.shape[1] != want:
-            raise ValueError(f"{'P' if pixels else 'Q'} must be (b, {want}), got {x.shape}")
-        b = x.shape[0]
-        res = np.empty((b, m), dtype=N.MATCH_DTYPE if kind == "matches" else np.int64)
-        if kind == "keys":
-            self._chk(self._lib.ef_search_topk(self._h, xp, b, m, mt, res.ctypes.data, 0))
-        elif kind == "matches":
-            self._chk(self._lib.ef_search_topk_matches(self._h, xp, b, m, mt, res.ctypes.data, 0))
-        else:
-            self._chk(self._lib.ef_recognize_topk(self._h, xp, dtype, b, m, mt, res.ctypes.data, None, 0))
-        return res
+                self._chk(self._lib.ef_recognize_topk(self._h, xp, dtype, b, m, mt, op, None, flags))
+        return out
 
     def search_topk_keys(self, Q, m, metric="l2", keys=None):
         """ef_search_topk: packed keys (b, m) int64 of the m best gallery rows per probe, best
