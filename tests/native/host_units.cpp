@@ -9,14 +9,18 @@
 //   * DevBuf, PinnedBuf, Event, Stream: default-empty, move-construct and move-assign leave
 //     the source empty, an empty or moved-from handle frees nothing, a full one frees once;
 //   * std::vector<DevBuf> resize / clear on empty buffers;
-//   * SideJoin never forked, ef_tm_sums_bits at the int32 limits.
+//   * SideJoin never forked, ef_tm_sums_bits at the int32 limits;
+//   * RitzPolicy, the fit's Rayleigh-Ritz schedule and acceptance rules, on hand-made Ritz
+//     sequences.
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <utility>
 #include <vector>
 
+#include "../../face-detection-recognization-pca_amd/csrc/ef_fit_policy.hpp"
 #include "../../face-detection-recognization-pca_amd/csrc/ef_internal.hpp"
 
 static int g_frees = 0;
@@ -176,7 +180,245 @@ static void check_owner(Set set, Get get) {
   CHECK(g_frees == 3 && g_last == fake);  // the destructor of a full handle frees once
 }
 
+// ---- RitzPolicy (csrc/ef_fit_policy.hpp): the fit's Rayleigh-Ritz rules on hand-made Ritz
+// sequences, each expectation written out from the rule's own comment.  kk = 2 kept pairs in
+// a block of m = 4, Chebyshev and shift on, order 2048 (period 16, early steps) unless said.
+static RitzPolicy policy(int64_t dim = 2048, int max_iters = 100, bool cheb = true, bool shift = true,
+                         bool coarse = false) {
+  return RitzPolicy(dim, 2, 4, max_iters, cheb, shift, coarse);
+}
+// One step on the Ritz values th of C: the solver hands over those of C - sigma I
+static RitzStep step_at(RitzPolicy& p, int it, const double (&th)[4], const double* rnorm) {
+  double raw[4];
+  for (int i = 0; i < 4; ++i) raw[i] = th[i] - p.sigma;
+  return p.step(it, raw, rnorm);
+}
+
+static void check_policy_schedule() {
+  {  // 1: before any step, order 2048: the early steps 1, 2, 4 and the first scheduled one, 8
+    const RitzPolicy p = policy();
+    for (int it = 1; it <= 8; ++it) CHECK(p.rr_due(it) == (it == 1 || it == 2 || it == 4 || it == 8));
+    const RitzPolicy big = policy(16384);  // no early steps from order 12288 on
+    for (int it = 1; it <= 8; ++it) CHECK(big.rr_due(it) == (it == 8));
+    const RitzPolicy capped = policy(16384, 5);  // the last iteration always takes a step
+    CHECK(capped.rr_due(5) && !capped.rr_due(3) && capped.rr_due(8));
+    CHECK(policy(2048, 3).rr_due(3));
+  }
+  {  // 2: Jacobi tolerance: 1e-2 first coarse step, 1e-4 later coarse steps, 1e-12 when fine
+    const double th[4] = {1.0, 0.9, 0.8, 0.7}, moved[4] = {1.5, 1.2, 0.9, 0.7};
+    RitzPolicy p = policy(4096, 100, false, true, true);  // (no rate: only the 1e-4 rule ends the phase)
+    CHECK(!p.fine() && p.jacobi_tol() == 1e-2);
+    CHECK(!step_at(p, 8, th, nullptr).accepted);
+    CHECK(!p.fine() && p.jacobi_tol() == 1e-4);  // (the first step has nothing to compare with: still coarse)
+    step_at(p, 16, moved, nullptr);
+    CHECK(!p.fine() && p.jacobi_tol() == 1e-4);
+    RitzPolicy f = policy();
+    CHECK(f.fine() && f.jacobi_tol() == 1e-12);  // fine, first step or not
+    step_at(f, 1, th, nullptr);
+    CHECK(f.jacobi_tol() == 1e-12);
+  }
+  {  // 9: the medium int8 form: it >= 5, and no step reads this product (it + 1 < next_rr) or
+     // the last one (it + 1 < max_iters); next_rr is 8 before any step
+    const RitzPolicy p = policy();
+    CHECK(!p.medium(4) && p.medium(5) && p.medium(6) && !p.medium(7) && !p.medium(8));
+    const RitzPolicy capped = policy(2048, 7);
+    CHECK(capped.medium(5) && !capped.medium(6));
+    RitzPolicy late = policy();
+    late.next_rr = 32;
+    CHECK(!late.medium(4) && late.medium(5) && late.medium(30) && !late.medium(31));
+  }
+}
+
+static void check_policy_acceptance() {
+  const double th[4] = {1.0, 0.9, 0.8, 0.7};  // all gaps 0.1 theta_1
+  {  // 3: the value rule needs two consecutive fine steps.  Residuals up to 1e-8 theta_1 (the
+     // larger in pair 2): above resid_tol (1e-9), within the gap rule (1e-8 <= 1e-5 x 0.1)
+    const double r[2] = {0.5e-8, 1e-8};
+    RitzPolicy p = policy(2048, 100, true, true, true);
+    CHECK(!step_at(p, 1, th, nullptr).accepted);  // coarse step
+    p.coarse = false;                             // the products are fp64 from here on
+    CHECK(p.wants_resid());
+    CHECK(!step_at(p, 2, th, r).accepted);  // fine, but the step before was not
+    const RitzStep s = step_at(p, 4, th, r);
+    CHECK(s.accepted && s.worst == 0.0 && std::fabs(s.resid_max - 1e-8) < 1e-20);
+    // "unchanged" is 1e-13 relative: theta_2 moving by 1e-12 is not, by 5e-14 is
+    const double moved[4] = {1.0, 0.9 * (1.0 + 1e-12), 0.8, 0.7};
+    const double settled[4] = {1.0, moved[1] * (1.0 + 5e-14), 0.8, 0.7};
+    const RitzStep t = step_at(p, 8, moved, r);
+    CHECK(!t.accepted && t.worst_i == 1 && t.worst > 0.9e-12 && t.worst < 1.1e-12);
+    CHECK(step_at(p, 9, settled, r).accepted);
+  }
+  {  // 4: the residual rule accepts from one fine step when every kept pair's residual is
+     // <= 1e-9 theta_1: pair 2 at 0.9e-9 passes, at 2e-9 it does not
+    for (int pass = 0; pass <= 1; ++pass) {
+      const double r[2] = {1e-10, pass ? 0.9e-9 : 2e-9};
+      RitzPolicy p = policy(2048, 100, true, true, true);
+      CHECK(!p.wants_resid());
+      CHECK(!step_at(p, 1, th, nullptr).accepted);
+      p.coarse = false;
+      const RitzStep s = step_at(p, 2, th, r);
+      CHECK(s.accepted == (pass == 1) && std::fabs(s.resid_max - r[1]) < 1e-20);
+    }
+  }
+  {  // 5: the gap rule vetoes, and places the next step.  theta_2 - theta_3 = 1e-4 theta_1:
+     // pair 2's bound is max(1e-5 x 1e-4, 1e-12) theta_1 = 1e-9 theta_1, its residual 1e-8
+     // theta_1, need = 10.  theta_m = 0.45: sigma = 0.225, x = theta_k / sigma - 1 = 1.22, so
+     // the rule asks for ceil(acosh(2 need) / acosh(x)) = ceil(3.69 / 0.655) = 6 more products
+    const double tg[4] = {1.0, 0.5, 0.5 - 1e-4, 0.45};
+    const double r[2] = {1e-8, 1e-8};
+    const double bound = std::fmax(1e-5 * (tg[1] - tg[2]), 1e-12 * tg[0]);
+    const double x = tg[1] / (0.5 * tg[3]) - 1.0;
+    const int p1 = (int)std::ceil(std::acosh(2.0 * (r[1] / bound)) / std::acosh(x));
+    CHECK(p1 == 6);
+    for (int stalls = 0; stalls <= 1; ++stalls) {
+      RitzPolicy p = policy();
+      const RitzStep a = step_at(p, 4, tg, r);  // first step: neither the rate nor the value rule places
+      CHECK(!a.accepted && a.gap_i == 1 && a.gap_worst > 0.99e-4 && a.gap_worst < 1.01e-4);
+      CHECK(p.next_rr == 4 + p1);  // 10, past the 8 every earlier step falls back to
+      CHECK(!p.rr_due(8) && p.rr_due(10));
+      if (stalls) {  // values converged and the residuals no longer shrinking: the arithmetic's floor
+        CHECK(step_at(p, 10, tg, r).accepted);
+      } else {  // residuals still shrinking (0.4 x, need = 4): not yet.  The value and rate rules
+                // ask for the very next iteration (unchanged values), the gap rule for
+                // ceil(acosh(8) / acosh(x)) = ceil(2.77 / 0.655) = 5 more products
+        const double r2[2] = {0.4e-8, 0.4e-8};
+        const int p2 = (int)std::ceil(std::acosh(2.0 * (r2[1] / bound)) / std::acosh(x));
+        CHECK(p2 == 5);
+        CHECK(!step_at(p, 10, tg, r2).accepted);
+        CHECK(p.next_rr == 10 + p2);
+      }
+    }
+  }
+  {  // 6: an exactly degenerate kept pair (gap 0) with residual 5e-13 theta_1 <= kResidFloor
+    const double td[4] = {1.0, 1.0, 0.8, 0.7};
+    const double r[2] = {5e-13, 5e-13};
+    RitzPolicy p = policy();
+    CHECK(step_at(p, 1, td, r).accepted);
+    const double r2[2] = {5e-12, 5e-12};  // above the floor: the gap rule holds it back
+    RitzPolicy q = policy();
+    CHECK(!step_at(q, 1, td, r2).accepted);
+  }
+  {  // 10: a non-finite theta_1 reports divergence and changes no state
+    RitzPolicy p = policy(2048, 100, true, true, true);
+    step_at(p, 1, th, nullptr);
+    const RitzPolicy before = p;
+    const double bad[4] = {NAN, 0.9, 0.8, 0.7}, r[2] = {1.0, 1.0};
+    const RitzStep s = p.step(2, bad, r);
+    CHECK(s.diverged && !s.accepted);
+    CHECK(p.coarse == before.coarse && p.sigma == before.sigma && p.prev == before.prev);
+    CHECK(p.have_prev == before.have_prev && p.prev_fine == before.prev_fine && p.last_worst == before.last_worst);
+    CHECK(p.prev_resid_max == before.prev_resid_max && p.rate_prev == before.rate_prev);
+    CHECK(p.last_rr_it == before.last_rr_it && p.next_rr == before.next_rr);
+    const double inf[4] = {INFINITY, 0.9, 0.8, 0.7};
+    CHECK(p.step(2, inf, nullptr).diverged && p.last_rr_it == before.last_rr_it);
+  }
+}
+
+static void check_policy_phase_and_shift() {
+  {  // 7: the coarse phase ends when the kept values moved by < 1e-4 since the previous step
+    const double a[4] = {1.0, 0.9, 0.8, 0.7}, b[4] = {1.0 + 0.5e-4, 0.9, 0.8, 0.7};
+    RitzPolicy p = policy(4096, 100, true, true, true);
+    step_at(p, 8, a, nullptr);
+    CHECK(p.coarse);
+    const RitzStep s = step_at(p, 16, b, nullptr);
+    CHECK(s.worst > 0.4e-4 && s.worst < 0.6e-4 && s.worst_i == 0 && !p.coarse);
+    // ... not at 1e-3 when no rate predicts the error (Chebyshev off: rate_prev = 0)
+    const double c[4] = {1.0 + 1e-3, 0.9, 0.8, 0.7};
+    RitzPolicy q = policy(4096, 100, false, true, true);
+    step_at(q, 8, a, nullptr);
+    CHECK(q.rate_prev == 0.0);
+    const RitzStep t = step_at(q, 16, c, nullptr);
+    CHECK(t.worst > 0.9e-3 && t.worst < 1.1e-3 && q.coarse);
+    // with the rate (x = 0.9 / 0.35 - 1, rho^2 = 7.7 per product) the 8 products since the
+    // last step predict 1e-3 / 7.7^8 < 1e-6: the phase ends
+    RitzPolicy u = policy(4096, 100, true, true, true);
+    step_at(u, 8, a, nullptr);
+    CHECK(u.rate_prev > 0.12 && u.rate_prev < 0.14);
+    step_at(u, 16, c, nullptr);
+    CHECK(!u.coarse);
+  }
+  {  // 8: the next shift is theta_m / 2 when theta_m > 0, else 0; 0 with the shift off
+    const double a[4] = {1.0, 0.9, 0.8, 0.5}, z[4] = {1.0, 0.9, 0.8, 0.0}, n[4] = {1.0, 0.9, 0.8, -0.125};
+    RitzPolicy p = policy();
+    CHECK(step_at(p, 1, a, nullptr).sigma_next == 0.25 && p.sigma == 0.25);
+    CHECK(p.theta()[3] == 0.5 && p.theta()[0] == 1.0);  // reported unshifted
+    CHECK(step_at(p, 2, a, nullptr).sigma_next == 0.25);  // (handed over shifted by 0.25)
+    CHECK(step_at(p, 4, z, nullptr).sigma_next == 0.0);
+    CHECK(step_at(p, 8, n, nullptr).sigma_next == 0.0 && p.sigma == 0.0 && p.rate_prev == 0.0);
+    RitzPolicy off = policy(2048, 100, true, false);
+    CHECK(step_at(off, 1, a, nullptr).sigma_next == 0.0 && off.rate_prev == 0.0);
+    // Chebyshev on: rate = 1 / rho^2, rho = x + sqrt(x^2 - 1), x = theta_k / sigma - 1 = 2.6
+    RitzPolicy on = policy();
+    step_at(on, 1, a, nullptr);
+    const double rho = 2.6 + std::sqrt(2.6 * 2.6 - 1.0);
+    CHECK(std::fabs(on.rate_prev - 1.0 / (rho * rho)) < 1e-15);
+    // Chebyshev off: the rate is 0, and next_rr follows the period (16 below order 12288, 8
+    // from there; 8 before iteration 8) and the one-step-later rule only
+    RitzPolicy q = policy(2048, 100, false);
+    step_at(q, 1, a, nullptr);
+    CHECK(q.rate_prev == 0.0 && q.sigma == 0.25 && q.next_rr == 8);
+    const double a6[4] = {1.0 + 1e-6, 0.9, 0.8, 0.5}, a10[4] = {1.0 + 1e-6 + 1e-10, 0.9, 0.8, 0.5};
+    step_at(q, 8, a6, nullptr);  // worst 1e-6 after 1: predicted 1e-12 > 3e-14
+    CHECK(q.next_rr == 16);
+    step_at(q, 16, a10, nullptr);  // worst 1e-10 after 1e-6: predicted 1e-14 <= 3e-14
+    CHECK(q.rate_prev == 0.0 && q.next_rr == 17);
+    step_at(q, 17, a, nullptr);  // moving again: back to the period
+    CHECK(q.next_rr == 32);
+    RitzPolicy big = policy(16384, 100, false);
+    step_at(big, 8, a, nullptr);
+    CHECK(big.next_rr == 16);
+    step_at(big, 16, a6, nullptr);
+    CHECK(big.next_rr == 24);
+  }
+}
+
+// Where the next step goes when the Chebyshev rate is known.  theta_k = 0.9, theta_m = 0.5:
+// sigma = 0.25, x = 2.6, rho = x + sqrt(x^2 - 1) = 5, so each product shrinks the error 25 x
+static void check_policy_placement() {
+  const double a[4] = {1.0, 0.9, 0.8, 0.5};
+  const double rate = 1.0 / 25.0;
+  {  // fine steps at 1 and 4, theta_1 moved by 1e-6: the three products since step 1 leave
+     // e = 1e-6 / 25^3 = 6.4e-11, which reaches 3e-14 after ceil(log(e / 3e-14) / log 25) =
+     // ceil(7.67 / 3.22) = 3 more: the step goes to 7, before the fallback 8
+    const double a6[4] = {1.0 + 1e-6, 0.9, 0.8, 0.5};
+    RitzPolicy p = policy();
+    step_at(p, 1, a, nullptr);
+    CHECK(std::fabs(p.rate_prev - rate) < 1e-15 && p.next_rr == 8);
+    const RitzStep s = step_at(p, 4, a6, nullptr);
+    const double e = (a6[0] - a[0]) / a6[0] * std::pow(rate, 4 - 1);
+    const int want = (int)std::ceil(std::log(e / 3e-14) / std::log(1.0 / rate));
+    CHECK(want == 3 && !s.accepted && p.next_rr == 4 + want);
+  }
+  {  // the step that ends the coarse phase (values moved by 5e-5 < 1e-4): its Ritz values carry
+     // the reduced-precision products' error, so the prediction starts from 3e-7, not from
+     // 5e-5 / 25^8: ceil(log(1e7) / log 25) = ceil(16.1 / 3.22) = 6 products, 16 + 6 = 22
+    const double b[4] = {1.0 + 5e-5, 0.9, 0.8, 0.5};
+    RitzPolicy p = policy(4096, 100, true, true, true);
+    step_at(p, 8, a, nullptr);
+    CHECK(p.coarse && p.next_rr == 16);
+    step_at(p, 16, b, nullptr);
+    const int want = (int)std::ceil(std::log(3e-7 / 3e-14) / std::log(1.0 / rate));
+    CHECK(want == 6 && !p.coarse && p.next_rr == 16 + want);
+  }
+  {  // exactly unchanged values (binary fractions, so the shift adds no rounding): nothing is
+     // left to predict, log 0 = -inf, and the step count takes its floor of 1.  At 16 the
+     // value rule asks for 17 as well; at 17 the change before was 0 too, so only the rate
+     // rule places the step
+    const double e[4] = {1.0, 0.875, 0.75, 0.5};
+    RitzPolicy p = policy();
+    step_at(p, 8, e, nullptr);
+    CHECK(p.next_rr == 16);
+    CHECK(step_at(p, 16, e, nullptr).worst == 0.0 && p.next_rr == 17);
+    CHECK(step_at(p, 17, e, nullptr).worst == 0.0 && p.last_worst == 0.0 && p.next_rr == 18);
+  }
+}
+
 int main() {
+  check_policy_schedule();
+  check_policy_acceptance();
+  check_policy_phase_and_shift();
+  check_policy_placement();
+
   // (parts, bpad_max, k1, kp): parts = nchunks x bpad of the largest piece
   check_carve(256, 256, 0, 16);
   check_carve(256 * 7, 256, 16, 32);

@@ -65,6 +65,13 @@ def test_sklearn_path_golden():
     (600, 4096, 128, 256), (1500, 4096, 100, 256), (3000, 1024, 130, 256),
     # order >= 2048: the 256 x 384 SYRK tiles, ragged against both tile sizes (Gram, covariance)
     (2100, 4096, 20, 32), (2500, 2116, 20, 32),
+    # covariance path, order 4096 with block 88: the smallest order with a coarse phase, which
+    # runs in the fp32 form (the split-bf16 form needs block 256); fine products fp64 dense
+    # (the int8 digit form needs block 256 too)
+    (4200, 4096, 20, 32),
+    # covariance path, odd order 47^2 (d % 4 != 0): no 16-byte rows of C, so Y = C.Q takes the
+    # generic GEMM plus the shift kernel
+    (2300, 2209, 20, 32),
     # covariance path with n > 65536: the int8 product's int32 -> int64 flush
     (70000, 256, 12, 64),
     # covariance path with d % 4 != 0: byte-granular transpose + separate column stats
@@ -422,7 +429,7 @@ def test_fit_c3_full_size_properties():
     * components orthonormal (|V^T V - I| <= 1e-10);
     * Rayleigh quotients v^T C v equal the returned eigenvalues (rtol 1e-9);
     * residuals |C v - lambda v| <= 1e-9 lambda_1 for every component (the engine's own
-      criterion, ef_fit.hip fit_resid_tol; round 5 asserted only 1e-6);
+      criterion, ef_fit_policy.hpp FitKnobs::resid_tol; round 5 asserted only 1e-6);
     * per component |r_i| / gap_i <= 1e-4, gap_i to the nearest other eigenvalue: the
       eigenvector error bound (Davis-Kahan).  The fit is run at k = 136 as well, so the gap
       of component 128 to lambda_129 is known; both fits are checked;

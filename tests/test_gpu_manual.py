@@ -223,8 +223,8 @@ def test_fit_exact_dark_spectrum(eng):
     eigenvalues (tests/golden/dark_evr.npz reproduces models/Joseph_Lai_dark_model_info.json:
     EVR 0.690 / 0.103 / 0.043).  Its smallest gap is 2.37e-6 lambda_1 (components 35/36):
     a residual-only stop rule (|r| <= 1e-9 lambda_1) would bound those eigenfaces only to
-    |r| / gap = 4.2e-4.  The round-6 gap-aware rule (|r_i| <= 1e-5 gap_i, ef_fit.hip
-    fit_gap_tol) holds them to 1e-5; here every eigenface equals the constructed one to 1e-6
+    |r| / gap = 4.2e-4.  The round-6 gap-aware rule (|r_i| <= 1e-5 gap_i,
+    ef_fit_policy.hpp FitKnobs::gap_tol) holds them to 1e-5; here every eigenface equals the constructed one to 1e-6
     per pixel and the eigenvalues the reference's to 1e-9."""
     from eigenface import manual_pca
     st, X, U, V, lam_ref = _exact_spectrum_case("dark_evr.npz", 2031)
