@@ -375,6 +375,82 @@ static BankWs carve_bank_ws(Carve& cv, size_t entries, size_t scales) {
   return BankWs{cv.take<double>(entries), cv.take<double>(entries), cv.take<int>(entries), cv.take<double>(scales)};
 }
 
+// The launches of one recognise call on device pointers (ef_internal.hpp): ef_bank_recognize
+// after its staging, and ef_scan_frame on the rows its ROI kernel wrote.
+int bank_recognize_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, int metric, long long* kdev, ef_match* mdev,
+                       int* sdev, float* fdev) {
+  Bank& bk = c->bank;
+  EF_TRY(bank_tables(c));
+  const int64_t M = (int64_t)bk.slots.size();
+  const int64_t bpad = round_up(b, BM);
+  const int64_t coltiles = bk.total_kpw / 128;
+  int ns = 0;
+  int64_t pps = 0, nwg = 0;
+  bank_split(b, bk.d, coltiles, &ns, &pps, &nwg);
+  EF_TRY(ensure(c, bk.part, (size_t)ns * bpad * bk.total_kpw * sizeof(float)));
+  EF_TRY(ensure(c, bk.q, (size_t)bpad * bk.total_kp * sizeof(float)));
+  const BankProjItem* items = static_cast<const BankProjItem*>(bk.proj_items.p);
+  const BankSlotDev* tab = static_cast<const BankSlotDev*>(bk.slot_tab.p);
+  float* part = static_cast<float*>(bk.part.p);
+  float* q = static_cast<float*>(bk.q.p);
+  TimerEvt t;
+  timer_begin(c, EF_KERNEL_PROJECT, &t);
+  EF_HIP(c,
+         p_dtype == EF_U8 ? bank_project_t<EF_U8>(c->stream, items, coltiles, Pd, b, bpad, bk.d, part, bk.total_kpw, ns, pps)
+                          : bank_project_t<EF_F32>(c->stream, items, coltiles, Pd, b, bpad, bk.d, part, bk.total_kpw, ns, pps),
+         "bank projection");
+  timer_end(c, &t);
+  {
+    const int64_t tot = bpad * bk.kp_max;
+    hipLaunchKernelGGL(bank_reduce_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)M), dim3(256), 0, c->stream, tab,
+                       part, ns, b, bpad, bk.total_kpw, bk.total_k, q, fdev);
+    EF_HIP(c, hipGetLastError(), "bank reduce");
+  }
+
+  // search: at least one entry per slot, so an empty slot's entry reads "no row"
+  // the probe tile of this call: the largest of 128 .. 8 that gives the launch kBankSearchWgs items
+  // (small banks and batches get small tiles: the fp64 chains need the waves, and the gallery
+  // rows a smaller tile re-reads come from L2)
+  int64_t items_max = 1;
+  int pt_cap = kBankPtMax;
+  for (;; pt_cap /= 2) {
+    int64_t items = 0;
+    items_max = 1;
+    for (const BankSlot& slot : bk.slots) {
+      const Gallery& s = slot.g;
+      int lds = 0;
+      const int pt = std::min(bank_search_pt(s.kp, &lds), pt_cap);
+      const int64_t rows = bank_slice_rows(s.n, M);
+      const int64_t it = (b + pt - 1) / pt * ((s.n + rows - 1) / rows);
+      items += it;
+      items_max = std::max(items_max, it);
+    }
+    if (items >= kBankSearchWgs || pt_cap <= 8) break;
+  }
+  const size_t entries = (size_t)std::max<int64_t>(bk.total_slices, 1) * (size_t)b;
+  Carve size_ws, cvw;
+  carve_bank_ws(size_ws, entries, (size_t)(M * b));
+  EF_TRY(ensure(c, bk.ws, size_ws.total));
+  cvw.base = bk.ws.p;
+  const BankWs ws = carve_bank_ws(cvw, entries, (size_t)(M * b));
+  timer_begin(c, EF_KERNEL_SEARCH, &t);
+  if (bk.total_slices > 0)
+    EF_HIP(c,
+           metric == EF_METRIC_L2
+               ? bank_search_t<EF_METRIC_L2>(c->stream, tab, (int)M, items_max, bk.search_lds, q, b, bpad, pt_cap, ws)
+               : bank_search_t<EF_METRIC_COSINE>(c->stream, tab, (int)M, items_max, bk.search_lds, q, b, bpad, pt_cap,
+                                                 ws),
+           "bank search");
+  hipLaunchKernelGGL(bank_merge_kernel, dim3((unsigned)((b * M + 255) / 256)), dim3(256), 0, c->stream, tab, (int)M, b, ws,
+                     kdev, mdev);
+  if (sdev)
+    hipLaunchKernelGGL(bank_best_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, kdev, (int)M, b,
+                       metric, sdev);
+  EF_HIP(c, hipGetLastError(), "bank merge");
+  timer_end(c, &t);
+  return EF_OK;
+}
+
 }  // namespace ef
 
 using namespace ef;
@@ -469,8 +545,6 @@ int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int3
   EF_TRY(bank_tables(c));
   const bool dev = flags & EF_MEM_DEVICE;
   const int64_t M = (int64_t)bk.slots.size();
-  const int64_t bpad = round_up(b, BM);
-  const int64_t coltiles = bk.total_kpw / 128;
 
   const void* Pd = nullptr;
   EF_TRY(stage_probes(c, P, p_dtype, b, bk.d, flags, bk.p_stage, &Pd));
@@ -484,74 +558,7 @@ int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int3
     EF_TRY(ensure(c, bk.out, (size_t)b * sizeof(int)));
     sdev = static_cast<int*>(bk.out.p);
   }
-  long long* kdev = r.kdev;
-  ef_match* mdev = r.mdev;
-  float* fdev = r.fdev;
-
-  int ns = 0;
-  int64_t pps = 0, nwg = 0;
-  bank_split(b, bk.d, coltiles, &ns, &pps, &nwg);
-  EF_TRY(ensure(c, bk.part, (size_t)ns * bpad * bk.total_kpw * sizeof(float)));
-  EF_TRY(ensure(c, bk.q, (size_t)bpad * bk.total_kp * sizeof(float)));
-  const BankProjItem* items = static_cast<const BankProjItem*>(bk.proj_items.p);
-  const BankSlotDev* tab = static_cast<const BankSlotDev*>(bk.slot_tab.p);
-  float* part = static_cast<float*>(bk.part.p);
-  float* q = static_cast<float*>(bk.q.p);
-  TimerEvt t;
-  timer_begin(c, EF_KERNEL_PROJECT, &t);
-  EF_HIP(c,
-         p_dtype == EF_U8 ? bank_project_t<EF_U8>(c->stream, items, coltiles, Pd, b, bpad, bk.d, part, bk.total_kpw, ns, pps)
-                          : bank_project_t<EF_F32>(c->stream, items, coltiles, Pd, b, bpad, bk.d, part, bk.total_kpw, ns, pps),
-         "bank projection");
-  timer_end(c, &t);
-  {
-    const int64_t tot = bpad * bk.kp_max;
-    hipLaunchKernelGGL(bank_reduce_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)M), dim3(256), 0, c->stream, tab,
-                       part, ns, b, bpad, bk.total_kpw, bk.total_k, q, fdev);
-    EF_HIP(c, hipGetLastError(), "bank reduce");
-  }
-
-  // search: at least one entry per slot, so an empty slot's entry reads "no row"
-  // the probe tile of this call: the largest of 128 .. 8 that gives the launch kBankSearchWgs items
-  // (small banks and batches get small tiles: the fp64 chains need the waves, and the gallery
-  // rows a smaller tile re-reads come from L2)
-  int64_t items_max = 1;
-  int pt_cap = kBankPtMax;
-  for (;; pt_cap /= 2) {
-    int64_t items = 0;
-    items_max = 1;
-    for (const BankSlot& slot : bk.slots) {
-      const Gallery& s = slot.g;
-      int lds = 0;
-      const int pt = std::min(bank_search_pt(s.kp, &lds), pt_cap);
-      const int64_t rows = bank_slice_rows(s.n, M);
-      const int64_t it = (b + pt - 1) / pt * ((s.n + rows - 1) / rows);
-      items += it;
-      items_max = std::max(items_max, it);
-    }
-    if (items >= kBankSearchWgs || pt_cap <= 8) break;
-  }
-  const size_t entries = (size_t)std::max<int64_t>(bk.total_slices, 1) * (size_t)b;
-  Carve size_ws, cvw;
-  carve_bank_ws(size_ws, entries, (size_t)(M * b));
-  EF_TRY(ensure(c, bk.ws, size_ws.total));
-  cvw.base = bk.ws.p;
-  const BankWs ws = carve_bank_ws(cvw, entries, (size_t)(M * b));
-  timer_begin(c, EF_KERNEL_SEARCH, &t);
-  if (bk.total_slices > 0)
-    EF_HIP(c,
-           metric == EF_METRIC_L2
-               ? bank_search_t<EF_METRIC_L2>(c->stream, tab, (int)M, items_max, bk.search_lds, q, b, bpad, pt_cap, ws)
-               : bank_search_t<EF_METRIC_COSINE>(c->stream, tab, (int)M, items_max, bk.search_lds, q, b, bpad, pt_cap,
-                                                 ws),
-           "bank search");
-  hipLaunchKernelGGL(bank_merge_kernel, dim3((unsigned)((b * M + 255) / 256)), dim3(256), 0, c->stream, tab, (int)M, b, ws,
-                     kdev, mdev);
-  if (sdev)
-    hipLaunchKernelGGL(bank_best_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, kdev, (int)M, b,
-                       metric, sdev);
-  EF_HIP(c, hipGetLastError(), "bank merge");
-  timer_end(c, &t);
+  EF_TRY(bank_recognize_dev(c, Pd, p_dtype, b, metric, r.kdev, r.mdev, sdev, r.fdev));
   if (!dev && best_slot)
     EF_HIP(c, hipMemcpyAsync(best_slot, sdev, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H best slot");
   return r.fetch(c);

@@ -32,8 +32,18 @@
 //   summed in int64 by `tm_score_kernel`, which applies OpenCV's TM_CCOEFF_NORMED
 //   normalisation rule in float64 and reduces the first raster-order maximum with one
 //   packed-key atomicMin per wave.
+//
+// Frame scan — scan-template-v4.py:340-391, one frame of process_live_camera:
+//     gray = cvtColor(frame, BGR2GRAY); template_match_all_models(gray); per detection
+//     recognize_face_all_models(frame[y:y+h, x:x+w])
+//   `ef_scan_frame` queues the grey plane (`frame_gray_kernel`), the localiser's kernels
+//   (`tm_queue`, shared with ef_tm_match), the per-person choice with the corner rule
+//   (`scan_select_kernel`), the crops' grey + resize read in place from the grey plane
+//   (`roi_resize_kernel`, also ef_preprocess_rois) and the model bank's recognise
+//   (ef_bank.hip `bank_recognize_dev`) on one stream: one upload, one download, one wait.
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -59,12 +69,16 @@ struct ImgDesc {
   int h, w, c, oh, ow, pad;
 };
 
+// grey of the c-channel pixel at p
 template <bool RGB>
-__device__ __forceinline__ int gray_at(const uint8_t* __restrict__ src, int w, int c, int y, int x) {
-  const uint8_t* p = src + ((int64_t)y * w + x) * c;
+__device__ __forceinline__ int gray_px(const uint8_t* __restrict__ p, int c) {
   if (c == 1) return p[0];
   const int b = RGB ? p[2] : p[0], g = p[1], r = RGB ? p[0] : p[2];
   return (b * 1868 + g * 9617 + r * 4899 + 8192) >> 14;
+}
+template <bool RGB>
+__device__ __forceinline__ int gray_at(const uint8_t* __restrict__ src, int w, int c, int y, int x) {
+  return gray_px<RGB>(src + ((int64_t)y * w + x) * c, c);
 }
 
 // grid (ceil(max_out_pixels / 256), count); thread = one output pixel.
@@ -90,6 +104,73 @@ static hipError_t launch_resize(hipStream_t s, const uint8_t* src, const ImgDesc
   else
     hipLaunchKernelGGL(resize_kernel<false>, grid, dim3(256), 0, s, src, desc_dev, dst);
   return hipGetLastError();
+}
+
+// ROI ingest (ef_preprocess_rois): resize_kernel for rectangles of one strided frame.
+// grid (ceil(oh * ow / 256), n); thread = one output pixel of rectangle blockIdx.y, whose
+// {x, y, w, h} are the four ints at rects + blockIdx.y * rect_stride (4 for a rectangle list,
+// 8 for the x field of an ef_scan_det array).  The rectangle is clipped to the frame before
+// any load (a no-op for the host path's validated rectangles); one that is empty after
+// clipping or starts at a negative coordinate gives a zero row.  The source pixel (yy, xx)
+// of the rectangle is frame[(y + yy) * ld + (x + xx) * c], with 0 <= yy < h <= fh - y and
+// 0 <= xx < w <= fw - x: inside fh rows of ld >= fw * c bytes whatever the rectangle holds.
+template <bool RGB>
+__global__ __launch_bounds__(256) void roi_resize_kernel(const uint8_t* __restrict__ frame, int64_t ld, int fh, int fw,
+                                                         int c, const int* __restrict__ rects, int rect_stride, int oh,
+                                                         int ow, uint8_t* __restrict__ dst) {
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= oh * ow) return;
+  const int* rc = rects + (int64_t)blockIdx.y * rect_stride;
+  const int x = rc[0], y = rc[1];
+  int w = rc[2], h = rc[3];
+  uint8_t* out = dst + (int64_t)blockIdx.y * oh * ow + o;
+  if (x < 0 || y < 0 || x >= fw || y >= fh || w <= 0 || h <= 0) {
+    *out = 0;
+    return;
+  }
+  w = w < fw - x ? w : fw - x;
+  h = h < fh - y ? h : fh - y;
+  const int dy = o / ow, dx = o - (o / ow) * ow;
+  const uint8_t* s = frame + (int64_t)y * ld + (int64_t)x * c;
+  const auto gray = [&](int yy, int xx) { return gray_px<RGB>(s + (int64_t)yy * ld + (int64_t)xx * c, c); };
+  *out = (uint8_t)resize_px(gray, h, w, oh, ow, dy, dx);
+}
+
+static hipError_t launch_roi_resize(hipStream_t s, const uint8_t* frame, int64_t ld, int fh, int fw, int c,
+                                    const int* rects, int rect_stride, int64_t n, int oh, int ow, bool rgb,
+                                    uint8_t* dst) {
+  if (n == 0) return hipSuccess;
+  const dim3 grid((unsigned)(((int64_t)oh * ow + 255) / 256), (unsigned)n);
+  if (rgb)
+    hipLaunchKernelGGL(roi_resize_kernel<true>, grid, dim3(256), 0, s, frame, ld, fh, fw, c, rects, rect_stride, oh, ow,
+                       dst);
+  else
+    hipLaunchKernelGGL(roi_resize_kernel<false>, grid, dim3(256), 0, s, frame, ld, fh, fw, c, rects, rect_stride, oh, ow,
+                       dst);
+  return hipGetLastError();
+}
+
+// Grey plane of a 3- or 4-channel frame (ef_scan_frame): dst is H rows of W bytes with no
+// padding, taken as one flat array of H * W pixels; a thread produces flat pixels 4 t .. 4 t + 3
+// (they may straddle a row end) and stores them as one dword.  dst is 4-byte aligned and
+// holds round_up(H * W, 4) bytes: the last dword's bytes past H * W are written as zero.
+template <bool RGB>
+__global__ __launch_bounds__(256) void frame_gray_kernel(const uint8_t* __restrict__ src, int64_t ld, int H, int W,
+                                                         int c, uint32_t* __restrict__ dst) {
+  const int64_t total = (int64_t)H * W;
+  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i0 >= total) return;
+  int y = (int)(i0 / W), x = (int)(i0 - (int64_t)y * W);
+  uint32_t v = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (i0 + j < total) v |= (uint32_t)gray_px<RGB>(src + (int64_t)y * ld + (int64_t)x * c, c) << (8 * j);
+    if (++x == W) {
+      x = 0;
+      ++y;
+    }
+  }
+  dst[i0 >> 2] = v;
 }
 
 // Interface used by the Haar pyramid (ef_haar.hip): grey single-channel ragged resize.
@@ -794,14 +875,92 @@ __global__ __launch_bounds__(256) void tm_score_kernel(const TmProblem* __restri
   }
 }
 
+// ------------------------------------------------------------------- frame scan
+// The four integers of is_detection_in_corner (scan-template-v4.py:75-125) for the frame.
+struct ScanCorner {
+  int W, H, corner_w, corner_h, border_w, border_h;
+};
+
+// template_match_all_models' choice per group (scan-template-v4.py:153-193), one block per
+// group over the packed keys tm_score_kernel left.  The reference walks the group's problems
+// in order and takes a candidate with v > best (best from 0.0) unless it sits in a corner or
+// border, which leaves the state alone: so the result is the first non-corner problem that
+// attains the maximum v > 0 over the group's non-corner problems — a max over
+// (v, descending problem index) here (v > 0: its float bits order as unsigned).
+__global__ __launch_bounds__(256) void scan_select_kernel(const unsigned long long* __restrict__ keys,
+                                                          const TmProblem* __restrict__ probs,
+                                                          const int* __restrict__ prob_group, int nprob,
+                                                          ScanCorner cr, double threshold,
+                                                          ef_scan_det* __restrict__ dets) {
+  const int g = blockIdx.x;
+  unsigned long long best = 0;
+  for (int p = threadIdx.x; p < nprob; p += 256) {
+    if (prob_group[p] != g) continue;
+    const unsigned long long key = keys[p];
+    const unsigned o = ~(unsigned)(key >> 32);
+    const unsigned bits = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+    const float v = __uint_as_float(bits);
+    if (!(v > 0.f)) continue;
+    const TmProblem pb = probs[p];
+    const unsigned idx = (unsigned)(key & 0xffffffffu);
+    const int x = (int)(idx % (unsigned)pb.wr), y = (int)(idx / (unsigned)pb.wr), w = pb.tw, h = pb.th;
+    const int cx = x + w / 2, cy = y + h / 2;
+    const bool border = x < cr.border_w || y < cr.border_h || x + w > cr.W - cr.border_w || y + h > cr.H - cr.border_h;
+    const bool left = cx < cr.corner_w, right = cx > cr.W - cr.corner_w;
+    const bool top = cy < cr.corner_h, bottom = cy > cr.H - cr.corner_h;
+    if (border || ((left || right) && (top || bottom))) continue;
+    const unsigned long long k = ((unsigned long long)bits << 32) | (0xffffffffu - (unsigned)p);
+    best = k > best ? k : best;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(best, off);
+    best = o > best ? o : best;
+  }
+  __shared__ unsigned long long red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
+  ef_scan_det d{};
+  const float v = __uint_as_float((unsigned)(best >> 32));
+  if (best != 0 && (double)v > threshold) {
+    const int p = (int)(0xffffffffu - (unsigned)(best & 0xffffffffu));
+    const TmProblem pb = probs[p];
+    const unsigned idx = (unsigned)(keys[p] & 0xffffffffu);
+    d.found = 1;
+    d.problem = p;
+    d.x = (int)(idx % (unsigned)pb.wr);
+    d.y = (int)(idx / (unsigned)pb.wr);
+    d.w = pb.tw;
+    d.h = pb.th;
+    d.confidence = v;
+  }
+  dets[g] = d;
+}
 
 // ------------------------------------------------------------------ ctx state
+// ef_scan_prepare's plan.  The result block of one frame is one device allocation
+// [dets | keys | best slots | rows] (each piece 256-byte aligned) with a pinned mirror, so a
+// host call downloads it with one copy.
+struct ScanPlan {
+  int n_groups = 0, face_h = 0, face_w = 0;
+  double threshold = 0.0;
+  ScanCorner corner{};
+  DevBuf prob_group;  // int[nprob]
+  DevBuf frame_in;    // a host call's frame, H rows of W * channels bytes
+  DevBuf gray;        // the grey plane of a colour frame, round_up(H * W, 4) bytes
+  DevBuf out;         // the result block
+  PinnedBuf host;     // its pinned mirror
+};
+
 struct TmState {
   int H = 0, W = 0, nprob = 0, nwork = 0, max_nkb = 0;
   bool ii64 = false;  // int64 integral images (some template area >= 2^18, or EF_TM_II64)
   int64_t pitch = 0, max_pos = 0, map_total = 0;
   std::vector<TmProblem> probs;
   DevBuf raw, scaled, bands, d_probs, d_pieces, d_works, d_stat, parts, f8, ii1, ii2, keys, frame_stage, maps;
+  std::unique_ptr<ScanPlan> scan;  // null until ef_scan_prepare
 };
 
 void tm_release(ef_ctx* c) {
@@ -839,6 +998,61 @@ static int tm_tile_groups(int nrb, int nkb, int maxnkb) {
     if (ring >= 32 * (4 / g) + 6 && 4 * ring > 128 + 32 * (4 / g) + 6 && rw <= 1024) return g;
   }
   return 1;
+}
+
+// The queue-only part of one frame of the localiser, shared by ef_tm_match and ef_scan_frame:
+// integral images, correlation and score on c->stream (and the side stream), no copy and no
+// host wait.  f: the grey frame on the device, rows frame_ld bytes apart; maps: the device
+// maps to fill, or null.  Leaves the per-problem packed keys in t->keys.  tev (optional): the
+// caller's running timer, ended behind the last kernel.
+static int tm_queue(ef_ctx* c, TmState* t, const uint8_t* f, int64_t frame_ld, float* maps, TimerEvt* tev) {
+  hipStream_t s = c->stream;
+  const int W = t->W;
+  int8_t* f8 = static_cast<int8_t*>(t->f8.p);
+  unsigned long long* keys = static_cast<unsigned long long*>(t->keys.p);
+  // The integral images' column pass runs on a side stream beside the correlation kernel
+  // (it needs only the row pass; the score kernel joins both): its 8 KiB blocks fit next to
+  // a correlation workgroup's 147 KiB of LDS.  The guard joins it on every other exit too,
+  // so the next call's row pass cannot write ii1 / ii2 under it.
+  bool side = t->nprob > 0 && t->nwork > 0;
+#ifdef EF_DIAGNOSTICS
+  if (std::getenv("EF_TM_NOSIDE")) side = false;  // A/B: column pass in line
+#endif
+  SideJoin col_join(c->tm_side, s);
+  EF_TRY(t->ii64 ? tm_integrals<long long>(c, t, col_join, side, f, frame_ld)
+                 : tm_integrals<unsigned>(c, t, col_join, side, f, frame_ld));
+  if (t->nprob == 0) {
+    if (tev) timer_end(c, tev);
+    return EF_OK;
+  }
+  if (t->nwork > 0) {
+    bool narrow = t->max_nkb <= 5;
+#ifdef EF_DIAGNOSTICS
+    if (std::getenv("EF_TM_WIDE")) narrow = false;  // A/B: one workgroup per CU
+#endif
+    auto corr = narrow ? tm_corr_kernel<5> : tm_corr_kernel<12>;
+    hipLaunchKernelGGL(corr, dim3((unsigned)t->nwork), dim3(512), 0, s, f8, t->pitch,
+                       static_cast<const uint8_t*>(t->bands.p), static_cast<const TmPiece*>(t->d_pieces.p),
+                       static_cast<const TmWork*>(t->d_works.p), static_cast<const TmProblem*>(t->d_probs.p),
+                       static_cast<int*>(t->parts.p), t->nwork);
+  }
+  EF_HIP(c, col_join.join(), "score waits cols");
+  const int64_t sblk = 64;  // row-strided blocks per problem
+  const dim3 sgrid((unsigned)sblk, (unsigned)t->nprob);
+  const TmProblem* dp = static_cast<const TmProblem*>(t->d_probs.p);
+  const TmStat* dst = static_cast<const TmStat*>(t->d_stat.p);
+  const int* dparts = static_cast<const int*>(t->parts.p);
+  if (t->ii64)
+    hipLaunchKernelGGL(tm_score_kernel<long long>, sgrid, dim3(256), 0, s, dp, dst, dparts,
+                       static_cast<const long long*>(t->ii1.p), static_cast<const long long*>(t->ii2.p), W, maps,
+                       keys);
+  else
+    hipLaunchKernelGGL(tm_score_kernel<unsigned>, sgrid, dim3(256), 0, s, dp, dst, dparts,
+                       static_cast<const unsigned*>(t->ii1.p), static_cast<const unsigned*>(t->ii2.p), W, maps,
+                       keys);
+  if (tev) timer_end(c, tev);
+  EF_HIP(c, hipGetLastError(), "template match kernels");
+  return EF_OK;
 }
 
 }  // namespace ef
@@ -1073,58 +1287,20 @@ int ef_tm_match(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, float* best_o
     f = static_cast<const uint8_t*>(t->frame_stage.p);
     frame_ld = W;
   }
-  int8_t* f8 = static_cast<int8_t*>(t->f8.p);
-  unsigned long long* keys = static_cast<unsigned long long*>(t->keys.p);
+  float* maps = nullptr;
+  if (maps_out && t->nprob > 0) {
+    if (dev) {
+      maps = maps_out;
+    } else {
+      EF_TRY(ensure(c, t->maps, (size_t)t->map_total * 4));
+      maps = static_cast<float*>(t->maps.p);
+    }
+  }
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_TMATCH, &tev);
-  // The integral images' column pass runs on a side stream beside the correlation kernel
-  // (it needs only the row pass; the score kernel joins both): its 8 KiB blocks fit next to
-  // a correlation workgroup's 147 KiB of LDS.  The guard joins it on every other exit too,
-  // so the next call's row pass cannot write ii1 / ii2 under it.
-  bool side = t->nprob > 0 && t->nwork > 0;
-#ifdef EF_DIAGNOSTICS
-  if (std::getenv("EF_TM_NOSIDE")) side = false;  // A/B: column pass in line
-#endif
-  SideJoin col_join(c->tm_side, s);
-  EF_TRY(t->ii64 ? tm_integrals<long long>(c, t, col_join, side, f, frame_ld)
-                 : tm_integrals<unsigned>(c, t, col_join, side, f, frame_ld));
+  EF_TRY(tm_queue(c, t, f, frame_ld, maps, &tev));
   if (t->nprob > 0) {
-    if (t->nwork > 0) {
-      bool narrow = t->max_nkb <= 5;
-#ifdef EF_DIAGNOSTICS
-      if (std::getenv("EF_TM_WIDE")) narrow = false;  // A/B: one workgroup per CU
-#endif
-      auto corr = narrow ? tm_corr_kernel<5> : tm_corr_kernel<12>;
-      hipLaunchKernelGGL(corr, dim3((unsigned)t->nwork), dim3(512), 0, s, f8, t->pitch,
-                         static_cast<const uint8_t*>(t->bands.p), static_cast<const TmPiece*>(t->d_pieces.p),
-                         static_cast<const TmWork*>(t->d_works.p), static_cast<const TmProblem*>(t->d_probs.p),
-                         static_cast<int*>(t->parts.p), t->nwork);
-    }
-    float* maps = nullptr;
-    if (maps_out) {
-      if (dev) {
-        maps = maps_out;
-      } else {
-        EF_TRY(ensure(c, t->maps, (size_t)t->map_total * 4));
-        maps = static_cast<float*>(t->maps.p);
-      }
-    }
-    EF_HIP(c, col_join.join(), "score waits cols");
-    const int64_t sblk = 64;  // row-strided blocks per problem
-    const dim3 sgrid((unsigned)sblk, (unsigned)t->nprob);
-    const TmProblem* dp = static_cast<const TmProblem*>(t->d_probs.p);
-    const TmStat* dst = static_cast<const TmStat*>(t->d_stat.p);
-    const int* dparts = static_cast<const int*>(t->parts.p);
-    if (t->ii64)
-      hipLaunchKernelGGL(tm_score_kernel<long long>, sgrid, dim3(256), 0, s, dp, dst, dparts,
-                         static_cast<const long long*>(t->ii1.p), static_cast<const long long*>(t->ii2.p), W, maps,
-                         keys);
-    else
-      hipLaunchKernelGGL(tm_score_kernel<unsigned>, sgrid, dim3(256), 0, s, dp, dst, dparts,
-                         static_cast<const unsigned*>(t->ii1.p), static_cast<const unsigned*>(t->ii2.p), W, maps,
-                         keys);
-    timer_end(c, &tev);
-    EF_HIP(c, hipGetLastError(), "template match kernels");
+    const unsigned long long* keys = static_cast<const unsigned long long*>(t->keys.p);
     std::vector<unsigned long long> hk((size_t)t->nprob);
     EF_HIP(c, hipMemcpyAsync(hk.data(), keys, hk.size() * 8, hipMemcpyDeviceToHost, s), "D2H keys");
     if (maps_out && !dev)
@@ -1141,7 +1317,6 @@ int ef_tm_match(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, float* best_o
       if (y_out) y_out[p] = (int32_t)(idx / (unsigned)t->probs[p].wr);
     }
   } else {
-    timer_end(c, &tev);
     EF_HIP(c, hipStreamSynchronize(s), "sync");
   }
   return EF_OK;
@@ -1157,6 +1332,197 @@ int ef_tm_info(ef_ctx* c, int32_t* n_problems, int64_t* map_elems, int32_t* resu
     if (result_h) result_h[p] = t->probs[p].hr;
     if (result_w) result_w[p] = t->probs[p].wr;
   }
+  return EF_OK;
+}
+
+int ef_preprocess_rois(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t frame_h, int32_t frame_w,
+                       int32_t channels, const int32_t* rects, int64_t n, int32_t out_h, int32_t out_w, uint8_t* out,
+                       uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (n < 0 || out_h <= 0 || out_w <= 0 || frame_h <= 0 || frame_w <= 0 ||
+      (channels != 1 && channels != 3 && channels != 4) || frame_ld < (int64_t)frame_w * channels ||
+      (n > 0 && (!frame || !rects || !out)))
+    return set_err(c, EF_E_INVALID, "ef_preprocess_rois: bad arguments");
+  if (n == 0) return EF_OK;
+  if (n > 65535) return set_err(c, EF_E_INVALID, "ef_preprocess_rois: at most 65535 rectangles per call");
+  const bool dev = flags & EF_MEM_DEVICE, rdev = flags & EF_ROI_RECTS_DEVICE;
+  if (!rdev)
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t* r = rects + 4 * i;
+      if (r[0] < 0 || r[1] < 0 || r[2] <= 0 || r[3] <= 0 || (int64_t)r[0] + r[2] > frame_w ||
+          (int64_t)r[1] + r[3] > frame_h)
+        return set_err(c, EF_E_INVALID, "ef_preprocess_rois: rectangle " + std::to_string(i) + " is not inside the frame");
+    }
+  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+  hipStream_t s = c->stream;
+  // host rectangles, host pixels (rows packed to frame_w * channels bytes) and the host
+  // call's output staged in one scratch buffer
+  const int64_t row_bytes = (int64_t)frame_w * channels;
+  const size_t rbytes = rdev ? 0 : round_up(n * 16, 256);
+  const size_t fbytes = dev ? 0 : round_up((int64_t)frame_h * row_bytes, 256);
+  const size_t obytes = (size_t)n * out_h * out_w;
+  const size_t need = rbytes + fbytes + (dev ? 0 : round_up((int64_t)obytes, 256));
+  char* base = nullptr;
+  if (need > 0) {
+    EF_TRY(ensure(c, c->p_stage, need));
+    base = static_cast<char*>(c->p_stage.p);
+  }
+  const int* drects = rects;
+  if (!rdev) {
+    EF_HIP(c, hipMemcpyAsync(base, rects, (size_t)n * 16, hipMemcpyHostToDevice, s), "H2D rectangles");
+    drects = reinterpret_cast<const int*>(base);
+  }
+  const uint8_t* src = frame;
+  uint8_t* dst = out;
+  int64_t ld = frame_ld;
+  if (!dev) {
+    uint8_t* fs = reinterpret_cast<uint8_t*>(base + rbytes);
+    EF_HIP(c, hipMemcpy2DAsync(fs, row_bytes, frame, frame_ld, row_bytes, frame_h, hipMemcpyHostToDevice, s),
+           "H2D frame");
+    src = fs;
+    ld = row_bytes;
+    dst = reinterpret_cast<uint8_t*>(base + rbytes + fbytes);
+  }
+  TimerEvt tev;
+  timer_begin(c, EF_KERNEL_INGEST, &tev);
+  EF_HIP(c, launch_roi_resize(s, src, ld, frame_h, frame_w, channels, drects, 4, n, out_h, out_w, flags & EF_IMG_RGB, dst),
+         "ROI resize kernel");
+  timer_end(c, &tev);
+  if (!dev) EF_HIP(c, hipMemcpyAsync(out, dst, obytes, hipMemcpyDeviceToHost, s), "D2H faces");
+  // staged rectangles and pixels live in scratch that the next call may overwrite: wait.  Only
+  // the all-device form (pixels, rows and rectangles) stays stream-ordered.
+  if (!dev || !rdev) EF_HIP(c, hipStreamSynchronize(s), "sync");
+  return EF_OK;
+}
+
+// The pieces of a scan's result block for g groups, M bank slots and d face pixels.
+struct ScanOut {
+  ef_scan_det* dets;
+  long long* keys;
+  int* best;
+  uint8_t* rows;
+};
+static ScanOut carve_scan_out(Carve& cv, size_t g, size_t M, size_t d) {
+  return ScanOut{cv.take<ef_scan_det>(g), cv.take<long long>(g * M), cv.take<int>(g), cv.take<uint8_t>(g * d)};
+}
+
+int ef_scan_prepare(ef_ctx* c, const int32_t* prob_group, int32_t n_groups, int32_t face_h, int32_t face_w,
+                    double threshold) {
+  if (!c) return EF_E_INVALID;
+  TmState* t = c->tm;
+  if (!t) return set_err(c, EF_E_STATE, "ef_scan_prepare: call ef_tm_prepare first");
+  if (n_groups < 1 || n_groups > EF_BANK_MAX_PROBES || face_h <= 0 || face_w <= 0 || !(threshold == threshold) ||
+      (t->nprob > 0 && !prob_group))
+    return set_err(c, EF_E_INVALID, "ef_scan_prepare: bad arguments");
+  for (int p = 0; p < t->nprob; ++p)
+    if (prob_group[p] < 0 || prob_group[p] >= n_groups)
+      return set_err(c, EF_E_INVALID, "ef_scan_prepare: problem " + std::to_string(p) + " has no valid group");
+  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+  // the stream may still run a frame of the old plan
+  EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  t->scan.reset();
+  std::unique_ptr<ScanPlan> sp(new ScanPlan());
+  sp->n_groups = n_groups;
+  sp->face_h = face_h;
+  sp->face_w = face_w;
+  sp->threshold = threshold;
+  // int(frame_width * corner_threshold) etc. of is_detection_in_corner, in double as Python does
+  sp->corner = ScanCorner{t->W, t->H, (int)((double)t->W * 0.15), (int)((double)t->H * 0.15),
+                          (int)((double)t->W * 0.05), (int)((double)t->H * 0.05)};
+  EF_TRY(ensure(c, sp->prob_group, std::max<size_t>((size_t)t->nprob * sizeof(int), 16)));
+  EF_TRY(ensure(c, sp->gray, (size_t)round_up((int64_t)t->H * t->W, 4)));
+  if (t->nprob > 0) {
+    EF_HIP(c, hipMemcpyAsync(sp->prob_group.p, prob_group, (size_t)t->nprob * sizeof(int), hipMemcpyHostToDevice,
+                             c->stream), "H2D groups");
+    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  }
+  t->scan = std::move(sp);
+  return EF_OK;
+}
+
+int ef_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
+                  ef_scan_det* dets, int64_t* keys, int32_t* best_slot, uint8_t* rows, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  TmState* t = c->tm;
+  ScanPlan* sp = t ? t->scan.get() : nullptr;
+  if (!sp) return set_err(c, EF_E_STATE, "ef_scan_frame: no scan plan (call ef_tm_prepare, then ef_scan_prepare)");
+  Bank& bk = c->bank;
+  if (bk.slots.empty()) return set_err(c, EF_E_STATE, "ef_scan_frame: the bank is empty (call ef_bank_add)");
+  const int64_t d = (int64_t)sp->face_h * sp->face_w;
+  if (bk.d != d)
+    return set_err(c, EF_E_STATE, "ef_scan_frame: the bank's models take " + std::to_string(bk.d) +
+                                      " pixels, the scan plan's faces have " + std::to_string(d));
+  if (c->comm && c->comm_size > 1)
+    return set_err(c, EF_E_STATE, "ef_scan_frame: not available with a communicator attached");
+  if (!frame || !dets || !keys || (channels != 1 && channels != 3 && channels != 4) ||
+      frame_ld < (int64_t)t->W * channels || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE))
+    return set_err(c, EF_E_INVALID, "ef_scan_frame: bad arguments");
+  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+  const bool dev = flags & EF_MEM_DEVICE;
+  hipStream_t s = c->stream;
+  const int H = t->H, W = t->W, G = sp->n_groups;
+  const size_t M = bk.slots.size();
+
+  // where the kernels write: the caller's device arrays, or the result block; the rows always
+  // exist (the bank reads them)
+  Carve size_out, cv;
+  carve_scan_out(size_out, (size_t)G, M, (size_t)d);
+  ScanOut o{dets, reinterpret_cast<long long*>(keys), best_slot, rows};
+  if (!dev || !rows) {
+    EF_TRY(ensure(c, sp->out, size_out.total));
+    cv.base = sp->out.p;
+    const ScanOut blk = carve_scan_out(cv, (size_t)G, M, (size_t)d);
+    if (!dev)
+      o = blk;
+    else
+      o.rows = blk.rows;
+  }
+  if (!dev && sp->host.bytes < size_out.total) EF_HIP(c, pinned_alloc(sp->host, size_out.total), "pinned results");
+  const uint8_t* f = frame;
+  if (!dev) {
+    const int64_t row_bytes = (int64_t)W * channels;
+    EF_TRY(ensure(c, sp->frame_in, (size_t)H * row_bytes));
+    EF_HIP(c, hipMemcpy2DAsync(sp->frame_in.p, row_bytes, frame, frame_ld, row_bytes, H, hipMemcpyHostToDevice, s),
+           "H2D frame");
+    f = static_cast<const uint8_t*>(sp->frame_in.p);
+    frame_ld = row_bytes;
+  }
+  TimerEvt tev;
+  timer_begin(c, EF_KERNEL_SCAN, &tev);
+  if (channels != 1) {
+    const int64_t quads = ((int64_t)H * W + 3) / 4;
+    const dim3 grid((unsigned)((quads + 255) / 256));
+    uint32_t* g32 = static_cast<uint32_t*>(sp->gray.p);
+    if (flags & EF_IMG_RGB)
+      hipLaunchKernelGGL(frame_gray_kernel<true>, grid, dim3(256), 0, s, f, frame_ld, H, W, channels, g32);
+    else
+      hipLaunchKernelGGL(frame_gray_kernel<false>, grid, dim3(256), 0, s, f, frame_ld, H, W, channels, g32);
+    EF_HIP(c, hipGetLastError(), "frame grey kernel");
+    f = static_cast<const uint8_t*>(sp->gray.p);
+    frame_ld = W;
+  }
+  EF_TRY(tm_queue(c, t, f, frame_ld, nullptr, nullptr));
+  hipLaunchKernelGGL(scan_select_kernel, dim3((unsigned)G), dim3(256), 0, s,
+                     static_cast<const unsigned long long*>(t->keys.p), static_cast<const TmProblem*>(t->d_probs.p),
+                     static_cast<const int*>(sp->prob_group.p), t->nprob, sp->corner, sp->threshold, o.dets);
+  EF_HIP(c, hipGetLastError(), "scan selection kernel");
+  // grey of a crop == crop of the grey: the rectangles come straight from the dets (x, y, w, h
+  // are four consecutive ints of a 32-byte record; found = 0 leaves w = h = 0: a zero row)
+  static_assert(sizeof(ef_scan_det) == 32 && offsetof(ef_scan_det, x) == 8, "ef_scan_det layout");
+  EF_HIP(c, launch_roi_resize(s, f, frame_ld, H, W, 1, &o.dets->x, 8, G, sp->face_h, sp->face_w, false, o.rows),
+         "ROI resize kernel");
+  EF_TRY(bank_recognize_dev(c, o.rows, EF_U8, G, metric, o.keys, nullptr, o.best, nullptr));
+  timer_end(c, &tev);
+  if (dev) return EF_OK;
+  EF_HIP(c, hipMemcpyAsync(sp->host.p, sp->out.p, size_out.total, hipMemcpyDeviceToHost, s), "D2H results");
+  EF_HIP(c, hipStreamSynchronize(s), "sync");
+  Carve hv;
+  hv.base = sp->host.p;
+  const ScanOut h = carve_scan_out(hv, (size_t)G, M, (size_t)d);
+  std::memcpy(dets, h.dets, (size_t)G * sizeof(ef_scan_det));
+  std::memcpy(keys, h.keys, (size_t)G * M * sizeof(long long));
+  if (best_slot) std::memcpy(best_slot, h.best, (size_t)G * sizeof(int));
+  if (rows) std::memcpy(rows, h.rows, (size_t)G * d);
   return EF_OK;
 }
 

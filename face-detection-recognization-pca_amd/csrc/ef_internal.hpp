@@ -41,6 +41,7 @@ inline int proj_pad(int kp) { return kp <= 64 ? 64 : (kp + 127) / 128 * 128; }
 constexpr int kSearchProbeTile = 256;   // probes per search workgroup (4 waves x 64)
 constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
+constexpr int kTimers = 9;              // EF_KERNEL_* ids (include/eigenface.h)
 constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
 
 // Workspace of one search call (device pointers).
@@ -303,6 +304,13 @@ struct Bank {
   DevBuf p_stage;     // probe pixels staged from host
 };
 
+// ef_bank_recognize on device pointers (ef_bank.hip), shared with ef_scan_frame: b probes
+// Pd[b][bank.d] -> kdev[b][slots] and, each optional, mdev[b][slots], sdev[b] (best slot) and
+// fdev[b][sum k].  Everything is queued on c->stream; only the table upload after the bank
+// changed waits.  The caller has checked the bank's state and the arguments.
+int bank_recognize_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, int metric, long long* kdev, ef_match* mdev,
+                       int* sdev, float* fdev);
+
 struct TmState;    // template-localiser state (ef_image.hip)
 struct HaarState;  // Haar cascade state (ef_haar.hip)
 
@@ -399,8 +407,8 @@ struct ef_ctx {
   ef::DevBuf q_local;      // float[cpad][kp] this rank's slice of the projected probes
 
   bool timing = false;
-  double t_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int64_t t_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double t_ms[ef::kTimers] = {};
+  int64_t t_n[ef::kTimers] = {};
 
   // streams and events, all created on first use except own_stream (ef_create)
   ef::Stream own_stream;

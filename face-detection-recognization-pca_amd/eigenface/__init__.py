@@ -8,6 +8,7 @@ from ._native import EigenfaceError, NativeLibraryError, LIB_PATH  # noqa: F401
 from .engine import Engine, FitResult, decode_keys, device_count, merge_matches_host, merge_topk_host  # noqa: F401
 from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_face_to_eigenspace  # noqa: F401
 from .bank import ModelBank, best_over_models  # noqa: F401
+from .scanner import FrameScanner, decide  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
     get_engine,
@@ -31,4 +32,5 @@ __all__ = [
     "recognize_face_candidates_with_model", "EigenfaceError",
     "NativeLibraryError", "LIB_PATH", "save_gallery_cache", "load_gallery_cache", "ManualPCA",
     "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity", "ModelBank", "best_over_models",
+    "FrameScanner", "decide",
 ]

@@ -21,8 +21,10 @@ EF_FIT_STANDARDIZE = 0x1
 EF_MODEL_BF16 = 0x2
 EF_MEM_DEVICE = 0x100
 EF_IMG_RGB = 0x200
+EF_ROI_RECTS_DEVICE = 0x400
 EF_KERNEL_SEARCH, EF_KERNEL_PROJECT, EF_KERNEL_TMATCH, EF_KERNEL_INGEST, EF_KERNEL_HAAR, EF_KERNEL_JPEG, \
     EF_KERNEL_SYRK, EF_KERNEL_JPEG_HOST = 0, 1, 2, 3, 4, 5, 6, 7
+EF_KERNEL_SCAN = 8
 EF_JPEG_GRAY, EF_JPEG_BGR = 0, 1
 EF_JPEG_E_UNSUPPORTED, EF_JPEG_E_CORRUPT = -10, -11
 EF_KEY_NONE = (1 << 63) - 1
@@ -41,6 +43,17 @@ EF_TOPK_MAX = 64  # most ranks of a top-m search
 EF_BANK_MAX_MODELS = 4096
 EF_BANK_MAX_PROBES = 4096  # per ef_bank_recognize call
 EF_E_NUMERIC = -5
+
+
+class ef_scan_det(C.Structure):
+    """include/eigenface.h ef_scan_det: one group's detection of a scanned frame."""
+    _fields_ = [("found", C.c_int32), ("problem", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32),
+                ("h", C.c_int32), ("confidence", C.c_float), ("pad", C.c_int32)]
+
+
+# numpy view of an ef_scan_det array
+SCAN_DET_DTYPE = [("found", "<i4"), ("problem", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"),
+                  ("confidence", "<f4"), ("pad", "<i4")]
 
 
 class ef_match(C.Structure):
@@ -132,6 +145,10 @@ _SIGS = {
     "ef_bank_recognize": ([vp, vp, i32, i64, i32, vp, vp, vp, vp, u32], C.c_int),
     "ef_bank_schedule": ([i64, i64, vp, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)],
                          C.c_int),
+    # ROI ingest and frame scan: added the same way, bound by symbol
+    "ef_preprocess_rois": ([vp, vp, i64, i32, i32, i32, vp, i64, i32, i32, vp, u32], C.c_int),
+    "ef_scan_prepare": ([vp, vp, i32, i32, i32, C.c_double], C.c_int),
+    "ef_scan_frame": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, u32], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

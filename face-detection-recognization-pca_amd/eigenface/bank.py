@@ -90,6 +90,11 @@ class ModelBank:
         if getattr(eng, "bank_owner", None) is not self:  # another bank replaced this one's slots
             self.refresh()
         idx, sim, _ = eng.bank_recognize(rows, "cosine")
+        return self.label(idx, sim, threshold)
+
+    def label(self, idx, sim, threshold=0.8):
+        """recognize_face_all_models' labelling of per-slot results ``idx[b, M]`` (gallery row,
+        -1 for none) and ``sim[b, M]`` (cosine similarity): [(person_id, name, confidence)]."""
         best = best_over_models(sim, "cosine")  # the labelling rule, on the returned scores
         out = []
         for p, m in enumerate(best):

@@ -142,6 +142,9 @@ class Engine:
         self.gallery_owner = None
         self.bank_owner = None  # the ModelBank whose slots the bank holds, if one filled it
         self._bank_k = []
+        self._tm = None    # (problems, H, W, problem table) of the prepared localiser
+        self._scan = None  # (groups, face height, face width) of the frame scan's plan
+        self.scan_owner = None  # the FrameScanner whose plan and localiser are in place, if any
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -926,6 +929,73 @@ class Engine:
                                           ws.ctypes.data, cs.ctypes.data, n, oh, ow, res.ctypes.data, flags))
         return res
 
+    @staticmethod
+    def _frame_view(frame):
+        """(array or tensor, pointer, row stride in bytes, H, W, channels, on device) of a uint8
+        frame (H, W) or (H, W, 1|3|4).  A view whose pixels are contiguous inside each row (a
+        column slice of a wider frame) is passed as it is, with its row stride; anything else
+        is copied."""
+        dev = _is_dev(frame)
+        if dev:
+            import torch
+            if frame.dtype != torch.uint8:
+                raise TypeError(f"frame must be uint8, got {frame.dtype}")
+            f = frame
+            strides = tuple(int(v) for v in f.stride())
+        else:
+            f = np.asarray(frame)
+            if f.dtype != np.uint8:
+                raise TypeError(f"frame must be uint8, got {f.dtype}")
+            strides = f.strides
+        if f.ndim not in (2, 3) or 0 in f.shape:
+            raise ValueError("frame must be (H, W) or (H, W, channels) and not empty")
+        h, w = int(f.shape[0]), int(f.shape[1])
+        ch = 1 if f.ndim == 2 else int(f.shape[2])
+        inner = strides[1:] == ((1,) if f.ndim == 2 else (ch, 1))
+        if not inner or strides[0] < w * ch:
+            f = f.contiguous() if dev else np.ascontiguousarray(f)
+            ld = w * ch
+        else:
+            ld = int(strides[0])
+        return f, (f.data_ptr() if dev else f.ctypes.data), ld, h, w, ch, dev
+
+    def preprocess_rois(self, frame, rects, size=(64, 64), rgb=False, out=None):
+        """Grey + INTER_LINEAR resize of rectangles of one frame (include/eigenface.h
+        ef_preprocess_rois): row i equals ``preprocess([frame[y:y+h, x:x+w]], size)[0]`` for
+        ``rects[i] = (x, y, w, h)``, without the crops being copied out.  ``frame`` is a uint8
+        array (H, W) or (H, W, 3|4) (BGR unless ``rgb``), or a device tensor; a row-strided
+        view is read in place.  Host ``rects`` are validated (a bad one raises).  With a
+        device frame, ``rects`` may be a device int32 tensor (n, 4): the call is then
+        stream-ordered with no host wait, and the kernel clips each rectangle to the frame (a
+        zero row for an empty one or a negative origin).  Returns (n, height*width) uint8:
+        NumPy for a host frame, a device tensor (``out`` when given) for a device frame."""
+        ow, oh = int(size[0]), int(size[1])
+        f, fp, ld, h, w, ch, dev = self._frame_view(frame)
+        flags = N.EF_IMG_RGB if rgb else 0
+        if _is_dev(rects):
+            import torch
+            if not dev:
+                raise TypeError("device rectangles need a device frame")
+            r, rp = _dev(rects, torch.int32)
+            flags |= N.EF_ROI_RECTS_DEVICE
+        else:
+            r, rp = _host(rects, np.int32)
+        if r.shape[0] and (r.ndim != 2 or r.shape[1] != 4):
+            raise ValueError("rects must be (n, 4): x, y, w, h")
+        n = int(r.shape[0])
+        if not dev:
+            res = np.empty((n, oh * ow), np.uint8)
+            self._chk(self._lib.ef_preprocess_rois(self._h, fp, ld, h, w, ch, rp, n, oh, ow, res.ctypes.data, flags))
+            return res
+        import torch
+        if out is None:
+            out = torch.empty((n, oh * ow), dtype=torch.uint8, device=f.device)
+        self._dev_out(out, (n, oh * ow), torch.uint8, "out")
+        with self._torch_order(f, out, r if _is_dev(r) else None):
+            self._chk(self._lib.ef_preprocess_rois(self._h, fp, ld, h, w, ch, rp, n, oh, ow, out.data_ptr(),
+                                                   flags | N.EF_MEM_DEVICE))
+        return out
+
     # ----------------------------------------------------------------- JPEG decode
     def decode_jpegs(self, blobs, mode="bgr"):
         """GPU decode of a batch of JPEG files (include/eigenface.h ef_jpeg_decode):
@@ -999,6 +1069,7 @@ class Engine:
         pr = np.asarray(problems, dtype=np.int64).reshape(-1, 3)
         pt, ph, pw = (np.ascontiguousarray(pr[:, i], dtype=np.int32) for i in range(3))
         H, W = (int(v) for v in frame_shape)
+        self._scan = self.scan_owner = None  # a new localiser drops the frame scan's plan
         self._chk(self._lib.ef_tm_prepare(self._h, buf.ctypes.data, offs.ctypes.data, th.ctypes.data,
                                           tw.ctypes.data, nt, pt.ctypes.data, ph.ctypes.data, pw.ctypes.data,
                                           len(pr), H, W, 0))
@@ -1036,6 +1107,58 @@ class Engine:
             o += m
         return best, xs, ys, out
 
+    # ----------------------------------------------------------------- frame scan
+    def scan_prepare(self, prob_group, n_groups, face_size=(64, 64), threshold=0.6):
+        """The frame scan's plan over the prepared localiser (ef_scan_prepare): problem p
+        belongs to group (person) ``prob_group[p]``; faces are resized to cv2's ``face_size``
+        (width, height).  A later tm_prepare drops the plan."""
+        if getattr(self, "_tm", None) is None:  # the library reports the state error
+            self._chk(self._lib.ef_scan_prepare(self._h, None, int(n_groups), 1, 1, float(threshold)))
+        g, gp = _host(prob_group, np.int32)
+        if g.ndim != 1 or g.shape[0] != self._tm[0]:
+            raise ValueError(f"prob_group must have one group per problem ({self._tm[0]})")
+        fw, fh = int(face_size[0]), int(face_size[1])
+        self._chk(self._lib.ef_scan_prepare(self._h, gp if g.shape[0] else None, int(n_groups), fh, fw,
+                                            float(threshold)))
+        self._scan = (int(n_groups), fh, fw)
+
+    def scan_frame(self, frame, metric="cosine", rgb=False):
+        """One frame through grey, localiser, selection, ROI rows and the model bank
+        (ef_scan_frame): (dets, keys[G, M] int64, best_slot[G] int32, rows[G, h*w] uint8) for
+        the plan's G groups and the bank's M slots.  ``frame`` is (H, W) grey or (H, W, 3|4)
+        BGR(A) (RGB(A) with ``rgb``) of the prepared frame size.  A host frame gives NumPy
+        arrays, dets as records of N.SCAN_DET_DTYPE, after one upload, one download and one
+        synchronisation; a device tensor gives device tensors, dets as (G, 8) int32 in the
+        fields' order (confidence as float32 bits), stream-ordered with no host wait."""
+        mt = _metric(metric)
+        if getattr(self, "_tm", None) is None or getattr(self, "_scan", None) is None:
+            # the library reports the state error
+            self._chk(self._lib.ef_scan_frame(self._h, None, 0, 1, mt, None, None, None, None, 0))
+            raise RuntimeError("call scan_prepare first")
+        (G, fh, fw), H, W = self._scan, self._tm[1], self._tm[2]
+        f, fp, ld, h, w, ch, dev = self._frame_view(frame)
+        if (h, w) != (H, W):
+            raise ValueError(f"frame must be {(H, W)}, got {(h, w)}")
+        M = self.bank_info()[0]
+        flags = N.EF_IMG_RGB if rgb else 0
+        if dev:
+            import torch
+            dets = torch.empty((G, 8), dtype=torch.int32, device=f.device)
+            keys = torch.empty((G, M), dtype=torch.int64, device=f.device)
+            best = torch.empty(G, dtype=torch.int32, device=f.device)
+            rows = torch.empty((G, fh * fw), dtype=torch.uint8, device=f.device)
+            with self._torch_order(f, dets, keys, best, rows):
+                self._chk(self._lib.ef_scan_frame(self._h, fp, ld, ch, mt, dets.data_ptr(), keys.data_ptr(),
+                                                  best.data_ptr(), rows.data_ptr(), flags | N.EF_MEM_DEVICE))
+            return dets, keys, best, rows
+        dets = np.empty(G, dtype=N.SCAN_DET_DTYPE)
+        keys = np.empty((G, M), dtype=np.int64)
+        best = np.empty(G, dtype=np.int32)
+        rows = np.empty((G, fh * fw), dtype=np.uint8)
+        self._chk(self._lib.ef_scan_frame(self._h, fp, ld, ch, mt, dets.ctypes.data, keys.ctypes.data,
+                                          best.ctypes.data, rows.ctypes.data, flags))
+        return dets, keys, best, rows
+
     # --------------------------------------------------------------------- timing
     def timing(self, on=True):
         self._chk(self._lib.ef_timing_enable(self._h, 1 if on else 0))
@@ -1046,7 +1169,7 @@ class Engine:
     def timing_get(self, kernel="search"):
         kid = {"search": N.EF_KERNEL_SEARCH, "project": N.EF_KERNEL_PROJECT, "tmatch": N.EF_KERNEL_TMATCH,
                "ingest": N.EF_KERNEL_INGEST, "haar": N.EF_KERNEL_HAAR, "jpeg": N.EF_KERNEL_JPEG,
-               "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST}[kernel]
+               "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST, "scan": N.EF_KERNEL_SCAN}[kernel]
         ms = C.c_double(0)
         n = C.c_int64(0)
         self._chk(self._lib.ef_timing_get(self._h, kid, C.byref(ms), C.byref(n)))

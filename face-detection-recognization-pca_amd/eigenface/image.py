@@ -3,6 +3,8 @@
 * ``preprocess_faces``   — the per-image ``cv2.cvtColor(BGR2GRAY)`` + ``cv2.resize(64, 64)``
                            of train-v4.py:59-68 / scan-template-v4.py:257-263, for a whole
                            ragged batch in one launch (``ef_preprocess``).
+* ``preprocess_rois``    — the same for rectangles of one frame, read in place
+                           (``ef_preprocess_rois``).
 * ``match_template``     — ``cv2.matchTemplate(frame, templ, TM_CCOEFF_NORMED)``
                            (scan-template-v4.py:183), exact integer correlation on the int8
                            matrix cores (``ef_tm_prepare`` / ``ef_tm_match``).
@@ -29,6 +31,13 @@ SCALES = (0.8, 1.0, 1.2)  # scan-template-v4.py:161
 def preprocess_faces(images, size=(64, 64), rgb=False, device=0):
     """uint8 (n, h*w) face rows from decoded images (BGR or grey; ``rgb`` for RGB order)."""
     return get_engine(device).preprocess(images, size, rgb=rgb)
+
+
+def preprocess_rois(frame, rects, size=(64, 64), rgb=False, device=0):
+    """uint8 (n, h*w) face rows of the rectangles ``rects[i] = (x, y, w, h)`` of one frame: the
+    crop + grey + resize of scan-template-v4.py:360 / :257-263 (and of the Haar path,
+    useless/scan.py:231-249) for every detection in one launch, no crop copied (``ef_preprocess_rois``)."""
+    return get_engine(device).preprocess_rois(frame, rects, size, rgb=rgb)
 
 
 def is_detection_in_corner(det, frame_width, frame_height, corner_threshold=0.15, border_threshold=0.05):

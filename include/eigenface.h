@@ -53,6 +53,7 @@ extern "C" {
 #define EF_MODEL_BF16 0x2u      /* ef_model_set: project on bf16 MFMA (config 5), fp32 features */
 #define EF_MEM_DEVICE 0x100u    /* pointer args are device pointers, call is asynchronous    */
 #define EF_IMG_RGB 0x200u       /* ef_preprocess: 3/4-channel pixels are RGB(A), not BGR(A)  */
+#define EF_ROI_RECTS_DEVICE 0x400u /* ef_preprocess_rois: rects is a device pointer          */
 
 /* kernels whose device time can be queried with ef_timing_get */
 #define EF_KERNEL_SEARCH 0  /* distance GEMM + fused arg-best   */
@@ -64,6 +65,11 @@ extern "C" {
 #define EF_KERNEL_SYRK 6    /* the fit's int8 covariance/Gram SYRK, all passes of one fit */
 #define EF_KERNEL_JPEG_HOST 7 /* host staging of one ef_jpeg_ingest part (marker parse, destuff, tables):
                                 wall time on the host, not a device kernel (API v7) */
+#define EF_KERNEL_SCAN 8    /* everything one ef_scan_frame queues: grey, localiser, selection, ROI rows, bank.
+                                The bank's launches inside it also count under EF_KERNEL_PROJECT and
+                                EF_KERNEL_SEARCH (one launch each per frame, as in ef_bank_recognize), and their
+                                two event pairs are recorded inside the scan's span; EF_KERNEL_TMATCH and
+                                EF_KERNEL_INGEST do not count scans */
 
 /* No-result sentinel in a key array (empty gallery). */
 #define EF_KEY_NONE INT64_MAX
@@ -466,6 +472,77 @@ int ef_tm_info(ef_ctx* ctx, int32_t* n_problems, int64_t* map_elems, int32_t* re
  * every area is < 2^18 and (frame_h + 1)(frame_w + 1) < 2^30, else 64 (int64 sums); the
  * EF_OPT_TM_INT64_SUMS option forces 64 per context.  EF_E_INVALID on bad sizes. */
 int ef_tm_sums_bits(int32_t frame_h, int32_t frame_w, int64_t max_template_area);
+
+/* ------------------------------------------------------------------ ROI ingest
+ * Added after API v7 without a version bump (purely additive): detect by symbol.
+ *
+ * ef_preprocess for n rectangles of one frame, without copying the crops out: row i of out
+ * (n x out_h x out_w uint8) is bit-identical to ef_preprocess of the contiguous copy of
+ * frame[y:y+h, x:x+w] (scan-template-v4.py:360, :390; useless/scan.py:231-249), with the same
+ * meaning of EF_IMG_RGB and the same identity and exact-2x shortcuts.  The frame is
+ * frame_h x frame_w x channels (1, 3, 4) with a row stride of frame_ld >= frame_w * channels
+ * bytes; rects[i] = {x, y, w, h}.  The bilinear neighbours clamp to the rectangle, never to
+ * the frame.
+ *   host rects (default): x, y >= 0, w, h > 0, x + w <= frame_w and y + h <= frame_h, else
+ *     EF_E_INVALID naming the rectangle; the call waits for the stream before it returns.
+ *   EF_ROI_RECTS_DEVICE: rects is a device pointer (it may have been written by a kernel
+ *     queued earlier on the ctx's stream).  Nothing can be validated on the host, so the
+ *     kernel clips every rectangle to the frame before any load: a rectangle that overhangs
+ *     gives the row of its clipped part, one that is empty after clipping or has a negative
+ *     origin gives an all-zero row, and no value makes the kernel read outside
+ *     frame_h x frame_ld bytes.
+ *   EF_MEM_DEVICE: frame and out are device pointers; with EF_ROI_RECTS_DEVICE too the call is
+ *     stream-ordered with no host wait.
+ * n <= 65535; n = 0 is EF_OK. */
+int ef_preprocess_rois(ef_ctx* ctx, const uint8_t* frame, int64_t frame_ld, int32_t frame_h, int32_t frame_w,
+                       int32_t channels, const int32_t* rects, int64_t n, int32_t out_h, int32_t out_w,
+                       uint8_t* out, uint32_t flags);
+
+/* ------------------------------------------------------------------ frame scan
+ * Added after API v7 without a version bump (purely additive): detect by symbol.
+ *
+ * One frame of the live loop (scan-template-v4.py:340-391) as one stream-ordered sequence:
+ * BGR -> grey, template_match_all_models (:127-200), the crop + grey + resize of every
+ * detection (:360, :257-263) and recognize_face_all_models (:289-319) through the model bank.
+ *
+ * ef_scan_prepare: needs a prepared localiser (ef_tm_prepare), else EF_E_STATE.  Problem p of
+ *   the localiser belongs to group prob_group[p] in [0, n_groups) (a group is a person, the
+ *   reference's models in order), 1 <= n_groups <= EF_BANK_MAX_PROBES.  Faces are resized to
+ *   face_h x face_w; `threshold` is template_match_all_models' (0.6).  The four integers of
+ *   is_detection_in_corner, int(W*0.15), int(H*0.15), int(W*0.05), int(H*0.05), are computed
+ *   here once, in double arithmetic.  The plan belongs to the localiser: a new ef_tm_prepare
+ *   drops it.  Host pointer; synchronous.
+ *
+ * ef_scan_frame: frame is frame_h x frame_w (of ef_tm_prepare) x channels (1 grey; 3, 4 BGR(A),
+ *   or RGB(A) with EF_IMG_RGB), row stride frame_ld bytes.  On the ctx's stream it queues
+ *     a. channels 3, 4: the grey plane, BT.601 fixed point as ef_preprocess;
+ *     b. the localiser's kernels (as ef_tm_match) on that plane;
+ *     c. per group template_match_all_models' rule over the group's problems in index order: a
+ *        candidate with v > best (strict, best from 0.0) that is_detection_in_corner rejects
+ *        never changes the state, any other becomes the best; a best with (double)v >
+ *        threshold is a detection -> dets[g] = {found, problem, x, y, w, h, confidence};
+ *        every field is 0 where found = 0;
+ *     d. ef_preprocess_rois of the dets' rectangles on the grey plane -> rows[g] (zero where
+ *        found = 0);
+ *     e. ef_bank_recognize of those n_groups rows (EF_U8, b = n_groups, `metric`) ->
+ *        keys[n_groups][M] and best_slot[n_groups], with exactly ef_bank_recognize's meaning
+ *        (bit-identical to that call on the same rows with the same b).
+ *   best_slot and rows are optional.  EF_E_STATE without a scan plan, with an empty bank, when
+ *   the bank's d is not face_h * face_w, or with a communicator of more than one rank attached.
+ *   Host pointers: one upload of the frame, one download of one pinned result block, one
+ *   stream synchronisation.  EF_MEM_DEVICE: every array is a device pointer and nothing waits
+ *   on the host (apart from the bank's one-time table upload after the bank changed). */
+typedef struct ef_scan_det {
+  int32_t found, problem, x, y, w, h;
+  float confidence;
+  int32_t pad;
+} ef_scan_det;
+int ef_scan_prepare(ef_ctx* ctx, const int32_t* prob_group /* [n_problems] */, int32_t n_groups, int32_t face_h,
+                    int32_t face_w, double threshold);
+int ef_scan_frame(ef_ctx* ctx, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
+                  ef_scan_det* dets /* [n_groups] */, int64_t* keys /* [n_groups][M] */,
+                  int32_t* best_slot /* [n_groups], optional */, uint8_t* rows /* [n_groups][face_h*face_w], optional */,
+                  uint32_t flags);
 
 /* --------------------------------------------------------- Haar cascade detector
  * Replaces face_cascade.detectMultiScale(gray, scaleFactor, minNeighbors, minSize)
