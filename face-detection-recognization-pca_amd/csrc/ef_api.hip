@@ -690,6 +690,13 @@ int ef_trim(ef_ctx* c) {
   return EF_OK;
 }
 
+// no reconstruction state: the flag first, then the resident operands (the frees wait for the device)
+static void recon_drop(ef_ctx* c) {
+  c->recon = false;
+  release(c->recon_R);
+  release(c->recon_w);
+}
+
 int ef_model_set(ef_ctx* c, const float* mean, const float* W, int64_t d, int32_t k, uint32_t flags) {
   if (!c) return EF_E_INVALID;
   if (!mean || !W || d < 1 || k < 1) return set_err(c, EF_E_INVALID, "ef_model_set: bad arguments");
@@ -699,6 +706,7 @@ int ef_model_set(ef_ctx* c, const float* mean, const float* W, int64_t d, int32_
   const bool bf16 = (flags & EF_MODEL_BF16) != 0;
   const int kpw = bf16 ? (kp + 127) / 128 * 128 : proj_pad(kp);  // bf16 kernel: 128-column tiles
   c->d = 0;  // no model until the last step has succeeded (never old dimensions over new buffers)
+  recon_drop(c);  // its R belonged to the old W
   {
     DevBuf staging;  // freed at the end of this block, after the synchronise (or by a hipFree that waits)
     EF_TRY(weights_load(c, c->mean, c->W, mean, W, d, k, kpw, flags, staging));
@@ -759,6 +767,120 @@ int ef_project(ef_ctx* c, const void* P, int32_t dtype, int64_t b, float* F, uin
   Results r{(flags & EF_MEM_DEVICE) != 0, b, 1, c->k, nullptr, nullptr, F};
   EF_TRY(r.stage_feats(c));
   EF_TRY(project_dev(c, Pd, dtype, b, bpad, r.fdev, &c->q_pad));
+  return r.fetch(c);
+}
+
+int ef_recon_set(ef_ctx* c, const float* R, const float* weight, int64_t d, int32_t k, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (c->d == 0) return set_err(c, EF_E_STATE, "ef_recon_set: no model (call ef_model_set)");
+  (void)hipSetDevice(c->device);
+  recon_drop(c);  // a failed call leaves none
+  if (!R || d != c->d || k != c->k) return set_err(c, EF_E_INVALID, "ef_recon_set: R must be the model's k x d");
+  if (d > (int64_t)INT_MAX - 128) return set_err(c, EF_E_INVALID, "ef_recon_set: d >= 2^31 - 128 is not supported");
+  const int64_t dp = recon_dpad(d);
+  const bool dev = (flags & EF_MEM_DEVICE) != 0;
+  std::vector<float> ones;
+  DevBuf staging;  // freed after the synchronise below
+  EF_TRY(ensure(c, c->recon_R, (size_t)c->kp * dp * sizeof(float)));
+  EF_TRY(ensure(c, c->recon_w, (size_t)d * sizeof(float)));
+  if (!dev) {
+    EF_TRY(ensure(c, staging, (size_t)k * d * sizeof(float)));
+    EF_HIP(c, hipMemcpyAsync(staging.p, R, (size_t)k * d * sizeof(float), hipMemcpyHostToDevice, c->stream), "copy R");
+    R = static_cast<const float*>(staging.p);
+  }
+  EF_HIP(c, launch_pad_rows(c->stream, R, k, (int)d, c->kp, static_cast<float*>(c->recon_R.p), (int)dp), "pad R");
+  if (!weight) {
+    ones.assign((size_t)d, 1.f);
+    weight = ones.data();
+  }
+  EF_HIP(c,
+         hipMemcpyAsync(c->recon_w.p, weight, (size_t)d * sizeof(float),
+                        dev && ones.empty() ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
+         "copy weight");
+  EF_HIP(c, hipStreamSynchronize(c->stream), "pad R");
+  c->recon = true;
+  return EF_OK;
+}
+
+int ef_reconstruct(ef_ctx* c, const float* F, int64_t b, int32_t out_dtype, void* out, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (!c->recon) return set_err(c, EF_E_STATE, "ef_reconstruct: no reconstruction state (call ef_recon_set)");
+  if (b < 0 || (out_dtype != EF_U8 && out_dtype != EF_F32) || (b > 0 && (!F || !out)))
+    return set_err(c, EF_E_INVALID, "ef_reconstruct: bad arguments");
+  if (b == 0) return EF_OK;  // (an empty batch may come with null pointers)
+  (void)hipSetDevice(c->device);
+  const bool dev = (flags & EF_MEM_DEVICE) != 0;
+  const int64_t bpad = round_up(b, kProjRowTile);
+  const size_t obytes = (size_t)b * c->d * (out_dtype == EF_U8 ? 1 : 4);
+  EF_TRY(ensure(c, c->q_pad, (size_t)bpad * c->kp * sizeof(float)));
+  if (!dev) {
+    const size_t fbytes = (size_t)b * c->k * sizeof(float);
+    EF_TRY(ensure(c, c->p_stage, fbytes));
+    EF_TRY(ensure(c, c->recon_out, obytes));
+    EF_HIP(c, hipMemcpyAsync(c->p_stage.p, F, fbytes, hipMemcpyHostToDevice, c->stream), "H2D features");
+    F = static_cast<const float*>(c->p_stage.p);
+  }
+  void* odev = dev ? out : c->recon_out.p;
+  EF_HIP(c, launch_pad_rows(c->stream, F, b, c->k, bpad, static_cast<float*>(c->q_pad.p), c->kp), "pad features");
+  int tps = 0;
+  const int ns = recon_nsplit(b, c->d, &tps);
+  TimerEvt t;
+  timer_begin(c, EF_KERNEL_RECON, &t);
+  EF_HIP(c,
+         launch_recon(c->stream, out_dtype == EF_U8 ? 1 : 0, EF_F32, static_cast<const float*>(c->q_pad.p), c->kp,
+                      static_cast<const float*>(c->recon_R.p), static_cast<const float*>(c->mean.p),
+                      static_cast<const float*>(c->recon_w.p), nullptr, b, c->d, odev, nullptr, ns, tps),
+         "reconstruct kernel");
+  timer_end(c, &t);
+  if (dev) return EF_OK;
+  EF_HIP(c, hipMemcpyAsync(out, odev, obytes, hipMemcpyDeviceToHost, c->stream), "D2H reconstruction");
+  EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  return EF_OK;
+}
+
+int ef_face_distance(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, float* dffs2, float* energy, float* F_out,
+                     uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (!c->recon) return set_err(c, EF_E_STATE, "ef_face_distance: no reconstruction state (call ef_recon_set)");
+  if (b < 0 || (p_dtype != EF_U8 && p_dtype != EF_F32) || (b > 0 && (!P || !dffs2)))
+    return set_err(c, EF_E_INVALID, "ef_face_distance: bad arguments");
+  if (b == 0) return EF_OK;  // (an empty batch may come with null pointers)
+  (void)hipSetDevice(c->device);
+  const int64_t bpad = round_up(b, kSearchProbeTile);  // ef_project's padding: the same features, bit for bit
+  const void* Pd = nullptr;
+  EF_TRY(stage_probes(c, P, p_dtype, b, c->d, flags, c->p_stage, &Pd));
+  Results r{(flags & EF_MEM_DEVICE) != 0, b, 1, c->k, nullptr, nullptr, F_out};
+  EF_TRY(r.stage_feats(c));
+  EF_TRY(project_dev(c, Pd, p_dtype, b, bpad, r.fdev, &c->q_pad));
+  int tps = 0;
+  const int ns = recon_nsplit(b, c->d, &tps);
+  const int64_t bp = round_up(b, kProjRowTile);
+  EF_TRY(ensure(c, c->recon_part, (size_t)2 * ns * bp * sizeof(float)));
+  float* ddev = dffs2;
+  float* edev = energy;
+  if (!r.dev) {
+    EF_TRY(ensure(c, c->recon_out, (size_t)2 * b * sizeof(float)));
+    ddev = static_cast<float*>(c->recon_out.p);
+    edev = energy ? ddev + b : nullptr;
+  }
+  TimerEvt t;
+  timer_begin(c, EF_KERNEL_RECON, &t);
+  EF_HIP(c,
+         launch_recon(c->stream, 2, p_dtype, static_cast<const float*>(c->q_pad.p), c->kp,
+                      static_cast<const float*>(c->recon_R.p), static_cast<const float*>(c->mean.p),
+                      static_cast<const float*>(c->recon_w.p), Pd, b, c->d, nullptr,
+                      static_cast<float*>(c->recon_part.p), ns, tps),
+         "residual kernel");
+  timer_end(c, &t);
+  timer_begin(c, EF_KERNEL_RECON_REDUCE, &t);
+  EF_HIP(c, launch_recon_reduce(c->stream, static_cast<const float*>(c->recon_part.p), ns, b, ddev, edev),
+         "residual reduce");
+  timer_end(c, &t);
+  if (!r.dev) {
+    EF_HIP(c, hipMemcpyAsync(dffs2, ddev, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H distances");
+    if (energy)
+      EF_HIP(c, hipMemcpyAsync(energy, edev, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H energy");
+  }
   return r.fetch(c);
 }
 

@@ -41,7 +41,7 @@ inline int proj_pad(int kp) { return kp <= 64 ? 64 : (kp + 127) / 128 * 128; }
 constexpr int kSearchProbeTile = 256;   // probes per search workgroup (4 waves x 64)
 constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
-constexpr int kTimers = 9;              // EF_KERNEL_* ids (include/eigenface.h)
+constexpr int kTimers = 11;             // EF_KERNEL_* ids (include/eigenface.h)
 constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
 
 // Workspace of one search call (device pointers).
@@ -380,6 +380,13 @@ struct ef_ctx {
   ef::DevBuf proj_part; // float[nsplit][bpad][kpw]
   ef::DevBuf feats_dev; // float[b][k] staging for host output
 
+  // reconstruction x^ = mean + f . R of the model above (ef_recon_set; ef_model_set drops it)
+  bool recon = false;
+  ef::DevBuf recon_R;     // float[kp][recon_dpad(d)], zero past k and past d
+  ef::DevBuf recon_w;     // float[d] per-pixel weight (ones when the caller gave none)
+  ef::DevBuf recon_part;  // float[2][nsplit][round_up(b, 128)] partial eps^2 and E
+  ef::DevBuf recon_out;   // staging of a host call's outputs (pixels, or eps^2 and E)
+
   ef::Bank bank;  // model bank (ef_bank_*): independent of the model and gallery above
 
   std::vector<ef::DevBuf> fit_pool;  // ef_fit workspaces, reused across calls (ef_trim frees)
@@ -581,5 +588,19 @@ hipError_t launch_project_bf16(hipStream_t s, int p_dtype, const void* P, int64_
 bool bf16_frag_supported(int64_t d, int ldw);
 hipError_t launch_bf16_frag(hipStream_t s, const unsigned short* Wt16, int64_t d, int ldw, void* Wf);
 hipError_t launch_mean_u8(hipStream_t s, const float* mean_r, int64_t d, uint8_t* out, int* bad);
+
+// ---- back-projection (ef_recon.hip) ---------------------------------------------------
+// R is kept as [kp][recon_dpad(d)] (zero past k and past d).  recon_nsplit: pixel-axis splits of
+// a launch over b probes and the 128-pixel tiles each split walks.  launch_recon: qpad holds at
+// least round_up(b, 128) rows of kp (zero past b and past k); epi 0 stores mean + f . R as fp32
+// into out[b][d], 1 as uint8 (clamped, round half to even), 2 reads the pixels P (p_dtype) and
+// writes part[2][nsplit][round_up(b, 128)]: the partial eps^2, then the partial energy, which
+// launch_recon_reduce adds in split order into dffs2[b] and (optional) energy[b].
+int64_t recon_dpad(int64_t d);
+int recon_nsplit(int64_t b, int64_t d, int* tiles_per_split);
+hipError_t launch_recon(hipStream_t s, int epi, int p_dtype, const float* qpad, int kp, const float* R, const float* mean,
+                        const float* wgt, const void* P, int64_t b, int64_t d, void* out, float* part, int nsplit,
+                        int tiles_per_split);
+hipError_t launch_recon_reduce(hipStream_t s, const float* part, int nsplit, int64_t b, float* dffs2, float* energy);
 
 }  // namespace ef

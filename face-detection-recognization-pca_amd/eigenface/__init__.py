@@ -9,6 +9,7 @@ from .engine import Engine, FitResult, decode_keys, device_count, merge_matches_
 from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_face_to_eigenspace  # noqa: F401
 from .bank import ModelBank, best_over_models  # noqa: F401
 from .scanner import FrameScanner, decide  # noqa: F401
+from .compat import face_space_distance, reconstruct_faces  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
     get_engine,
@@ -32,5 +33,5 @@ __all__ = [
     "recognize_face_candidates_with_model", "EigenfaceError",
     "NativeLibraryError", "LIB_PATH", "save_gallery_cache", "load_gallery_cache", "ManualPCA",
     "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity", "ModelBank", "best_over_models",
-    "FrameScanner", "decide",
+    "FrameScanner", "decide", "reconstruct_faces", "face_space_distance",
 ]

@@ -25,6 +25,7 @@ EF_ROI_RECTS_DEVICE = 0x400
 EF_KERNEL_SEARCH, EF_KERNEL_PROJECT, EF_KERNEL_TMATCH, EF_KERNEL_INGEST, EF_KERNEL_HAAR, EF_KERNEL_JPEG, \
     EF_KERNEL_SYRK, EF_KERNEL_JPEG_HOST = 0, 1, 2, 3, 4, 5, 6, 7
 EF_KERNEL_SCAN = 8
+EF_KERNEL_RECON, EF_KERNEL_RECON_REDUCE = 9, 10
 EF_JPEG_GRAY, EF_JPEG_BGR = 0, 1
 EF_JPEG_E_UNSUPPORTED, EF_JPEG_E_CORRUPT = -10, -11
 EF_KEY_NONE = (1 << 63) - 1
@@ -149,6 +150,10 @@ _SIGS = {
     "ef_preprocess_rois": ([vp, vp, i64, i32, i32, i32, vp, i64, i32, i32, vp, u32], C.c_int),
     "ef_scan_prepare": ([vp, vp, i32, i32, i32, C.c_double], C.c_int),
     "ef_scan_frame": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, u32], C.c_int),
+    # reconstruction and distance from face space: added the same way, bound by symbol
+    "ef_recon_set": ([vp, vp, vp, i64, i32, u32], C.c_int),
+    "ef_reconstruct": ([vp, vp, i64, i32, vp, u32], C.c_int),
+    "ef_face_distance": ([vp, vp, i32, i64, vp, vp, vp, u32], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

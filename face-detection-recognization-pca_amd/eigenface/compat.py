@@ -410,6 +410,49 @@ def _folded(md):
     return mu, w
 
 
+def _recon_engine(md, device):
+    """Engine holding a model dict's projection and its way back.  ``face_model.pkl`` layout
+    (``pca`` + ``scaler``): the folded (mean, W) with R = V diag(sigma), weight 1/sigma;
+    ``models/*_pca_model.pkl`` layout (``eigenfaces`` (d, k) + ``mean_face``): R = eigenfaces^T."""
+    from .pca import reconstruction_operands
+
+    if "pca" in md:
+        mu, w = _folded(md)
+        comps, scale = md["pca"].components_, md["scaler"].scale_
+    else:
+        mu = md["mean_face"] if isinstance(md["mean_face"], np.ndarray) else np.asarray(md["mean_face"])
+        w = md["eigenfaces"] if isinstance(md["eigenfaces"], np.ndarray) else np.asarray(md["eigenfaces"])
+        comps, scale = np.asarray(w).T, None
+    eng = _model_engine(mu, w, device)
+    if eng.recon_owner is not eng.model_owner:  # the resident model is this dict's; is its way back?
+        R, s = reconstruction_operands(comps, scale)
+        eng.set_reconstruction(R, s, owner=eng.model_owner)
+    return eng
+
+
+def _pixel_rows(pixels):
+    p = np.asarray(pixels)
+    p = p if p.dtype == np.uint8 else p.astype(np.float32)
+    return p.reshape(1, -1) if p.ndim == 1 else p
+
+
+def reconstruct_faces(pixels, model_data, dtype="uint8", device=0):
+    """The faces ``pixels`` (b, d) as the model's eigenfaces explain them: project, then
+    scaler.inverse_transform(pca.inverse_transform(.)) (``face_model.pkl`` dicts) or
+    mean_face + f . eigenfaces^T (``models/*_pca_model.pkl`` dicts), on the GPU.  dtype
+    "uint8" (clamped, rounded half to even: an image to show or save) or "float32"."""
+    eng = _recon_engine(model_data, device)
+    return eng.reconstruct(eng.project(_pixel_rows(pixels)), dtype)
+
+
+def face_space_distance(pixels, model_data, device=0):
+    """Squared distance from face space of ``pixels`` (b, d) for either model-dict layout:
+    the energy of each face its eigenfaces do not explain (Turk-Pentland's face / non-face
+    measure), float64; ``face_model.pkl`` dicts measure it in the scaler's space."""
+    eng = _recon_engine(model_data, device)
+    return eng.face_distance(_pixel_rows(pixels)).astype(np.float64)
+
+
 def preprocess_faces(face_imgs, device=0):
     """Grey 64x64 rows of a batch of face crops (scan-template-v4.py:257-263): one GPU
     launch (ef_preprocess) for the whole batch."""

@@ -139,6 +139,7 @@ class Engine:
         # Callers that cache "my model is resident" (EigenfacePCA, recognize_face_with_model)
         # compare their token with these instead of assuming nobody else replaced it.
         self.model_owner = None
+        self.recon_owner = None  # None: no reconstruction state (set_reconstruction)
         self.gallery_owner = None
         self.bank_owner = None  # the ModelBank whose slots the bank holds, if one filled it
         self._bank_k = []
@@ -489,6 +490,7 @@ class Engine:
         if precision == "bf16":
             flags |= N.EF_MODEL_BF16
         self.model_owner = None  # a failed upload leaves no valid owner
+        self.recon_owner = None  # ef_model_set drops the reconstruction state
         self._chk(self._lib.ef_model_set(self._h, mp, wp, d, k, flags))
         if flags:
             self.synchronize()
@@ -533,6 +535,106 @@ class Engine:
         f = np.empty((b, self.model_k), dtype=np.float32)
         self._chk(self._lib.ef_project(self._h, pp, dtype, b, f.ctypes.data, 0))
         return f
+
+    # ------------------------------------------------------------- reconstruction
+    def set_reconstruction(self, R, weight=None, owner=None):
+        """The way back for the resident model: x^ = mean + f . R with R (k x d) and an optional
+        per-pixel weight (d,) of the residual (ef_recon_set).  manual_pca models: R =
+        eigenfaces^T; standardised models (W = diag(1/sigma) V^T): R = V diag(sigma), weight =
+        1/sigma.  A later set_model drops it."""
+        if self.model_k is None:
+            raise RuntimeError("no model: call set_model first")
+        if _is_dev(R):
+            import torch
+            r, rp = _dev(R, torch.float32)
+            w, wp = _dev(weight, torch.float32) if weight is not None else (None, None)
+            flags = N.EF_MEM_DEVICE
+        else:
+            r, rp = _host(R, np.float32)
+            w, wp = _host(weight, np.float32) if weight is not None else (None, None)
+            flags = 0
+        if r.ndim != 2:
+            raise ValueError("R must be 2-D (k, d)")
+        k, d = (int(v) for v in r.shape)
+        if w is not None and tuple(w.shape) != (d,):
+            raise ValueError("weight and R disagree on d")
+        self.recon_owner = None  # a failed upload leaves none
+        self._chk(self._lib.ef_recon_set(self._h, rp, wp, d, k, flags))
+        self.recon_owner = owner if owner is not None else object()
+
+    def reconstruct(self, F, dtype="float32", out=None):
+        """x^ = mean + F . R for features F (b, k): float32, or uint8 (clamped to [0, 255], then
+        rounded half to even) (ef_reconstruct).  Device F gives a device result (``out``
+        optional); host F a NumPy array."""
+        if self.model_k is None:
+            raise RuntimeError("no model: call set_model first")
+        if dtype not in ("float32", "uint8"):
+            raise ValueError("dtype must be 'float32' or 'uint8'")
+        code = N.EF_U8 if dtype == "uint8" else N.EF_F32
+        if _is_dev(F):
+            import torch
+            f, fp = _dev(F, torch.float32)
+            if f.ndim != 2 or f.shape[1] != self.model_k:
+                raise ValueError(f"F must be (b, {self.model_k}), got {tuple(f.shape)}")
+            b = f.shape[0]
+            tdt = torch.uint8 if dtype == "uint8" else torch.float32
+            if out is None:
+                out = torch.empty((b, self.model_d), dtype=tdt, device=f.device)
+            self._dev_out(out, (b, self.model_d), tdt, "out")
+            with self._torch_order(f, out):
+                self._chk(self._lib.ef_reconstruct(self._h, fp, b, code, out.data_ptr(), N.EF_MEM_DEVICE))
+            return out
+        f, fp = _host(F, np.float32)
+        if f.ndim != 2 or f.shape[1] != self.model_k:
+            raise ValueError("F must be (b, k)")
+        b = f.shape[0]
+        ndt = np.uint8 if dtype == "uint8" else np.float32
+        if out is None:
+            out = np.empty((b, self.model_d), dtype=ndt)
+        elif not (isinstance(out, np.ndarray) and out.dtype == ndt and out.shape == (b, self.model_d)
+                  and out.flags.c_contiguous):
+            raise ValueError(f"out must be a contiguous {dtype} array of shape {(b, self.model_d)}")
+        self._chk(self._lib.ef_reconstruct(self._h, fp, b, code, out.ctypes.data, 0))
+        return out
+
+    def face_distance(self, P, return_energy=False, return_features=False, out=None):
+        """Squared distance from face space eps^2 = sum_j (s_j (p_j - x^_j))^2 of pixels P (b, d),
+        uint8 or float32 (ef_face_distance): projection, reduce and residual in one stream-ordered
+        sequence, x^ never written.  Returns eps^2 (b,) float32 and, when asked, the energy
+        sum_j (s_j (p_j - mean_j))^2 and the features (exactly ``project(P)``), in that order.
+        Device P gives device results; ``out`` is then an optional float32 tensor (b,) for eps^2."""
+        if self.model_k is None:
+            raise RuntimeError("no model: call set_model first")
+        if _is_dev(P):
+            import torch
+            p, pp, dtype = self._dev_pixels(P)
+            b = p.shape[0]
+            if out is None:
+                out = torch.empty((b,), dtype=torch.float32, device=p.device)
+            self._dev_out(out, (b,), torch.float32, "out")
+            en = torch.empty((b,), dtype=torch.float32, device=p.device) if return_energy else None
+            ft = torch.empty((b, self.model_k), dtype=torch.float32, device=p.device) if return_features else None
+            with self._torch_order(p, out, en, ft):
+                self._chk(self._lib.ef_face_distance(self._h, pp, dtype, b, out.data_ptr(),
+                                                     en.data_ptr() if en is not None else None,
+                                                     ft.data_ptr() if ft is not None else None, N.EF_MEM_DEVICE))
+        else:
+            if out is not None:
+                raise ValueError("out= is for device tensors")
+            p = np.asarray(P)
+            dtype = N.EF_U8 if p.dtype == np.uint8 else N.EF_F32
+            p, pp = _host(p, np.uint8 if dtype == N.EF_U8 else np.float32)
+            if p.ndim != 2 or p.shape[1] != self.model_d:
+                raise ValueError("P must be (b, d)")
+            b = p.shape[0]
+            out = np.empty((b,), dtype=np.float32)
+            en = np.empty((b,), dtype=np.float32) if return_energy else None
+            ft = np.empty((b, self.model_k), dtype=np.float32) if return_features else None
+            self._chk(self._lib.ef_face_distance(self._h, pp, dtype, b, out.ctypes.data,
+                                                 en.ctypes.data if en is not None else None,
+                                                 ft.ctypes.data if ft is not None else None, 0))
+        res = (out,) + ((en,) if return_energy else ()) + ((ft,) if return_features else ())
+        return res[0] if len(res) == 1 else res
 
     # --------------------------------------------------------------------- search
     def set_gallery(self, G, global_offset: int = 0, owner=None):
@@ -1169,7 +1271,8 @@ class Engine:
     def timing_get(self, kernel="search"):
         kid = {"search": N.EF_KERNEL_SEARCH, "project": N.EF_KERNEL_PROJECT, "tmatch": N.EF_KERNEL_TMATCH,
                "ingest": N.EF_KERNEL_INGEST, "haar": N.EF_KERNEL_HAAR, "jpeg": N.EF_KERNEL_JPEG,
-               "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST, "scan": N.EF_KERNEL_SCAN}[kernel]
+               "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST, "scan": N.EF_KERNEL_SCAN,
+               "recon": N.EF_KERNEL_RECON, "recon_reduce": N.EF_KERNEL_RECON_REDUCE}[kernel]
         ms = C.c_double(0)
         n = C.c_int64(0)
         self._chk(self._lib.ef_timing_get(self._h, kid, C.byref(ms), C.byref(n)))

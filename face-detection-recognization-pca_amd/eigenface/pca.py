@@ -114,6 +114,39 @@ class EigenfacePCA:
         if eng.model_owner is not self._model_token:
             eng.set_model(self._mu, self._W, owner=self._model_token)
 
+    def _ensure_recon(self, eng):
+        """The model and, next to it, the way back: R = components for raw pixels; with the
+        scaler W = diag(1/sigma) V^T, so R = V diag(sigma) and the residual is weighted by
+        1/sigma (measured in the scaler's space, where the components are orthonormal)."""
+        self._ensure_model(eng)
+        if eng.recon_owner is not self._model_token:
+            R, s = reconstruction_operands(self.components_, self.scaler_scale_ if self.standardize else None)
+            eng.set_reconstruction(R, s, owner=self._model_token)
+
+    def inverse_transform(self, F):
+        """mean + F . R on the GPU (fp32 MFMA), returned as float64: sklearn's
+        scaler.inverse_transform(pca.inverse_transform(F))."""
+        eng = get_engine(self.device)
+        self._ensure_recon(eng)
+        f = np.asarray(F, dtype=np.float32)
+        return eng.reconstruct(f.reshape(-1, self.n_components_)).astype(np.float64)
+
+    def reconstruct(self, X):
+        """inverse_transform(transform(X)): the faces as their eigenfaces explain them."""
+        return self.inverse_transform(self.transform(X))
+
+    def face_distance(self, X, squared=True):
+        """Distance from face space of pixels X (b, d): the energy of each face that the
+        eigenfaces do not explain, sum_j (s_j (x_j - x^_j))^2 (its root with squared=False);
+        with the scaler, measured in the scaler's space.  float64."""
+        eng = get_engine(self.device)
+        self._ensure_recon(eng)
+        x = np.asarray(X)
+        if x.dtype != np.uint8:
+            x = np.asarray(x, dtype=np.float32)
+        e2 = eng.face_distance(x).astype(np.float64)
+        return e2 if squared else np.sqrt(e2)
+
     def transform(self, X):
         """(p - mean) . W on the GPU (fp32 MFMA), returned as float64."""
         eng = get_engine(self.device)
@@ -169,6 +202,18 @@ class EigenfacePCA:
         if threshold is not None:
             idx = np.where(best >= threshold, idx, -1)
         return idx, best
+
+
+def reconstruction_operands(components, scale=None):
+    """(R (k, d) float32, weight (d,) float32 or None) of a model with ``components`` (k, d)
+    as rows and, for a standardised model, the scaler's ``scale`` (sigma; a zero counts as 1,
+    the scaler's own rule): R = V diag(sigma), weight = 1 / sigma."""
+    v = np.asarray(components, dtype=np.float64)
+    if scale is None:
+        return np.ascontiguousarray(v, dtype=np.float32), None
+    sg = np.asarray(scale, dtype=np.float64)
+    sg = np.where(sg == 0.0, 1.0, sg)
+    return np.ascontiguousarray(v * sg[None, :], dtype=np.float32), np.ascontiguousarray(1.0 / sg, dtype=np.float32)
 
 
 def save_gallery_cache(path, features):

@@ -70,6 +70,8 @@ extern "C" {
                                 EF_KERNEL_SEARCH (one launch each per frame, as in ef_bank_recognize), and their
                                 two event pairs are recorded inside the scan's span; EF_KERNEL_TMATCH and
                                 EF_KERNEL_INGEST do not count scans */
+#define EF_KERNEL_RECON 9   /* back-projection GEMM of ef_reconstruct / ef_face_distance with its epilogue */
+#define EF_KERNEL_RECON_REDUCE 10 /* ef_face_distance: the fixed-order sum of the pixel splits' partials */
 
 /* No-result sentinel in a key array (empty gallery). */
 #define EF_KEY_NONE INT64_MAX
@@ -180,6 +182,33 @@ int ef_fit_transform(ef_ctx* ctx, const uint8_t* X, int64_t n, int64_t d, const 
 int ef_model_set(ef_ctx* ctx, const float* mean, const float* W, int64_t d, int32_t k, uint32_t flags);
 /* P[b*d] pixels (EF_U8 or EF_F32) -> F[b*k] float32. */
 int ef_project(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, float* F, uint32_t flags);
+
+/* ----------------------------------------------- reconstruction, distance from face space
+ * The way back out of face space, for the resident model (mean, W):
+ *   x^   = mean + f . R                        reconstruction, b x d
+ *   eps2 = sum_j (s_j (p_j - x^_j))^2          squared distance from face space, per probe
+ *   E    = sum_j (s_j (p_j - mean_j))^2        total energy, per probe
+ * sklearn's scaler.inverse_transform(pca.inverse_transform(f)) and Turk-Pentland's face / non-face
+ * measure.  R[k*d] float32 row-major (k rows of d), weight[d] float32 or NULL (= 1).  manual_pca
+ * models: R = eigenfaces^T, no weight.  Standardised models (W = diag(1/sigma) V^T): R = V diag(sigma),
+ * weight = 1/sigma, so the residual is measured in the scaler's space, where the components are
+ * orthonormal.  eps2 is summed from the residual itself, never as E - |f|^2.
+ * Added after API v7 without a version bump: probe by symbol.
+ * ef_recon_set: EF_E_STATE without a model, EF_E_INVALID when d or k differ from the model's; a
+ *   failed call leaves no reconstruction state and the model untouched.  ef_model_set drops the
+ *   reconstruction state.  Synchronous on return.
+ * ef_reconstruct: F[b*k] float32 -> out[b*d] as EF_F32, or EF_U8 (clamped to [0, 255], then
+ *   rounded half to even: np.rint, OpenCV's saturate_cast<uchar>).
+ * ef_face_distance: P[b*d] pixels (EF_U8 or EF_F32) -> dffs2[b] = eps2 and, each optional,
+ *   energy[b] = E and F_out[b*k], the features exactly as ef_project returns them.  Projection,
+ *   its reduce and the residual are queued on the ctx's stream with nothing downloaded in
+ *   between; x^ is never written.  Works with the fp32 and the EF_MODEL_BF16 model (the
+ *   back-projection is fp32 either way).  The same inputs give the same bits on every call.
+ * Both: EF_E_STATE without reconstruction state; b = 0 is EF_OK. */
+int ef_recon_set(ef_ctx* ctx, const float* R, const float* weight, int64_t d, int32_t k, uint32_t flags);
+int ef_reconstruct(ef_ctx* ctx, const float* F, int64_t b, int32_t out_dtype, void* out, uint32_t flags);
+int ef_face_distance(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, float* dffs2, float* energy,
+                     float* F_out, uint32_t flags);
 
 /* ------------------------------------------------------------------ search
  * Gallery rows G[n*k] float32 (face_features / projected_data), kept resident; any
