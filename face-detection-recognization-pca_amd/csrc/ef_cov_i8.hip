@@ -10,9 +10,12 @@
 // integers.  S' runs on v_mfma_i32_32x32x32_i8 with int32 accumulators: a work item covers
 // at most kMaxSplitK samples (|x'x'| <= 2^14, 131008 * 2^14 < 2^31), so it ends with one
 // plain int32 store into its split's slab, and the finalize sums the slabs in int64/int128.
-// The only rounding of the whole covariance is the final int128 -> fp64 conversion and
-// division (<= 1 ulp), tighter than the fp64 GEMM the reference runs.  StandardScaler
-// scaling (train-v4.py:131) is applied afterwards as C_ij / (scale_i scale_j).
+// The only roundings of the whole covariance are the final int128 -> fp64 conversion of the
+// numerator and the division by the (exactly representable) denominator: two correctly
+// rounded operations, |C - exact| <= 2 * 2^-53 |exact| to first order, and bit-equal to the
+// same two operations on a host (tests/native/kernel_units.cpp, group cov) — tighter than
+// the fp64 GEMM the reference runs.  StandardScaler scaling (train-v4.py:131) is applied
+// afterwards as C_ij * (w_i w_j), w = 1 / scale: two more roundings.
 //
 // Operand layout in HBM: At = [kpad/64][dim][64] bytes ("K-blocked"): the 64 samples of one
 // K-stage for all dim rows are one contiguous dim*64-byte block, so a stage's 256-row panel
@@ -746,7 +749,8 @@ __global__ void slab_accumulate_kernel(const int* __restrict__ slabs, int nslab,
   }
 }
 
-// C from the exact integer pieces (one rounding); w = 1/scale or null.  One workgroup per
+// C from the exact integer pieces (two roundings: the numerator's conversion and the
+// division; two more with w); w = 1/scale or null.  One workgroup per
 // upper 64-block: the block and (off the diagonal) its mirror, the mirror through LDS so
 // both writes are row-contiguous.
 __global__ __launch_bounds__(256) void cov_finalize_kernel(const int* __restrict__ slabs, int nslab,

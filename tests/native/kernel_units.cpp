@@ -2,10 +2,10 @@
 // `kernel_units`, run by tests/test_gpu_kernel_units.py).  The program links the product
 // objects, creates one stream and calls the ef:: launchers of csrc/ef_linalg.hpp directly;
 // every case has a host reference of its own in plain loops (long double for real-valued
-// cases, int64 for integer ones).
+// cases, int64 / __int128 for integer ones).
 //
 //   kernel_units --list            groups and cases
-//   kernel_units <group> [case]    tall | s3 | cq | chol | jacobi  (GPU)
+//   kernel_units <group> [case]    tall | s3 | cq | chol | jacobi | cov | proj  (GPU)
 //   kernel_units --host            the references against their own bounds; no HIP call
 //
 // One line per case:  case=<id> worst=<measured/bound> rms=<...> PASS|FAIL   (exit 1 on any
@@ -65,6 +65,12 @@ struct Dev {  // device buffer with 256 bytes of slack
   void up(const std::vector<T>& v) const {
     HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   }
+  template <class T>
+  void up_at(size_t off, const std::vector<T>& v) const {  // the same, `off` bytes into the buffer
+    HIP(hipMemcpy(static_cast<char*>(p) + off, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  }
+  // every byte of the buffer = `byte`, in stream order (0x55: a dirty pool buffer; 0xff: NaN)
+  void fill(int byte) const { HIP(hipMemsetAsync(p, byte, bytes, g_stream)); }
   template <class T>
   void down(std::vector<T>& v) const {
     HIP(hipStreamSynchronize(g_stream));
@@ -162,6 +168,25 @@ static std::vector<int64_t> sample_rows(int64_t M) {
 }
 
 static const double kU64 = std::ldexp(1.0, -53), kU32 = std::ldexp(1.0, -24);
+
+// f(i) for every i in [0, n), handed out in blocks of `grain` to at most 16 threads
+static size_t pool_threads(size_t jobs) {
+  const unsigned hw = std::thread::hardware_concurrency();
+  return std::max<size_t>(1, std::min<size_t>(std::min<size_t>(16, hw ? hw : 4), jobs));
+}
+template <class F>
+static void parallel_for(size_t n, size_t grain, F f) {
+  std::atomic<size_t> next{0};
+  auto work = [&] {
+    for (size_t b; (b = next.fetch_add(grain)) < n;)
+      for (size_t i = b; i < std::min(n, b + grain); ++i) f(i);
+  };
+  const size_t nt = pool_threads((n + grain - 1) / grain);
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < nt; ++t) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+}
 static ld gamma_n(int n) { return (ld)n * kU64 / (1 - (ld)n * kU64); }
 
 // ------------------------------------------------------------------ tall
@@ -1225,9 +1250,853 @@ static void group_jacobi() {
   }
 }
 
+// ------------------------------------------------------------------ cov
+// The exact integer covariance / Gram (ef_cov_i8.hip), driven as ef_fit.hip drives it, with
+// the product's allocation sizes (At: dim * kpad + kSyrkPadBytes, order, slabs: no slack of
+// the test's own) and every work buffer dirty before each launch: At, slabs, S64, cvec, R
+// and Q2 hold 0x55 bytes, C holds NaN, so an entry read before it is written, or never
+// written, shows.
+//
+// Host reference: X' = X - 128 as int8 rows of the operand (dim x K), S' = X'^T X' (or
+// X' X'^T) in int64, the column sums c, R_i = X'_i . c in int64, Q = c . c in __int128, the
+// numerator  n S'_ij - c_i c_j  (Gram: n^2 S'_ij - n (R_i + R_j) + Q) in __int128 and the
+// quotient by n (n - 1) (Gram: n^2 (n - 1)) in long double.
+//
+// Per case:
+//   /pieces  bit-equal: At's bytes against [kb][row][kk] = x ^ 0x80 (zero past K) and the
+//            0x55 of the pad behind it; S1 = sum x, S2 = sum x^2 from the fused transpose
+//            (where it runs) and from launch_colstats; S64 of launch_cov_i8_cross on the
+//            upper 64-blocks (i / 64 <= j / 64; the rest is not part of the contract); the
+//            plan's expectations.
+//   /C       |C - ref| <= 2 u 1.01 |ref| (the conversion of the numerator and the division;
+//            den < 2^53 is exact, asserted), 4 u 1.01 |ref| with w (w_i w_j, and the
+//            product with it); ref = 0 gives exactly 0.  AND bit-equal to the host's
+//            (double)num / den [* (w_i * w_j)]: int128 -> fp64 and the division are both
+//            correctly rounded on either side.
+//   /whole   C[j][i] bit-equal to C[i][j] everywhere and no NaN left (the mirror write
+//            through LDS on ragged last blocks); launch_cov_from_cross fed the S64 and S1 of
+//            the same rows gives a C bit-equal to launch_cov_i8's.
+enum CovKind { CK_UNI, CK_EXT, CK_255 };  // uniform 0..255; only {0, 255} (x' = -128 / 127); all 255
+static const int64_t kDefaultSlabBytes = (int64_t)8 << 30;  // ef_internal.hpp opt_cov_slab_bytes
+
+struct CovCase {
+  const char* tag;
+  int64_t n, d;
+  bool gram;
+  CovKind kind;
+  bool stdz;
+  int slabs;  // slab budget in slabs of dim x dim int32; 0: the product's default (8 GiB)
+  int xoff;   // X starts this many bytes into its allocation
+  // what the plan must look like (-1 / false: anything)
+  int want_passes = -1, want_splits = -1;
+  int64_t want_kps = -1;
+  bool must_split = false, short_split = false, short_pass = false;
+  std::string id() const {
+    char b[160];
+    std::snprintf(b, sizeof b, "cov/%s/%s_n%lld_d%lld_%s%s", tag, gram ? "gram" : "cov", (long long)n, (long long)d,
+                  kind == CK_UNI ? "uni" : kind == CK_EXT ? "ext" : "255", stdz ? "_std" : "");
+    std::string s = b;
+    if (slabs) s += "_b" + std::to_string(slabs);
+    if (xoff) s += "_off" + std::to_string(xoff);
+    return s;
+  }
+  int64_t dim() const { return gram ? n : d; }
+  int64_t K() const { return gram ? d : n; }
+  int64_t budget() const { return slabs ? (int64_t)slabs * dim() * dim() * 4 : kDefaultSlabBytes; }
+};
+
+static std::vector<CovCase> cov_cases() {
+  std::vector<CovCase> v;
+  auto add = [&](const char* tag, int64_t n, int64_t d, bool gram, CovKind kind, bool stdz, int slabs,
+                 int xoff = 0) -> CovCase& {
+    v.push_back(CovCase{tag, n, d, gram, kind, stdz, slabs, xoff});
+    return v.back();
+  };
+  // tile geometry, covariance path: syrk_i8_kernel<256> below order 2048 (one tile, ragged,
+  // exact fit, one row / column into the next tile), syrk16_i8_kernel<6> on 256 x 384 tiles
+  // from 2048 (exact fit of the rows, two ragged rows, one column into a new 384 tile);
+  // d % 4 != 0 ends in cov_finalize_kernel, the others in cov_finalize4_kernel
+  for (int64_t d : {1, 3, 63, 64, 65, 255, 256, 257, 513}) {
+    add("tile", 100, d, false, CK_UNI, false, 0);
+    add("tile", 100, d, false, (d & 1) ? CK_EXT : CK_UNI, true, 1);
+  }
+  for (int64_t d : {2048, 2050, 2305}) add("tile", 130, d, false, CK_UNI, false, 0);
+  add("tile", 130, 2050, false, CK_EXT, true, 1);
+  add("tile", 130, 2048, false, CK_EXT, true, 0);
+  // K edges: one work item (budget one slab: splits = 1) walks 1..5 stages around the
+  // 4-stage LDS ring, zero padding past n inside the last stage; n = 1 has den = 0 on this
+  // path and checks the pieces only
+  for (int64_t n : {1, 63, 64, 65, 191, 192, 256, 257, 320}) {
+    add("kedge", n, 64, false, (n & 1) ? CK_EXT : CK_UNI, false, 1);
+    add("kedge", n, 2050, false, CK_UNI, false, 1);
+  }
+  add("kedge", 320, 64, false, CK_UNI, false, 0);  // the default budget: one stage per split
+  // split-K and passes
+  add("split", 448, 64, false, CK_UNI, false, 2).short_split = true;  // 7 stages as 4 + 3
+  add("split", 448, 64, false, CK_EXT, true, 3).short_split = true;   // 3 + 3 + 1
+  {
+    CovCase& c = add("split", 131073, 64, false, CK_UNI, false, 1);  // 2049 stages: 1025 + 1024
+    c.want_passes = 2, c.short_pass = true;
+  }
+  {
+    CovCase& c = add("split", 262100, 64, false, CK_UNI, false, 1);  // 4096 stages: 1366 + 1366 + 1364
+    c.want_passes = 3, c.short_pass = true;
+  }
+  {
+    CovCase& c = add("split", 262200, 8, false, CK_EXT, false, 2);  // 4097 stages: (1025 + 1024) + (1025 + 1023)
+    c.want_passes = 2, c.want_splits = 2, c.short_split = true, c.short_pass = true;
+  }
+  {
+    CovCase& c = add("split", 393100, 8, false, CK_UNI, true, 3);  // 6143 stages: 3 x 1024 + (1024 + 1024 + 1023)
+    c.want_passes = 2, c.want_splits = 3, c.short_pass = true;
+  }
+  // the int32 accumulator margin: 131008 samples in one work item, a column of pixels all 0
+  // (x' = -128: the diagonal entry is 131008 * 16384 = 2^31 - 1048576); one sample more
+  // must split
+  {
+    CovCase& c = add("margin", 131008, 64, false, CK_EXT, false, 1);
+    c.want_passes = 1, c.want_splits = 1, c.want_kps = 2047;
+    add("margin", 131009, 64, false, CK_EXT, false, 1).must_split = true;
+  }
+  // the finalize's int128 branch on the covariance path (n > 2^23) beside the int64 one;
+  // d = 6 reaches it in cov_finalize_kernel
+  add("wide", (int64_t)1 << 23, 8, false, CK_UNI, false, 0);
+  add("wide", ((int64_t)1 << 23) + 1, 8, false, CK_UNI, false, 0);
+  add("wide", ((int64_t)1 << 23) + 1, 8, false, CK_EXT, true, 0);
+  add("wide", ((int64_t)1 << 23) + 1, 6, false, CK_EXT, false, 0);
+  // Gram path (dim = n, K = d): shift_copy_kernel, rowdot_kernel, sumsq128_kernel and the
+  // finalize with gram = 1; all-255 pixels: the cancellation n^2 S' - n (R_i + R_j) + Q = 0
+  add("gram", 2, 1, true, CK_UNI, false, 0);
+  add("gram", 3, 64, true, CK_EXT, false, 0);
+  add("gram", 65, 100, true, CK_UNI, false, 0);
+  add("gram", 65, 100, true, CK_255, false, 0);
+  add("gram", 257, 130, true, CK_EXT, false, 1);
+  add("gram", 300, 4097, true, CK_UNI, false, 0);
+  add("gram", 300, 4097, true, CK_255, false, 2);
+  add("gram", 2050, 70, true, CK_UNI, false, 0);
+  // transposes: transpose_stats_lds_kernel (d % 256 == 0), transpose_stats_kernel (d % 4 ==
+  // 0), shift_transpose_kernel + launch_colstats (other d, or X not 4-byte aligned: a sliced
+  // device tensor); n = 8200 makes workgroups stride over more than one 64-row block
+  const int64_t tr[8][4] = {{256, 1, 17, 8200}, {512, 15, 64, 8200}, {4, 1, 17, 8200}, {252, 15, 200, 0},
+                            {260, 64, 8200, 0}, {50, 1, 17, 200},    {65, 15, 64, 8200}, {256, 200, 0, 0}};
+  for (auto& t : tr)
+    for (int a = 1; a < 4; ++a)
+      if (t[a]) add("transpose", t[a], t[0], false, (a & 1) ? CK_UNI : CK_EXT, false, 0);
+  for (int64_t n : {17, 200, 8200}) add("transpose", n, 256, false, CK_UNI, false, 0, 1);
+  return v;
+}
+
+struct CovData {
+  int64_t n, d, dim, K;
+  bool gram;
+  std::vector<uint8_t> X;  // n x d pixels
+  std::vector<int8_t> Xt;  // dim x K: the operand's rows, x - 128
+};
+
+static CovData cov_data(const CovCase& c) {
+  CovData D;
+  D.n = c.n, D.d = c.d, D.gram = c.gram, D.dim = c.dim(), D.K = c.K();
+  const int64_t n = c.n, d = c.d;
+  D.X.assign((size_t)n * d, 255);
+  if (c.kind != CK_255) {
+    Rng rng(77003ull * n + 131ull * d + (int)c.kind);
+    for (size_t e = 0; e < D.X.size(); e += 8) {
+      const uint64_t r = rng.next();
+      for (size_t b = 0; b < 8 && e + b < D.X.size(); ++b) {
+        const unsigned v = (unsigned)(r >> (8 * b)) & 255u;
+        D.X[e + b] = (uint8_t)(c.kind == CK_UNI ? v : ((v & 1) ? 255 : 0));
+      }
+    }
+    // one all-zero column and one constant column (StandardScaler scale 1, covariance 0)
+    for (int64_t i = 0; i < n; ++i) {
+      if (d >= 2) D.X[(size_t)i * d + d - 1] = 0;
+      if (d >= 3) D.X[(size_t)i * d + 1] = 200;
+    }
+  }
+  D.Xt.resize((size_t)D.dim * D.K);
+  if (c.gram) {
+    for (size_t e = 0; e < D.X.size(); ++e) D.Xt[e] = (int8_t)(D.X[e] ^ 0x80u);
+  } else {
+    parallel_for((size_t)d, 1, [&](size_t col) {
+      for (int64_t k = 0; k < n; ++k) D.Xt[col * (size_t)n + k] = (int8_t)(D.X[(size_t)k * d + col] ^ 0x80u);
+    });
+  }
+  return D;
+}
+
+// sum a_k b_k in int64 (int32 partial sums over 32768 terms: 2^15 2^14 < 2^31); skip: one
+// term left out (--host's sensitivity check)
+static int64_t dot_i8(const int8_t* a, const int8_t* b, int64_t K, int64_t skip = -1) {
+  int64_t s = 0;
+  for (int64_t k0 = 0; k0 < K; k0 += 32768) {
+    const int64_t k1 = std::min(K, k0 + 32768);
+    int32_t t = 0;
+    for (int64_t k = k0; k < k1; ++k) t += (int32_t)a[k] * (int32_t)b[k];
+    s += t;
+  }
+  if (skip >= 0 && skip < K) s -= (int64_t)a[skip] * (int64_t)b[skip];
+  return s;
+}
+
+struct CovRef {
+  std::vector<int64_t> rows;     // the rows of the dim x dim result the reference covers
+  std::vector<int64_t> S;        // [rows][dim]: S'
+  std::vector<uint64_t> s1, s2;  // [d]: sum x, sum x^2
+  std::vector<long long> c, R;   // [d]: s1 - 128 n; Gram: [n] X'_i . c
+  __int128 Q = 0;                // Gram: c . c
+};
+
+static CovRef cov_reference(const CovData& D, int64_t skip = -1) {
+  CovRef r;
+  r.rows = sample_rows(D.dim);
+  r.S.assign(r.rows.size() * (size_t)D.dim, 0);
+  parallel_for(r.S.size(), D.K > 4096 ? 1 : 64, [&](size_t e) {
+    const int64_t i = r.rows[e / (size_t)D.dim], j = (int64_t)(e % (size_t)D.dim);
+    r.S[e] = dot_i8(&D.Xt[(size_t)i * D.K], &D.Xt[(size_t)j * D.K], D.K, skip);
+  });
+  r.s1.assign((size_t)D.d, 0), r.s2.assign((size_t)D.d, 0), r.c.assign((size_t)D.d, 0);
+  for (int64_t i = 0; i < D.n; ++i)
+    for (int64_t k = 0; k < D.d; ++k) {
+      const uint64_t x = D.X[(size_t)i * D.d + k];
+      r.s1[k] += x;
+      r.s2[k] += x * x;
+    }
+  for (int64_t k = 0; k < D.d; ++k) r.c[k] = (long long)r.s1[k] - 128LL * D.n;
+  if (D.gram) {
+    r.R.assign((size_t)D.n, 0);
+    for (int64_t i = 0; i < D.n; ++i) {
+      long long s = 0;
+      for (int64_t k = 0; k < D.d; ++k) s += (long long)D.Xt[(size_t)i * D.d + k] * r.c[k];
+      r.R[i] = s;
+    }
+    for (int64_t k = 0; k < D.d; ++k) r.Q += (__int128)r.c[k] * r.c[k];
+  }
+  return r;
+}
+
+static __int128 cov_num(const CovData& D, const CovRef& r, size_t ri, int64_t j) {
+  const int64_t i = r.rows[ri];
+  const __int128 nn = D.n, s = r.S[ri * (size_t)D.dim + j];
+  if (D.gram) return nn * nn * s - nn * ((__int128)r.R[i] + r.R[j]) + r.Q;
+  return nn * s - (__int128)r.c[i] * r.c[j];
+}
+// the denominator; exact in fp64 below 2^53 (every case: asserted)
+static bool cov_den(const CovData& D, double& den, ld& den_ld) {
+  const __int128 nn = D.n, v = D.gram ? nn * nn * (nn - 1) : nn * (nn - 1);
+  den = D.gram ? (double)D.n * (double)D.n * (double)(D.n - 1) : (double)D.n * (double)(D.n - 1);
+  den_ld = (ld)v;
+  return v < ((__int128)1 << 53) && (__int128)den == v;
+}
+
+static std::string cov_plan_text(const ef::CovPlan& p) {
+  char b[200];
+  std::snprintf(b, sizeof b, "tj=%d njb=%d ntiles=%d splits=%d kps=%lld passes=%d nst=%lld spp=%lld", p.tj, p.njb,
+                p.ntiles, p.splits, (long long)p.kps, p.passes, (long long)p.nst, (long long)p.stages_per_pass);
+  return b;
+}
+// a split of some pass that has no stages ((splits - 1) kps >= the pass's stages)
+static bool cov_plan_has_empty_split(const ef::CovPlan& p) {
+  for (int pass = 0; pass < p.passes; ++pass) {
+    const int64_t st0 = (int64_t)pass * p.stages_per_pass, st1 = std::min(p.nst, st0 + p.stages_per_pass);
+    if ((int64_t)(p.splits - 1) * p.kps >= st1 - st0) return true;
+  }
+  return false;
+}
+// the plan against the case's expectations and the planner's own invariants (host only)
+static void cov_plan_check(const CovCase& c, const ef::CovPlan& p, Stat& st) {
+  st.exact(p.kps >= 1 && p.kps <= 2047);  // int32-exact work items
+  st.exact((int64_t)p.splits * p.kps >= p.stages_per_pass && (int64_t)p.passes * p.stages_per_pass >= p.nst);
+  st.exact(p.slab_elems == (int64_t)p.splits * c.dim() * c.dim() && p.slab_elems * 4 <= std::max(c.budget(), c.dim() * c.dim() * 4));
+  st.exact(p.njb == (c.dim() >= 2048 ? 6 : 0) && p.tj == (c.dim() >= 2048 ? 384 : 256));
+  if (c.want_passes >= 0) st.exact(p.passes == c.want_passes);
+  if (c.want_splits >= 0) st.exact(p.splits == c.want_splits);
+  if (c.want_kps >= 0) st.exact(p.kps == c.want_kps);
+  if (c.must_split) st.exact(p.splits * p.passes > 1);
+  if (c.short_split) st.exact(p.splits > 1 && p.stages_per_pass - (int64_t)(p.splits - 1) * p.kps < p.kps);
+  if (c.short_pass) st.exact(p.passes > 1 && p.nst - (int64_t)(p.passes - 1) * p.stages_per_pass < p.stages_per_pass);
+}
+
+static void cov_case(const CovCase& c) {
+  const std::string id = c.id();
+  if (g_list) { std::printf("%s\n", id.c_str()); return; }
+  if (!wanted(id)) return;
+  const CovData D = cov_data(c);
+  const CovRef r = cov_reference(D);
+  const int64_t n = c.n, d = c.d, dim = D.dim, K = D.K, kpad = ef::cov_i8_kpad(K);
+  const bool gram = c.gram;
+  // the product's allocations, byte for byte (ef_fit.hip)
+  Dev dX((size_t)n * d + c.xoff), dAt((size_t)dim * kpad + ef::kSyrkPadBytes, 0), dS1((size_t)d * 8), dS2((size_t)d * 8),
+      dS1b((size_t)d * 8), dS2b((size_t)d * 8);
+  dX.up_at(c.xoff, D.X);
+  const uint8_t* Xd = dX.as<uint8_t>() + c.xoff;
+  dAt.fill(0x55);
+  const bool fused = !gram && ef::cov_i8_fused_stats(Xd, d);
+  HIP(ef::launch_cov_i8_prep(g_stream, Xd, n, d, gram, dAt.as<uint8_t>(), fused ? dS1.as<unsigned long long>() : nullptr,
+                             fused ? dS2.as<unsigned long long>() : nullptr));
+  HIP(ef::launch_colstats(g_stream, Xd, n, d, dS1b.as<unsigned long long>(), dS2b.as<unsigned long long>()));
+  const unsigned long long* S1 = fused ? dS1.as<unsigned long long>() : dS1b.as<unsigned long long>();
+  const unsigned long long* S2 = fused ? dS2.as<unsigned long long>() : dS2b.as<unsigned long long>();
+
+  Stat sp;  // the integer pieces
+  {
+    std::vector<uint8_t> at(dAt.bytes);
+    dAt.down(at);
+    int64_t bad = 0;
+    for (int64_t kb = 0; kb < kpad / 64; ++kb)
+      for (int64_t row = 0; row < dim; ++row) {
+        const uint8_t* got = &at[((size_t)kb * dim + row) * 64];
+        for (int kk = 0; kk < 64; ++kk) {
+          const int64_t k = kb * 64 + kk;
+          bad += got[kk] != (k < K ? (uint8_t)D.Xt[(size_t)row * K + k] : (uint8_t)0);
+        }
+      }
+    for (size_t e = (size_t)dim * kpad; e < at.size(); ++e) bad += at[e] != 0x55;  // nothing written behind At
+    sp.n += (int64_t)at.size(), sp.mism += bad;
+    std::vector<uint64_t> a(d), b(d);
+    if (fused) {
+      dS1.down(a);
+      dS2.down(b);
+      for (int64_t k = 0; k < d; ++k) sp.exact(a[k] == r.s1[k] && b[k] == r.s2[k]);
+    }
+    dS1b.down(a);
+    dS2b.down(b);
+    for (int64_t k = 0; k < d; ++k) sp.exact(a[k] == r.s1[k] && b[k] == r.s2[k]);
+  }
+  std::vector<double> w;
+  Dev dMean((size_t)d * 8), dVar((size_t)d * 8), dScale((size_t)d * 8), dW((size_t)d * 8);
+  if (c.stdz) {
+    HIP(ef::launch_stats_finalize(g_stream, S1, S2, n, d, 1, dMean.as<double>(), dVar.as<double>(), dScale.as<double>(),
+                                  dW.as<double>()));
+    w.resize(d);
+    dW.down(w);
+    // a constant pixel gets scale 1; every other weight is 1 / sqrt(var) to its few roundings
+    // (the numerator's conversion, n^2, the division, the root, the reciprocal)
+    for (int64_t k = 0; k < d; ++k) {
+      const __int128 vn = (__int128)n * r.s2[k] - (__int128)r.s1[k] * r.s1[k];
+      if (vn == 0) sp.exact(w[k] == 1.0);
+      else sp.exact(fabsl((ld)w[k] - 1 / sqrtl((ld)vn / ((ld)n * n))) <= 5 * (ld)kU64 * w[k]);
+    }
+  }
+  const double* wd = c.stdz ? dW.as<double>() : nullptr;
+  const ef::CovPlan plan = ef::cov_i8_plan(dim, K, c.budget());
+  cov_plan_check(c, plan, sp);
+  sp.exact(!cov_plan_has_empty_split(plan));  // (none is reachable: --host enumerates the planner)
+  Dev dSl((size_t)plan.slab_elems * 4, 0), dS64x((size_t)dim * dim * 8), dS64((size_t)dim * dim * 8), dCv((size_t)d * 8),
+      dCv2((size_t)d * 8), dR((size_t)(gram ? n : 1) * 8), dQ2(16), dOrd((size_t)ef::cov_i8_order_bytes(dim), 0),
+      dC((size_t)dim * dim * 8), dC2((size_t)dim * dim * 8);
+  if (!gram) {
+    dSl.fill(0x55);
+    dS64x.fill(0x55);
+    HIP(ef::launch_cov_i8_cross(g_stream, plan, d, dAt.as<uint8_t>(), dSl.as<int>(), dS64x.as<long long>(), dOrd.p));
+    std::vector<long long> s64((size_t)dim * dim);
+    dS64x.down(s64);
+    for (size_t ri = 0; ri < r.rows.size(); ++ri)
+      for (int64_t j = 0; j < dim; ++j) {
+        const int64_t i = r.rows[ri];
+        if (i / 64 <= j / 64) sp.exact(s64[(size_t)i * dim + j] == r.S[ri * (size_t)dim + j]);
+      }
+  }
+  const char* prep = gram ? "shift_copy" : !fused ? "shift_transpose+colstats" : d % 256 == 0 ? "transpose_stats_lds"
+                                                                                               : "transpose_stats";
+  char path[160];
+  std::snprintf(path, sizeof path, " prep=%s finalize=%s/%s rows=%zu", prep, dim % 4 == 0 ? "finalize4" : "finalize",
+                gram ? "gram" : n > ((int64_t)1 << 23) ? "int128" : "narrow", r.rows.size());
+  report_exact(id + "/pieces", sp, cov_plan_text(plan) + path);
+  double den;
+  ld den_ld;
+  const bool den_exact = cov_den(D, den, den_ld);
+  if (n < 2) return;  // den = 0: the pieces only
+
+  dSl.fill(0x55);
+  dS64.fill(0x55);
+  dCv.fill(0x55);
+  dR.fill(0x55);
+  dQ2.fill(0x55);
+  dC.fill(0xff);
+  HIP(ef::launch_cov_i8(g_stream, plan, n, d, gram, S1, wd, dAt.as<uint8_t>(), dSl.as<int>(),
+                        plan.passes > 1 ? dS64.as<long long>() : nullptr, dCv.as<long long>(), dR.as<long long>(),
+                        dQ2.as<unsigned long long>(), dOrd.p, dC.as<double>()));
+  std::vector<double> C((size_t)dim * dim);
+  dC.down(C);
+  Stat sc;
+  sc.exact(den_exact);
+  int64_t biteq = 0, total = 0;
+  for (size_t ri = 0; ri < r.rows.size(); ++ri)
+    for (int64_t j = 0; j < dim; ++j) {
+      const int64_t i = r.rows[ri];
+      const __int128 num = cov_num(D, r, ri, j);
+      ld ref = (ld)num / den_ld;  // (|num| < 2^64: exact in long double)
+      double hv = (double)num / den;
+      if (c.stdz) ref = ref * (ld)w[i] * (ld)w[j], hv *= w[i] * w[j];
+      const double got = C[(size_t)i * dim + j];
+      sc.add(fabsl((ld)got - ref), (c.stdz ? 4 : 2) * (ld)kU64 * 1.01L * fabsl(ref));
+      const bool same = same_bits(got, hv) || (got == 0.0 && hv == 0.0);
+      sc.exact(same);
+      biteq += same, ++total;
+    }
+  report(id + "/C", sc, "biteq=" + std::to_string(biteq) + "/" + std::to_string(total));
+
+  Stat sw;
+  for (int64_t i = 0; i < dim; ++i)
+    for (int64_t j = i; j < dim; ++j) {
+      const double a = C[(size_t)i * dim + j], b = C[(size_t)j * dim + i];
+      sw.exact(a == a && same_bits(a, b));
+    }
+  if (!gram) {
+    dCv2.fill(0x55);
+    dC2.fill(0xff);
+    HIP(ef::launch_cov_from_cross(g_stream, dS64x.as<long long>(), S1, n, d, wd, dCv2.as<long long>(), dC2.as<double>()));
+    std::vector<double> C2((size_t)dim * dim);
+    dC2.down(C2);
+    sw.n += (int64_t)C.size();
+    sw.mism += std::memcmp(C.data(), C2.data(), C.size() * 8) ? 1 : 0;
+    if (sw.mism) {
+      int64_t m = 0;
+      for (size_t e = 0; e < C.size(); ++e) m += !same_bits(C[e], C2[e]);
+      std::printf("  from_cross: %lld entries differ\n", (long long)m);
+    }
+  }
+  report_exact(id + "/whole", sw);
+}
+
+static void group_cov() {
+  for (const CovCase& c : cov_cases()) cov_case(c);
+}
+
+// ------------------------------------------------------------------ proj
+// The training projection F = ((X - mu) w) . E on int8 digits (ef_proj_i8.hip), through
+// launch_proj_i8 with a dirty work buffer (0x55) and F pre-filled with NaN.
+//   E1  w = null, mu integer-valued (not all 128: cc_kernel counts), E column c = (integers
+//       -3..3) 2^e_c with e_c spread over -30..30 and one all-zero column (t_c = 0); pixels
+//       uniform with 0 and 255 present.  Every value, each Horner partial included, is an
+//       integer below 2^53 times a power of two: bit-equal to 2^e_c sum_k (x - mu) m.
+//   E2  all six digits: mu = 128 (cc = 0), at most 64 pixels per row differ from 128, all
+//       in {127, 129} and spread over every K stage, E = (random 46-bit integers) 2^e_c with
+//       the column's largest in [2^45, 2^46): V is that integer, |sum x' V| < 2^52, every
+//       Horner step is exact.  Bit-equal to 2^e_c sum_k x' V.
+//   R   real E (column maxima 2^-20..2^20), mu, and w with one entry 1.0; the componentwise
+//       bound of proj_bound below against the long-double product with E'' = fl(w E).
+enum ProjKind { PJ_E1, PJ_E2, PJ_R };
+static const char* kProjNames[3] = {"E1", "E2", "R"};
+
+struct ProjData {
+  int64_t n = 0, d = 0;
+  int kk = 0;
+  ProjKind kind = PJ_R;
+  std::vector<uint8_t> X;
+  std::vector<double> mu, w, E;  // w empty: null
+  std::vector<int64_t> M;        // E kinds: E[k][c] = M[k][c] 2^ec[c]
+  std::vector<int> ec;
+};
+
+static ProjData proj_data(int64_t n, int64_t d, int kk, ProjKind kind) {
+  ProjData p;
+  p.n = n, p.d = d, p.kk = kk, p.kind = kind;
+  Rng rng(900001ull * n + 7919ull * d + 31ull * kk + (int)kind);
+  p.X.resize((size_t)n * d);
+  p.mu.resize(d);
+  p.E.resize((size_t)d * kk);
+  p.ec.resize(kk);
+  for (int c = 0; c < kk; ++c) p.ec[c] = kk == 1 ? 7 : -30 + (60 * c) / (kk - 1);
+  if (kind == PJ_E2) {
+    for (auto& m : p.mu) m = 128.0;
+    std::fill(p.X.begin(), p.X.end(), (uint8_t)128);
+    const int64_t nstg = d / 64, cnt = d == 64 ? 40 : 64;
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t t = 0; t < cnt; ++t) {  // stage t % nstg (first and last included), a distinct offset in it
+        const int64_t stage = t % nstg, q = t / nstg;
+        const int64_t k = stage * 64 + (q * 7 + i * 13 + stage * 5) % 64;
+        p.X[(size_t)i * d + k] = (rng.next() & 1) ? 127 : 129;
+      }
+  } else {
+    for (auto& x : p.X) x = (uint8_t)(rng.next() & 255);
+    p.X[0] = 0;
+    p.X[p.X.size() - 1] = 255;
+    if (p.X.size() == 1) p.X[0] = 255;
+  }
+  if (kind == PJ_R) {
+    p.w.resize(d);
+    for (int64_t k = 0; k < d; ++k) {
+      p.mu[k] = 255.0 * rng.uni();
+      p.w[k] = 1.0 / (2.0 + 62.0 * rng.uni());
+    }
+    p.mu[d > 3 ? 3 : 0] = 200.0;  // a constant pixel: scale 1
+    p.w[d > 3 ? 3 : 0] = 1.0;
+    for (int c = 0; c < kk; ++c) p.ec[c] = kk == 1 ? -3 : -20 + (40 * c) / (kk - 1);
+    for (int64_t k = 0; k < d; ++k)
+      for (int c = 0; c < kk; ++c)  // magnitudes spread over 2^-12..1 of the column's scale
+        p.E[(size_t)k * kk + c] = std::ldexp(rng.real64(), p.ec[c] - rng.range(0, 12));
+    for (int c = 0; c < kk; ++c) p.E[(size_t)(c % d) * kk + c] = std::ldexp(rng.real64(), p.ec[c] + 6);
+    return p;
+  }
+  p.M.resize((size_t)d * kk);
+  if (kind == PJ_E1)
+    for (auto& m : p.mu) m = (double)rng.range(0, 255);
+  for (int64_t k = 0; k < d; ++k)
+    for (int c = 0; c < kk; ++c) {
+      int64_t m;
+      if (kind == PJ_E1) m = (kk >= 2 && c == 1) ? 0 : rng.range(-3, 3);
+      else {
+        m = (int64_t)(rng.next() >> 18);  // < 2^46
+        if (k == c % d) m |= (int64_t)1 << 45;
+        if (rng.next() & 1) m = -m;
+      }
+      p.M[(size_t)k * kk + c] = m;
+      p.E[(size_t)k * kk + c] = std::ldexp((double)m, p.ec[c]);
+    }
+  return p;
+}
+
+// The scheme's per-column state as ef_proj_i8.hip's header states it: E'' = fl(w E), t_c
+// with 2^t_c max|E''| in [2^45, 2^46) (0 for a zero column), V = rint(2^t_c E'') in six
+// signed base-256 digits, c = sum (128 - mu) w E in a plain fp64 loop.
+struct ProjCols {
+  std::vector<double> Epp, cc;
+  std::vector<int> t;
+  std::vector<int8_t> D;    // [6][kk][d]
+  std::vector<ld> ccabs;    // sum |128 - mu||E''|
+};
+static ProjCols proj_cols(const ProjData& p) {
+  ProjCols q;
+  const int64_t d = p.d;
+  const int kk = p.kk;
+  q.Epp.resize((size_t)d * kk);
+  q.cc.assign(kk, 0.0);
+  q.ccabs.assign(kk, 0);
+  q.t.resize(kk);
+  q.D.assign((size_t)6 * kk * d, 0);
+  for (int c = 0; c < kk; ++c) {
+    double mx = 0, s = 0;
+    for (int64_t k = 0; k < d; ++k) {
+      const double wv = p.w.empty() ? 1.0 : p.w[k], e = wv * p.E[(size_t)k * kk + c];
+      q.Epp[(size_t)k * kk + c] = e;
+      mx = std::fmax(mx, std::fabs(e));
+      s += (128.0 - p.mu[k]) * wv * p.E[(size_t)k * kk + c];
+      q.ccabs[c] += fabsl((ld)128 - p.mu[k]) * fabsl((ld)e);
+    }
+    q.cc[c] = s;
+    q.t[c] = oz_shift(mx);
+    for (int64_t k = 0; k < d; ++k) {
+      int32_t dg[6];
+      oz_digits_host(q.Epp[(size_t)k * kk + c], q.t[c], dg, 1);
+      for (int j = 0; j < 6; ++j) q.D[((size_t)j * kk + c) * d + k] = (int8_t)dg[j];
+    }
+  }
+  return q;
+}
+
+// One row of the emulated product: I_j = X' . D_j (exact), the fp64 Horner, ldexp, + c.
+// drop_digit / drop_stage leave one digit's product or one 64-pixel K stage out (--host's
+// sensitivity check).  T[c] = sum_j 256^j |I_j|, xabs = sum_k |x'|; *partials_exact: every
+// Horner partial equalled its exact integer value.
+static void proj_emulate_row(const ProjData& p, const ProjCols& q, int64_t i, int drop_digit, int drop_stage, double* F,
+                             ld* T, ld* xabs, bool* partials_exact) {
+  const int64_t d = p.d;
+  std::vector<int8_t> xs(d);
+  ld xa = 0;
+  for (int64_t k = 0; k < d; ++k) {
+    xs[k] = (int8_t)(p.X[(size_t)i * d + k] ^ 0x80u);
+    xa += std::abs((int)xs[k]);
+  }
+  if (xabs) *xabs = xa;
+  for (int c = 0; c < p.kk; ++c) {
+    int64_t I[6];
+    for (int j = 0; j < 6; ++j) {
+      const int8_t* dj = &q.D[((size_t)j * p.kk + c) * d];
+      I[j] = dot_i8(xs.data(), dj, d);
+      if (drop_stage >= 0) I[j] -= dot_i8(xs.data() + 64 * drop_stage, dj + 64 * drop_stage, 64);
+      if (j == drop_digit) I[j] = 0;
+    }
+    double v = (double)I[5];
+    __int128 ex = I[5];
+    ld t = ldexpl(fabsl((ld)I[5]), 40);
+    bool ok = true;
+    for (int j = 4; j >= 0; --j) {
+      v = std::fma(v, 256.0, (double)I[j]);
+      ex = ex * 256 + I[j];
+      ok = ok && (__int128)v == ex;
+      t += ldexpl(fabsl((ld)I[j]), 8 * j);
+    }
+    if (partials_exact) *partials_exact = *partials_exact && ok;
+    if (T) T[c] = t;
+    F[c] = std::ldexp(v, -q.t[c]) + q.cc[c];
+  }
+}
+
+// E kinds: 2^ec sum_k (x - mu) M in __int128, independent of the digit scheme; *fits: the
+// sum is below 2^53 (so the double holds it)
+static double proj_int_ref(const ProjData& p, int64_t i, int c, bool* fits) {
+  __int128 s = 0;
+  for (int64_t k = 0; k < p.d; ++k)
+    s += (__int128)((int64_t)p.X[(size_t)i * p.d + k] - (int64_t)p.mu[k]) * p.M[(size_t)k * p.kk + c];
+  const __int128 a = s < 0 ? -s : s;
+  if (fits) *fits = *fits && a < ((__int128)1 << 53);
+  return std::ldexp((double)(int64_t)s, p.ec[c]);
+}
+
+// R: long-double reference sum_k (x - mu) E'' and the bound, per entry:
+//   quantisation  |V - 2^t E''| <= 1/2 per entry:            2^-t sum_k |x'_k| / 2
+//   Horner        five fma, each rounding a partial no larger than T = sum_j 256^j |I_j|:
+//                                                             5 1.01 u 2^-t T
+//   cc            a length-d fp64 dot of (128 - mu) w E in some order (the products' own
+//                 roundings, fl(w E) against fl((128 - mu) w), inside the two extra units):
+//                                                             gamma_(d+2) sum |128 - mu||E''|
+//   final add                                                 u |F|
+// (ldexp is exact; the I_j are exact int32.)
+static ld proj_bound(const ProjData& p, const ProjCols& q, int c, ld T, ld xabs, double F) {
+  const ld s = ldexpl(1, -q.t[c]);
+  return 0.5L * s * xabs + 5 * 1.01L * (ld)kU64 * s * T + gamma_n((int)p.d + 2) * q.ccabs[c] + (ld)kU64 * fabsl((ld)F);
+}
+static ld proj_real_ref(const ProjData& p, const ProjCols& q, int64_t i, int c) {
+  ld s = 0;
+  for (int64_t k = 0; k < p.d; ++k) s += ((ld)p.X[(size_t)i * p.d + k] - (ld)p.mu[k]) * (ld)q.Epp[(size_t)k * p.kk + c];
+  return s;
+}
+
+// digit columns per tile, restating proj_layout's rule (ef_proj_i8.hip): 384 where it pads no
+// more than 256, 256 unless it pads > 15 % more than 128
+static int proj_tn(int kk) {
+  const int64_t p = 6 * (int64_t)kk, n128 = (p + 127) / 128 * 128, n256 = (p + 255) / 256 * 256,
+                n384 = (p + 383) / 384 * 384;
+  return n384 <= n256 ? 384 : n256 * 100 <= n128 * 115 ? 256 : 128;
+}
+
+struct ProjShape {
+  int64_t n, d;
+  int kk;
+};
+static std::vector<ProjShape> proj_shapes() {
+  // every (d, kk) pair of the lists once, n walking its list beside them (30 of the 150
+  // combinations), and the largest of everything
+  const int KK[6] = {1, 12, 40, 64, 65, 128}, DD[5] = {64, 128, 256, 320, 1024};
+  const int64_t NN[5] = {1, 255, 256, 257, 700};
+  std::vector<ProjShape> v;
+  for (int i = 0; i < 30; ++i) v.push_back({NN[(i + i / 5) % 5], DD[i % 5], KK[i % 6]});
+  v.push_back({700, 1024, 128});
+  v.push_back({257, 1024, 65});
+  v.push_back({1, 64, 1});
+  return v;
+}
+
+static void proj_case(const ProjShape& sh, ProjKind kind) {
+  char idb[96];
+  std::snprintf(idb, sizeof idb, "proj/%s/n%lld_d%lld_kk%d", kProjNames[kind], (long long)sh.n, (long long)sh.d, sh.kk);
+  if (g_list) { std::printf("%s\n", idb); return; }
+  if (!wanted(idb)) return;
+  const ProjData p = proj_data(sh.n, sh.d, sh.kk, kind);
+  const int64_t n = p.n, d = p.d;
+  const int kk = p.kk;
+  Dev dX((size_t)n * d), dMu((size_t)d * 8), dW((size_t)d * 8), dE((size_t)d * kk * 8), dF((size_t)n * kk * 8);
+  if (!ef::proj_i8_supported(dX.as<uint8_t>(), n, d, kk)) {
+    std::printf("case=%s worst=inf rms=0 FAIL (shape not supported)\n", idb);
+    ++g_fail;
+    return;
+  }
+  Dev dWork(ef::proj_i8_work_bytes(n, d, kk), 0);
+  dX.up(p.X);
+  dMu.up(p.mu);
+  if (!p.w.empty()) dW.up(p.w);
+  dE.up(p.E);
+  dWork.fill(0x55);
+  dF.fill(0xff);
+  HIP(ef::launch_proj_i8(g_stream, dX.as<uint8_t>(), n, d, dMu.as<double>(), p.w.empty() ? nullptr : dW.as<double>(),
+                         dE.as<double>(), kk, dWork.p, dF.as<double>()));
+  std::vector<double> F((size_t)n * kk);
+  dF.down(F);
+  char extra[64];
+  std::snprintf(extra, sizeof extra, "tn=%d tiles=%d stages=%lld", proj_tn(kk), (6 * kk + proj_tn(kk) - 1) / proj_tn(kk),
+                (long long)(d / 64));
+  if (kind != PJ_R) {
+    std::vector<char> same((size_t)n * kk);
+    std::atomic<bool> fits{true};
+    parallel_for((size_t)n, 1, [&](size_t i) {
+      bool f = true;
+      for (int c = 0; c < kk; ++c) {
+        const double want = proj_int_ref(p, (int64_t)i, c, &f), got = F[i * kk + c];
+        same[i * kk + c] = same_bits(got, want) || (got == 0.0 && want == 0.0);
+      }
+      if (!f) fits = false;
+    });
+    Stat st;
+    st.exact(fits);
+    for (char s : same) st.exact(s != 0);
+    report_exact(idb, st, extra);
+    return;
+  }
+  const ProjCols q = proj_cols(p);
+  std::vector<double> ratio((size_t)n * kk);
+  parallel_for((size_t)n, 1, [&](size_t i) {
+    std::vector<double> emu(kk);
+    std::vector<ld> T(kk);
+    ld xabs = 0;
+    proj_emulate_row(p, q, (int64_t)i, -1, -1, emu.data(), T.data(), &xabs, nullptr);
+    for (int c = 0; c < kk; ++c) {
+      const double got = F[i * kk + c];
+      const ld err = fabsl((ld)got - proj_real_ref(p, q, (int64_t)i, c)), b = proj_bound(p, q, c, T[c], xabs, got);
+      ratio[i * kk + c] = !(err == err) ? std::numeric_limits<double>::infinity()
+                          : b > 0       ? (double)(err / b)
+                                        : (err == 0 ? 0.0 : std::numeric_limits<double>::infinity());
+    }
+  });
+  Stat st;
+  for (double rt : ratio) st.add(rt, 1);
+  report(idb, st, extra);
+}
+
+// shapes launch_proj_i8 must not be given: the caller keeps the fp64 GEMM
+static Stat proj_refusals() {
+  Stat st;
+  const uint8_t* aligned = reinterpret_cast<const uint8_t*>((uintptr_t)1 << 20);
+  st.exact(ef::proj_i8_supported(aligned, 10, 128, 4));
+  st.exact(!ef::proj_i8_supported(aligned, 10, 100, 4));      // d % 64 != 0
+  st.exact(!ef::proj_i8_supported(aligned + 8, 10, 128, 4));  // X not 16-byte aligned
+  st.exact(!ef::proj_i8_supported(aligned, 10, 65600, 4));    // d > 65536
+  return st;
+}
+
+static void group_proj() {
+  for (const ProjShape& sh : proj_shapes())
+    for (ProjKind kind : {PJ_E1, PJ_E2, PJ_R}) proj_case(sh, kind);
+  if (g_list) { std::printf("proj/refusals\n"); return; }
+  if (wanted("proj/refusals")) report_exact("proj/refusals", proj_refusals());
+}
+
 // ------------------------------------------------------------------ host self-checks
 // The references against their own thresholds, before any kernel is involved.
+// cov and proj: the planner enumerated, the cases' plans, the integer references against
+// their representability conditions, the R bound on the host emulation of the scheme, and
+// the sensitivity of the E cases (one sample, one digit, one K stage dropped from the
+// emulated product must fail them).
+static void host_cov_proj() {
+  {  // every plan the planner can return for up to 300 stages and 1..64 slabs of budget
+    int64_t plans = 0, empty = 0, broken = 0;
+    std::string first;
+    for (int64_t dim : {8, 64, 513, 2050, 2305})
+      for (int64_t smax = 1; smax <= 64; ++smax)
+        for (int64_t nst = 1; nst <= 300; ++nst) {
+          const ef::CovPlan p = ef::cov_i8_plan(dim, nst * 64, smax * dim * dim * 4);
+          ++plans;
+          broken += !(p.nst == nst && p.kps >= 1 && p.kps <= 2047 && p.splits >= 1 && p.splits <= smax &&
+                      (int64_t)p.splits * p.kps >= p.stages_per_pass && (int64_t)p.passes * p.stages_per_pass >= nst);
+          if (cov_plan_has_empty_split(p)) {
+            if (!empty) first = "dim=" + std::to_string(dim) + " smax=" + std::to_string(smax) + " " + cov_plan_text(p);
+            ++empty;
+          }
+        }
+    Stat st;
+    st.n = plans, st.mism = broken;
+    report_exact("host/cov/plan_enumeration", st,
+                 empty ? "splits without stages: " + std::to_string(empty) + " plans, first " + first
+                       : "no reachable plan has a split without stages");
+    // (a plan with an empty split would need a case of its own in cov_cases(): the kernel
+    // must then store zeros to that slab)
+    Stat se;
+    se.exact(empty == 0);
+    report_exact("host/cov/no_empty_split_case_needed", se);
+  }
+  {  // the cases' plans (256 CUs assumed where no device answers)
+    Stat st;
+    for (const CovCase& c : cov_cases()) {
+      const ef::CovPlan p = ef::cov_i8_plan(c.dim(), c.K(), c.budget());
+      const int64_t before = st.mism;
+      cov_plan_check(c, p, st);
+      st.exact(!cov_plan_has_empty_split(p));
+      if (st.mism != before) std::printf("  plan of %s: %s\n", c.id().c_str(), cov_plan_text(p).c_str());
+    }
+    report_exact("host/cov/case_plans", st);
+  }
+  {  // the reference's pieces against a second, plain evaluation; one sample dropped shows
+    CovCase cc{"host", 100, 5, false, CK_UNI, false, 0, 0}, cg{"host", 7, 130, true, CK_EXT, false, 0, 0};
+    for (const CovCase& c : {cc, cg}) {
+      const CovData D = cov_data(c);
+      const CovRef r = cov_reference(D), rd = cov_reference(D, 37);
+      double den;
+      ld den_ld;
+      Stat st, sd;
+      st.exact(cov_den(D, den, den_ld));
+      int64_t differ = 0;
+      for (size_t ri = 0; ri < r.rows.size(); ++ri)
+        for (int64_t j = 0; j < D.dim; ++j) {
+          // C_ij from centred long-double data: (1 / (n - 1)) sum (x_i - mean_i)(x_j - mean_j)
+          const int64_t i = r.rows[ri];
+          ld s = 0;
+          if (c.gram) {
+            for (int64_t k = 0; k < D.d; ++k) {
+              const ld mk = (ld)r.s1[k] / D.n;
+              s += ((ld)D.X[(size_t)i * D.d + k] - mk) * ((ld)D.X[(size_t)j * D.d + k] - mk);
+            }
+          } else {
+            const ld mi = (ld)r.s1[i] / D.n, mj = (ld)r.s1[j] / D.n;
+            for (int64_t k = 0; k < D.n; ++k) s += ((ld)D.X[(size_t)k * D.d + i] - mi) * ((ld)D.X[(size_t)k * D.d + j] - mj);
+          }
+          s /= (D.n - 1);
+          const ld ref = (ld)cov_num(D, r, ri, j) / den_ld;
+          st.add(fabsl(ref - s), 1e-15L * (fabsl(s) + 1));
+          const double a = (double)cov_num(D, r, ri, j) / den, b = (double)cov_num(D, rd, ri, j) / den;
+          differ += !same_bits(a, b);
+        }
+      report(std::string("host/cov/reference_") + (c.gram ? "gram" : "cov"), st);
+      sd.exact(differ > 0);  // the E check (bit-equal C) sees one dropped sample
+      report_exact(std::string("host/cov/sensitivity_sample_") + (c.gram ? "gram" : "cov"), sd,
+                   std::to_string(differ) + " entries move");
+    }
+  }
+  for (const ProjShape& sh : {ProjShape{3, 320, 12}, ProjShape{2, 64, 65}, ProjShape{2, 1024, 5}}) {
+    char tail[64];
+    std::snprintf(tail, sizeof tail, "n%lld_d%lld_kk%d", (long long)sh.n, (long long)sh.d, sh.kk);
+    for (ProjKind kind : {PJ_E1, PJ_E2}) {
+      const ProjData p = proj_data(sh.n, sh.d, sh.kk, kind);
+      const ProjCols q = proj_cols(p);
+      const int nstg = (int)(sh.d / 64);
+      Stat st, sd;
+      std::vector<double> F(sh.kk), G(sh.kk);
+      bool fits = true, partials = true, digits_used = true;
+      int64_t stage_seen = 0, digit_seen[6] = {};
+      for (int64_t i = 0; i < sh.n; ++i) {
+        proj_emulate_row(p, q, i, -1, -1, F.data(), nullptr, nullptr, &partials);
+        for (int c = 0; c < sh.kk; ++c) st.exact(same_bits(F[c], proj_int_ref(p, i, c, &fits)) || (F[c] == 0 && proj_int_ref(p, i, c, nullptr) == 0));
+        for (int s : {0, nstg - 1}) {  // one K stage dropped: first and last
+          proj_emulate_row(p, q, i, -1, s, G.data(), nullptr, nullptr, nullptr);
+          for (int c = 0; c < sh.kk; ++c) stage_seen += !same_bits(F[c], G[c]);
+        }
+        for (int j = 0; j < 6; ++j) {  // one digit's product dropped
+          proj_emulate_row(p, q, i, j, -1, G.data(), nullptr, nullptr, nullptr);
+          for (int c = 0; c < sh.kk; ++c) digit_seen[j] += !same_bits(F[c], G[c]);
+        }
+      }
+      for (int j = 0; j < 6; ++j) digits_used = digits_used && digit_seen[j] > 0;
+      st.exact(fits);      // |sum (x - mu) M| < 2^53
+      st.exact(partials);  // every Horner partial is its exact integer
+      report_exact(std::string("host/proj/") + kProjNames[kind] + "_representable_" + tail, st);
+      sd.exact(stage_seen > 0);
+      if (kind == PJ_E2) sd.exact(digits_used);  // E1 has the top digit only: E2 carries all six
+      else sd.exact(digit_seen[5] > 0);
+      report_exact(std::string("host/proj/") + kProjNames[kind] + "_sensitivity_" + tail, sd,
+                   "entries moved by a dropped stage: " + std::to_string(stage_seen) + ", by digit 0..5: " +
+                       std::to_string(digit_seen[0]) + " " + std::to_string(digit_seen[1]) + " " +
+                       std::to_string(digit_seen[2]) + " " + std::to_string(digit_seen[3]) + " " +
+                       std::to_string(digit_seen[4]) + " " + std::to_string(digit_seen[5]));
+    }
+    {  // R: the emulation inside the bound
+      const ProjData p = proj_data(sh.n, sh.d, sh.kk, PJ_R);
+      const ProjCols q = proj_cols(p);
+      Stat st;
+      std::vector<double> F(sh.kk);
+      std::vector<ld> T(sh.kk);
+      for (int64_t i = 0; i < sh.n; ++i) {
+        ld xabs = 0;
+        proj_emulate_row(p, q, i, -1, -1, F.data(), T.data(), &xabs, nullptr);
+        for (int c = 0; c < sh.kk; ++c)
+          st.add(fabsl((ld)F[c] - proj_real_ref(p, q, i, c)), proj_bound(p, q, c, T[c], xabs, F[c]));
+      }
+      report(std::string("host/proj/R_emulation_") + tail, st);
+    }
+  }
+  report_exact("host/proj/refusals", proj_refusals());
+}
+
 static void group_host() {
+  host_cov_proj();
   for (int med = 0; med < 2; ++med) {  // the product's pair enumeration is the stated pair set, each pair once
     int seen[6][6] = {};
     for (int p = 0; p < ef::oz_pairs(med != 0); ++p) {
@@ -1322,12 +2191,14 @@ int main(int argc, char** argv) {
   g_only = argc > 2 ? argv[2] : nullptr;
   if (g == "--list") {
     g_list = true;
-    std::printf("groups: tall s3 cq chol jacobi (and --host)\n");
+    std::printf("groups: tall s3 cq chol jacobi cov proj (and --host)\n");
     group_tall();
     group_s3();
     group_cq();
     group_chol();
     group_jacobi();
+    group_cov();
+    group_proj();
     return 0;
   }
   if (g == "--host") {
@@ -1336,9 +2207,9 @@ int main(int argc, char** argv) {
     return g_fail ? 1 : 0;
   }
   void (*fn)() = g == "tall" ? group_tall : g == "s3" ? group_s3 : g == "cq" ? group_cq : g == "chol" ? group_chol
-                 : g == "jacobi" ? group_jacobi : nullptr;
+                 : g == "jacobi" ? group_jacobi : g == "cov" ? group_cov : g == "proj" ? group_proj : nullptr;
   if (!fn) {
-    std::printf("usage: kernel_units <tall|s3|cq|chol|jacobi> [case] | --list | --host\n");
+    std::printf("usage: kernel_units <tall|s3|cq|chol|jacobi|cov|proj> [case] | --list | --host\n");
     return 64;
   }
   HIP(hipSetDevice(0));

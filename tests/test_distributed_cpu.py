@@ -13,6 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import PKG, ROOT
+from shard_util import shard_pieces  # ef_fit_shard_stats' pieces in numpy, shared with the GPU test
 
 
 def _free_port():
@@ -326,13 +327,6 @@ def test_merge_mode_is_checked():
 
 
 # ------------------------------------------------------------- sample-sharded fit
-def _np_pieces(x):
-    """The exact integer pieces of include/eigenface.h ef_fit_shard_stats, in numpy."""
-    xi = np.asarray(x, np.int64)
-    xs = xi - 128
-    return xi.sum(0), (xi * xi).sum(0), xs.T @ xs
-
-
 def _np_fit_from_pieces(s1, s2, cr, n, k, standardize):
     """ef_fit_from_stats's arithmetic restated (the covariance from exact integers,
     oracle.top_eigh): what the sum over ranks must reproduce."""
@@ -365,7 +359,7 @@ def _fit_worker(rank, world, port, x, k, standardize, out):
     def transform(rows, res, stdz):
         z = (np.asarray(rows, np.float64) - res.mean) / res.scale
         return z @ res.components.T
-    res = sharded_fit(None, xl, k, standardize, stats_fn=_np_pieces, fit_fn=_np_fit_from_pieces,
+    res = sharded_fit(None, xl, k, standardize, stats_fn=shard_pieces, fit_fn=_np_fit_from_pieces,
                       transform_fn=transform)
     out[rank] = (res.eigenvalues.copy(), res.components.copy(), res.projection.copy(), res.mean.copy())
     dist.destroy_process_group()
@@ -381,7 +375,7 @@ def test_sharded_fit_pieces_allreduce(world):
     from oracle import eigenface_oracle as orc
     x, _ = orc.synth_faces(401, 8, r=20, seed=world)  # n = 401 >= d = 64
     k = 10
-    ref = _np_fit_from_pieces(*_np_pieces(x), len(x), k, True)
+    ref = _np_fit_from_pieces(*shard_pieces(x), len(x), k, True)
     o = orc.pca_cov_fit(x, k, standardize=True)
     np.testing.assert_allclose(ref.eigenvalues, o["explained_variance_"], rtol=1e-9)
     mgr = mp.Manager()

@@ -3,7 +3,9 @@
 tests/native/kernel_units.cpp links the product objects (`make kernel_units`) and calls the
 internal launchers of csrc/ef_linalg.hpp directly: the tall fp64 / fp32 GEMMs and transposes,
 the split-bf16 coarse product, the int8 digit-split product in its full and medium forms, the
-Cholesky factorisation and triangular inverse of CholQR, and both Jacobi solvers.  Each group
+Cholesky factorisation and triangular inverse of CholQR, both Jacobi solvers, the exact int8
+covariance / Gram with its transposes and finalize (against __int128 references) and the int8
+digit training projection.  Each group
 runs as a child process that prints one line per case and exits non-zero on any FAIL; exact
 (small-integer) cases must be bit-equal, rounding cases stay inside a bound written out in
 the program (DESIGN.md "Kernel-level numerics" lists them with the measured ratios).
@@ -54,7 +56,7 @@ def _run(exe, arg):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("group", ["tall", "s3", "cq", "chol", "jacobi"])
+@pytest.mark.parametrize("group", ["tall", "s3", "cq", "chol", "jacobi", "cov", "proj"])
 def test_kernel_group(kernel_units, group):
     out = _run(kernel_units, group)
     assert f"kernel_units {group}: ok" in out
