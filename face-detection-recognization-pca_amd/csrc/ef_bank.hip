@@ -11,10 +11,14 @@
 //   bank_search_kernel    every gallery row scored in fp64 with score64, two passes: the minimum
 //                         per (probe, slot), then the lowest row inside the tie window
 //   bank_merge_kernel     the row slices' answers -> keys and match records
-//   bank_best_kernel      the reference's best-over-models walk per probe
+//   bank_best_kernel      the reference's best-over-models walk per probe; with a face gate it
+//                         skips the slots whose distance from face space exceeds the bound
+// The distance from face space per slot (ef_bank_face_distance, the gated calls) is the grouped
+// residual of ef_bank_recon.hip on the feature blocks bank_reduce_kernel leaves.
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "ef_project_tile.hpp"
@@ -274,8 +278,12 @@ __global__ void bank_merge_kernel(const BankSlotDev* __restrict__ tab, int n_slo
 
 // scan-template-v4.py:293-309 on the decoded fp32 scores: start from 0.0 (cosine similarity) or
 // -inf (negated L2 distance), slots in order, a slot wins only with a strictly greater value.
+// GATED: slot m is skipped for probe p when dffs2[p][m] > bound is true (false for NaN), bound =
+// gate[m], or fl(gate[m] * energy[p][m]) when relative.
+template <bool GATED>
 __global__ void bank_best_kernel(const long long* __restrict__ keys, int n_slots, int64_t b, int metric,
-                                 int* __restrict__ best_slot) {
+                                 const float* __restrict__ gate, int relative, const float* __restrict__ dffs2,
+                                 const float* __restrict__ energy, int* __restrict__ best_slot) {
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= b) return;
   float best = metric == EF_METRIC_L2 ? -__builtin_inff() : 0.0f;
@@ -283,6 +291,10 @@ __global__ void bank_best_kernel(const long long* __restrict__ keys, int n_slots
   for (int m = 0; m < n_slots; ++m) {
     const long long key = keys[p * n_slots + m];
     if (key == LLONG_MAX) continue;
+    if constexpr (GATED) {
+      const float bound = relative ? __fmul_rn(gate[m], energy[p * n_slots + m]) : gate[m];
+      if (dffs2[p * n_slots + m] > bound) continue;
+    }
     const float val = -key_value(key);  // the key holds the distance, or minus the similarity
     if (val > best) {
       best = val;
@@ -297,8 +309,9 @@ static int bank_tables(ef_ctx* c) {
   if (bk.tables_valid) return EF_OK;
   std::vector<BankProjItem> items;
   std::vector<BankSlotDev> tab;
+  std::vector<BankReconDev> rtab;
   int64_t kp_off = 0, k_off = 0, pcol = 0, slice_off = 0;
-  int lds_bytes = 0, kp_max = 0;
+  int lds_bytes = 0, kp_max = 0, recon_rk = 32;
   for (const BankSlot& slot : bk.slots) {
     const Gallery& s = slot.g;
     BankSlotDev t{};
@@ -320,6 +333,10 @@ static int bank_tables(ef_ctx* c) {
       items.push_back(BankProjItem{static_cast<const float*>(slot.mean.p), static_cast<const float*>(slot.W.p), slot.kpw, col,
                                    pcol + col});
     tab.push_back(t);
+    rtab.push_back(BankReconDev{slot.recon ? static_cast<const float*>(slot.recon_R.p) : nullptr,
+                                static_cast<const float*>(slot.mean.p), static_cast<const float*>(slot.recon_w.p), s.kp,
+                                kp_off});
+    if (s.kp == 16) recon_rk = 16;
     kp_off += s.kp;
     k_off += s.k;
     pcol += slot.kpw;
@@ -327,13 +344,17 @@ static int bank_tables(ef_ctx* c) {
   }
   EF_TRY(ensure(c, bk.proj_items, items.size() * sizeof(BankProjItem)));
   EF_TRY(ensure(c, bk.slot_tab, tab.size() * sizeof(BankSlotDev)));
+  EF_TRY(ensure(c, bk.recon_tab, rtab.size() * sizeof(BankReconDev)));
   // the stream may still read the old tables: the copies are ordered on it, and waited for
   // because they read these host vectors
   EF_HIP(c, hipMemcpyAsync(bk.proj_items.p, items.data(), items.size() * sizeof(BankProjItem), hipMemcpyHostToDevice,
                            c->stream), "bank tables");
   EF_HIP(c, hipMemcpyAsync(bk.slot_tab.p, tab.data(), tab.size() * sizeof(BankSlotDev), hipMemcpyHostToDevice,
                            c->stream), "bank tables");
+  EF_HIP(c, hipMemcpyAsync(bk.recon_tab.p, rtab.data(), rtab.size() * sizeof(BankReconDev), hipMemcpyHostToDevice,
+                           c->stream), "bank tables");
   EF_HIP(c, hipStreamSynchronize(c->stream), "bank tables");
+  bk.recon_rk = recon_rk;
   bk.total_slices = slice_off;
   bk.search_lds = lds_bytes;
   bk.kp_max = kp_max;
@@ -375,12 +396,9 @@ static BankWs carve_bank_ws(Carve& cv, size_t entries, size_t scales) {
   return BankWs{cv.take<double>(entries), cv.take<double>(entries), cv.take<int>(entries), cv.take<double>(scales)};
 }
 
-// The launches of one recognise call on device pointers (ef_internal.hpp): ef_bank_recognize
-// after its staging, and ef_scan_frame on the rows its ROI kernel wrote.
-int bank_recognize_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, int metric, long long* kdev, ef_match* mdev,
-                       int* sdev, float* fdev) {
+// The grouped projection and its reduce: the bank's feature blocks bk.q (and fdev) of b probes.
+static int bank_project_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, float* fdev) {
   Bank& bk = c->bank;
-  EF_TRY(bank_tables(c));
   const int64_t M = (int64_t)bk.slots.size();
   const int64_t bpad = round_up(b, BM);
   const int64_t coltiles = bk.total_kpw / 128;
@@ -406,6 +424,43 @@ int bank_recognize_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, int me
                        part, ns, b, bpad, bk.total_kpw, bk.total_k, q, fdev);
     EF_HIP(c, hipGetLastError(), "bank reduce");
   }
+  return EF_OK;
+}
+
+// The grouped residual and its reduce on the feature blocks bank_project_dev left: dffs2[b][M]
+// and (optional) energy[b][M].  The caller has checked that every slot has its R.
+static int bank_residual_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, float* dffs2, float* energy) {
+  Bank& bk = c->bank;
+  const int M = (int)bk.slots.size();
+  const int64_t bpad = round_up(b, BM);
+  const BankReconPlan pl = bank_recon_plan(b, bk.d, M);
+  EF_TRY(ensure(c, bk.recon_part, (size_t)pl.scratch_bytes));
+  float* part = static_cast<float*>(bk.recon_part.p);
+  TimerEvt t;
+  timer_begin(c, EF_KERNEL_RECON, &t);
+  EF_HIP(c,
+         launch_bank_recon(c->stream, static_cast<const BankReconDev*>(bk.recon_tab.p), M, bk.recon_rk, p_dtype,
+                           static_cast<const float*>(bk.q.p), Pd, b, bpad, bk.d, part, pl),
+         "bank residual kernel");
+  timer_end(c, &t);
+  timer_begin(c, EF_KERNEL_RECON_REDUCE, &t);
+  EF_HIP(c, launch_bank_recon_reduce(c->stream, part, pl.nsplit, M, b, bpad, dffs2, energy), "bank residual reduce");
+  timer_end(c, &t);
+  return EF_OK;
+}
+
+// The launches of one recognise call on device pointers (ef_internal.hpp).
+int bank_recognize_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, int metric, long long* kdev, ef_match* mdev,
+                       int* sdev, float* fdev, const BankGate* gate) {
+  Bank& bk = c->bank;
+  EF_TRY(bank_tables(c));
+  const int64_t M = (int64_t)bk.slots.size();
+  const int64_t bpad = round_up(b, BM);
+  EF_TRY(bank_project_dev(c, Pd, p_dtype, b, fdev));
+  if (gate) EF_TRY(bank_residual_dev(c, Pd, p_dtype, b, gate->dffs2, gate->energy));
+  const BankSlotDev* tab = static_cast<const BankSlotDev*>(bk.slot_tab.p);
+  const float* q = static_cast<const float*>(bk.q.p);
+  TimerEvt t;
 
   // search: at least one entry per slot, so an empty slot's entry reads "no row"
   // the probe tile of this call: the largest of 128 .. 8 that gives the launch kBankSearchWgs items
@@ -443,11 +498,24 @@ int bank_recognize_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, int me
            "bank search");
   hipLaunchKernelGGL(bank_merge_kernel, dim3((unsigned)((b * M + 255) / 256)), dim3(256), 0, c->stream, tab, (int)M, b, ws,
                      kdev, mdev);
-  if (sdev)
-    hipLaunchKernelGGL(bank_best_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, kdev, (int)M, b,
-                       metric, sdev);
+  if (sdev && gate)
+    hipLaunchKernelGGL(bank_best_kernel<true>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, kdev, (int)M,
+                       b, metric, gate->gate, gate->relative ? 1 : 0, gate->dffs2, gate->energy, sdev);
+  else if (sdev)
+    hipLaunchKernelGGL(bank_best_kernel<false>, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, c->stream, kdev, (int)M,
+                       b, metric, nullptr, 0, nullptr, nullptr, sdev);
   EF_HIP(c, hipGetLastError(), "bank merge");
   timer_end(c, &t);
+  return EF_OK;
+}
+
+// EF_E_STATE naming the first slot without reconstruction state (ef_internal.hpp)
+int bank_recon_complete(ef_ctx* c, const char* who) {
+  const std::vector<BankSlot>& slots = c->bank.slots;
+  for (size_t m = 0; m < slots.size(); ++m)
+    if (!slots[m].recon)
+      return set_err(c, EF_E_STATE, std::string(who) + ": slot " + std::to_string(m) +
+                                        " has no reconstruction state (call ef_bank_recon_set)");
   return EF_OK;
 }
 
@@ -530,16 +598,19 @@ int ef_bank_add(ef_ctx* c, const float* mean, const float* W, int64_t d, int32_t
   return EF_OK;
 }
 
-int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int32_t metric, int64_t* keys,
-                      ef_match* matches, int32_t* best_slot, float* feats, uint32_t flags) {
+// ef_bank_recognize and ef_bank_recognize_gated: gate null is the former, with exactly its launches
+static int bank_recognize_call(ef_ctx* c, const char* who, const void* P, int32_t p_dtype, int64_t b, int32_t metric,
+                               const float* gate, int64_t* keys, ef_match* matches, int32_t* best_slot, float* dffs2,
+                               float* energy, float* feats, uint32_t flags) {
   if (!c) return EF_E_INVALID;
   Bank& bk = c->bank;
-  if (bk.slots.empty()) return set_err(c, EF_E_STATE, "ef_bank_recognize: the bank is empty (call ef_bank_add)");
-  if (c->comm && c->comm_size > 1)
-    return set_err(c, EF_E_STATE, "ef_bank_recognize: not available with a communicator attached");
+  const std::string w(who);
+  if (bk.slots.empty()) return set_err(c, EF_E_STATE, w + ": the bank is empty (call ef_bank_add)");
+  if (c->comm && c->comm_size > 1) return set_err(c, EF_E_STATE, w + ": not available with a communicator attached");
+  if (gate) EF_TRY(bank_recon_complete(c, who));
   if (!P || !keys || b < 0 || b > EF_BANK_MAX_PROBES || (p_dtype != EF_U8 && p_dtype != EF_F32) ||
-      (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE))
-    return set_err(c, EF_E_INVALID, "ef_bank_recognize: bad arguments");
+      (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE) || (gate && !dffs2))
+    return set_err(c, EF_E_INVALID, w + ": bad arguments");
   if (b == 0) return EF_OK;
   (void)hipSetDevice(c->device);
   EF_TRY(bank_tables(c));
@@ -558,9 +629,120 @@ int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int3
     EF_TRY(ensure(c, bk.out, (size_t)b * sizeof(int)));
     sdev = static_cast<int*>(bk.out.p);
   }
-  EF_TRY(bank_recognize_dev(c, Pd, p_dtype, b, metric, r.kdev, r.mdev, sdev, r.fdev));
+  BankGate g{gate, (flags & EF_BANK_GATE_RELATIVE) != 0, dffs2, energy};
+  const size_t bm = (size_t)(b * M);
+  if (gate && (!dev || !energy)) {
+    // [eps^2 | E | gate]: the host call's staging; a device call with no energy output only needs E's
+    EF_TRY(ensure(c, bk.recon_out, (2 * bm + (size_t)M) * sizeof(float)));
+    float* o = static_cast<float*>(bk.recon_out.p);
+    if (!dev) {
+      EF_HIP(c, hipMemcpyAsync(o + 2 * bm, gate, (size_t)M * sizeof(float), hipMemcpyHostToDevice, c->stream), "H2D gate");
+      g.gate = o + 2 * bm;
+      g.dffs2 = o;
+    }
+    if (!dev || !energy) g.energy = o + bm;
+  }
+  EF_TRY(bank_recognize_dev(c, Pd, p_dtype, b, metric, r.kdev, r.mdev, sdev, r.fdev, gate ? &g : nullptr));
   if (!dev && best_slot)
     EF_HIP(c, hipMemcpyAsync(best_slot, sdev, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, c->stream), "D2H best slot");
+  if (!dev && gate) {
+    EF_HIP(c, hipMemcpyAsync(dffs2, g.dffs2, bm * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H distances");
+    if (energy) EF_HIP(c, hipMemcpyAsync(energy, g.energy, bm * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H energy");
+  }
+  return r.fetch(c);
+}
+
+int ef_bank_recognize(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int32_t metric, int64_t* keys,
+                      ef_match* matches, int32_t* best_slot, float* feats, uint32_t flags) {
+  return bank_recognize_call(c, "ef_bank_recognize", P, p_dtype, b, metric, nullptr, keys, matches, best_slot, nullptr,
+                             nullptr, feats, flags);
+}
+
+int ef_bank_recognize_gated(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, int32_t metric, const float* gate,
+                            int64_t* keys, ef_match* matches, int32_t* best_slot, float* dffs2, float* energy,
+                            float* feats, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (!gate) return set_err(c, EF_E_INVALID, "ef_bank_recognize_gated: bad arguments");
+  return bank_recognize_call(c, "ef_bank_recognize_gated", P, p_dtype, b, metric, gate, keys, matches, best_slot, dffs2,
+                             energy, feats, flags);
+}
+
+int ef_bank_recon_set(ef_ctx* c, int32_t slot, const float* R, const float* weight, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  Bank& bk = c->bank;
+  if (slot < 0 || (size_t)slot >= bk.slots.size())
+    return set_err(c, EF_E_INVALID, "ef_bank_recon_set: slot " + std::to_string(slot) + " is outside the bank");
+  if (!R) return set_err(c, EF_E_INVALID, "ef_bank_recon_set: bad arguments");
+  if (bk.d > (int64_t)INT_MAX - 128) return set_err(c, EF_E_INVALID, "ef_bank_recon_set: d >= 2^31 - 128 is not supported");
+  (void)hipSetDevice(c->device);
+  BankSlot& s = bk.slots[(size_t)slot];
+  const int64_t d = bk.d, dp = recon_dpad(d);
+  const int k = s.g.k, kp = s.g.kp;
+  const bool dev = (flags & EF_MEM_DEVICE) != 0;
+  std::vector<float> ones;
+  DevBuf Rn, wn, staging;  // built here, published only when complete: a failure below changes nothing
+  EF_TRY(ensure(c, Rn, (size_t)kp * dp * sizeof(float)));
+  EF_TRY(ensure(c, wn, (size_t)d * sizeof(float)));
+  if (!dev) {
+    EF_TRY(ensure(c, staging, (size_t)k * d * sizeof(float)));
+    EF_HIP(c, hipMemcpyAsync(staging.p, R, (size_t)k * d * sizeof(float), hipMemcpyHostToDevice, c->stream), "copy R");
+    R = static_cast<const float*>(staging.p);
+  }
+  EF_HIP(c, launch_pad_rows(c->stream, R, k, (int)d, kp, static_cast<float*>(Rn.p), (int)dp), "pad R");
+  if (!weight) {
+    try {
+      ones.assign((size_t)d, 1.f);
+    } catch (const std::bad_alloc&) {
+      return set_err(c, EF_E_NOMEM, "ef_bank_recon_set: host allocation failed");
+    }
+    weight = ones.data();
+  }
+  EF_HIP(c,
+         hipMemcpyAsync(wn.p, weight, (size_t)d * sizeof(float),
+                        dev && ones.empty() ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
+         "copy weight");
+  // also behind every queued kernel that reads the slot's previous R
+  EF_HIP(c, hipStreamSynchronize(c->stream), "ef_bank_recon_set");
+  s.recon_R = std::move(Rn);
+  s.recon_w = std::move(wn);
+  s.recon = true;
+  bk.tables_valid = false;
+  return EF_OK;
+}
+
+int ef_bank_face_distance(ef_ctx* c, const void* P, int32_t p_dtype, int64_t b, float* dffs2, float* energy, float* feats,
+                          uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  Bank& bk = c->bank;
+  if (bk.slots.empty()) return set_err(c, EF_E_STATE, "ef_bank_face_distance: the bank is empty (call ef_bank_add)");
+  if (c->comm && c->comm_size > 1)
+    return set_err(c, EF_E_STATE, "ef_bank_face_distance: not available with a communicator attached");
+  EF_TRY(bank_recon_complete(c, "ef_bank_face_distance"));
+  if (b < 0 || b > EF_BANK_MAX_PROBES || (p_dtype != EF_U8 && p_dtype != EF_F32) || (b > 0 && (!P || !dffs2)))
+    return set_err(c, EF_E_INVALID, "ef_bank_face_distance: bad arguments");
+  if (b == 0) return EF_OK;
+  (void)hipSetDevice(c->device);
+  EF_TRY(bank_tables(c));
+  const bool dev = flags & EF_MEM_DEVICE;
+  const int64_t M = (int64_t)bk.slots.size();
+  const void* Pd = nullptr;
+  EF_TRY(stage_probes(c, P, p_dtype, b, bk.d, flags, bk.p_stage, &Pd));
+  Results r{dev, b, (int)M, bk.total_k, nullptr, nullptr, feats};
+  EF_TRY(r.stage_feats(c));
+  const size_t bm = (size_t)(b * M);
+  float* ddev = dffs2;
+  float* edev = energy;
+  if (!dev) {
+    EF_TRY(ensure(c, bk.recon_out, 2 * bm * sizeof(float)));
+    ddev = static_cast<float*>(bk.recon_out.p);
+    edev = energy ? ddev + bm : nullptr;
+  }
+  EF_TRY(bank_project_dev(c, Pd, p_dtype, b, r.fdev));
+  EF_TRY(bank_residual_dev(c, Pd, p_dtype, b, ddev, edev));
+  if (!dev) {
+    EF_HIP(c, hipMemcpyAsync(dffs2, ddev, bm * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H distances");
+    if (energy) EF_HIP(c, hipMemcpyAsync(energy, edev, bm * sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H energy");
+  }
   return r.fetch(c);
 }
 

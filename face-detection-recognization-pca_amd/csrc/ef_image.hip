@@ -952,6 +952,10 @@ struct ScanPlan {
   DevBuf gray;        // the grey plane of a colour frame, round_up(H * W, 4) bytes
   DevBuf out;         // the result block
   PinnedBuf host;     // its pinned mirror
+  // ef_scan_frame_gated, host form: the gate stays resident and is uploaded again only when its
+  // values change, so a frame still costs one upload
+  DevBuf gate;
+  std::vector<float> gate_host;
 };
 
 struct TmState {
@@ -1396,14 +1400,22 @@ int ef_preprocess_rois(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_
 }
 
 // The pieces of a scan's result block for g groups, M bank slots and d face pixels.
+// gated: the distances from face space and the energies too, behind the ungated pieces
 struct ScanOut {
   ef_scan_det* dets;
   long long* keys;
   int* best;
   uint8_t* rows;
+  float* dffs2;
+  float* energy;
 };
-static ScanOut carve_scan_out(Carve& cv, size_t g, size_t M, size_t d) {
-  return ScanOut{cv.take<ef_scan_det>(g), cv.take<long long>(g * M), cv.take<int>(g), cv.take<uint8_t>(g * d)};
+static ScanOut carve_scan_out(Carve& cv, size_t g, size_t M, size_t d, bool gated) {
+  ScanOut o{cv.take<ef_scan_det>(g), cv.take<long long>(g * M), cv.take<int>(g), cv.take<uint8_t>(g * d), nullptr, nullptr};
+  if (gated) {
+    o.dffs2 = cv.take<float>(g * M);
+    o.energy = cv.take<float>(g * M);
+  }
+  return o;
 }
 
 int ef_scan_prepare(ef_ctx* c, const int32_t* prob_group, int32_t n_groups, int32_t face_h, int32_t face_w,
@@ -1440,23 +1452,27 @@ int ef_scan_prepare(ef_ctx* c, const int32_t* prob_group, int32_t n_groups, int3
   return EF_OK;
 }
 
-int ef_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
-                  ef_scan_det* dets, int64_t* keys, int32_t* best_slot, uint8_t* rows, uint32_t flags) {
+// ef_scan_frame and ef_scan_frame_gated: gate null is the former, with exactly its launches
+static int scan_frame_call(ef_ctx* c, const char* who, const uint8_t* frame, int64_t frame_ld, int32_t channels,
+                           int32_t metric, const float* gate, ef_scan_det* dets, int64_t* keys, int32_t* best_slot,
+                           uint8_t* rows, float* dffs2, float* energy, uint32_t flags) {
   if (!c) return EF_E_INVALID;
+  const std::string w(who);
   TmState* t = c->tm;
   ScanPlan* sp = t ? t->scan.get() : nullptr;
-  if (!sp) return set_err(c, EF_E_STATE, "ef_scan_frame: no scan plan (call ef_tm_prepare, then ef_scan_prepare)");
+  if (!sp) return set_err(c, EF_E_STATE, w + ": no scan plan (call ef_tm_prepare, then ef_scan_prepare)");
   Bank& bk = c->bank;
-  if (bk.slots.empty()) return set_err(c, EF_E_STATE, "ef_scan_frame: the bank is empty (call ef_bank_add)");
+  if (bk.slots.empty()) return set_err(c, EF_E_STATE, w + ": the bank is empty (call ef_bank_add)");
   const int64_t d = (int64_t)sp->face_h * sp->face_w;
   if (bk.d != d)
-    return set_err(c, EF_E_STATE, "ef_scan_frame: the bank's models take " + std::to_string(bk.d) +
+    return set_err(c, EF_E_STATE, w + ": the bank's models take " + std::to_string(bk.d) +
                                       " pixels, the scan plan's faces have " + std::to_string(d));
   if (c->comm && c->comm_size > 1)
-    return set_err(c, EF_E_STATE, "ef_scan_frame: not available with a communicator attached");
+    return set_err(c, EF_E_STATE, w + ": not available with a communicator attached");
+  if (gate) EF_TRY(bank_recon_complete(c, who));
   if (!frame || !dets || !keys || (channels != 1 && channels != 3 && channels != 4) ||
-      frame_ld < (int64_t)t->W * channels || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE))
-    return set_err(c, EF_E_INVALID, "ef_scan_frame: bad arguments");
+      frame_ld < (int64_t)t->W * channels || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE) || (gate && !dffs2))
+    return set_err(c, EF_E_INVALID, w + ": bad arguments");
   EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
   const bool dev = flags & EF_MEM_DEVICE;
   hipStream_t s = c->stream;
@@ -1466,16 +1482,38 @@ int ef_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t cha
   // where the kernels write: the caller's device arrays, or the result block; the rows always
   // exist (the bank reads them)
   Carve size_out, cv;
-  carve_scan_out(size_out, (size_t)G, M, (size_t)d);
-  ScanOut o{dets, reinterpret_cast<long long*>(keys), best_slot, rows};
-  if (!dev || !rows) {
+  const bool gated = gate != nullptr;
+  carve_scan_out(size_out, (size_t)G, M, (size_t)d, gated);
+  ScanOut o{dets, reinterpret_cast<long long*>(keys), best_slot, rows, dffs2, energy};
+  if (!dev || !rows || (gated && !energy)) {
     EF_TRY(ensure(c, sp->out, size_out.total));
     cv.base = sp->out.p;
-    const ScanOut blk = carve_scan_out(cv, (size_t)G, M, (size_t)d);
-    if (!dev)
+    const ScanOut blk = carve_scan_out(cv, (size_t)G, M, (size_t)d, gated);
+    if (!dev) {
       o = blk;
-    else
-      o.rows = blk.rows;
+    } else {
+      if (!rows) o.rows = blk.rows;
+      if (!energy) o.energy = blk.energy;
+    }
+  }
+  BankGate bg{gate, (flags & EF_BANK_GATE_RELATIVE) != 0, o.dffs2, o.energy};
+  if (gated && !dev) {
+    if (sp->gate_host.size() != M || std::memcmp(sp->gate_host.data(), gate, M * sizeof(float)) != 0) {
+      try {
+        sp->gate_host.assign(gate, gate + M);
+      } catch (const std::bad_alloc&) {
+        return set_err(c, EF_E_NOMEM, w + ": host allocation failed");
+      }
+      const hipError_t e = [&] {
+        if (ensure(c, sp->gate, M * sizeof(float)) != EF_OK) return hipErrorOutOfMemory;
+        return hipMemcpyAsync(sp->gate.p, sp->gate_host.data(), M * sizeof(float), hipMemcpyHostToDevice, s);
+      }();
+      if (e != hipSuccess) {
+        sp->gate_host.clear();  // nothing resident: the next call uploads again
+        return hip_err(c, e, "H2D gate");
+      }
+    }
+    bg.gate = static_cast<const float*>(sp->gate.p);
   }
   if (!dev && sp->host.bytes < size_out.total) EF_HIP(c, pinned_alloc(sp->host, size_out.total), "pinned results");
   const uint8_t* f = frame;
@@ -1511,19 +1549,36 @@ int ef_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t cha
   static_assert(sizeof(ef_scan_det) == 32 && offsetof(ef_scan_det, x) == 8, "ef_scan_det layout");
   EF_HIP(c, launch_roi_resize(s, f, frame_ld, H, W, 1, &o.dets->x, 8, G, sp->face_h, sp->face_w, false, o.rows),
          "ROI resize kernel");
-  EF_TRY(bank_recognize_dev(c, o.rows, EF_U8, G, metric, o.keys, nullptr, o.best, nullptr));
+  EF_TRY(bank_recognize_dev(c, o.rows, EF_U8, G, metric, o.keys, nullptr, o.best, nullptr, gated ? &bg : nullptr));
   timer_end(c, &tev);
   if (dev) return EF_OK;
   EF_HIP(c, hipMemcpyAsync(sp->host.p, sp->out.p, size_out.total, hipMemcpyDeviceToHost, s), "D2H results");
   EF_HIP(c, hipStreamSynchronize(s), "sync");
   Carve hv;
   hv.base = sp->host.p;
-  const ScanOut h = carve_scan_out(hv, (size_t)G, M, (size_t)d);
+  const ScanOut h = carve_scan_out(hv, (size_t)G, M, (size_t)d, gated);
   std::memcpy(dets, h.dets, (size_t)G * sizeof(ef_scan_det));
   std::memcpy(keys, h.keys, (size_t)G * M * sizeof(long long));
   if (best_slot) std::memcpy(best_slot, h.best, (size_t)G * sizeof(int));
   if (rows) std::memcpy(rows, h.rows, (size_t)G * d);
+  if (gated) std::memcpy(dffs2, h.dffs2, (size_t)G * M * sizeof(float));
+  if (gated && energy) std::memcpy(energy, h.energy, (size_t)G * M * sizeof(float));
   return EF_OK;
+}
+
+int ef_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
+                  ef_scan_det* dets, int64_t* keys, int32_t* best_slot, uint8_t* rows, uint32_t flags) {
+  return scan_frame_call(c, "ef_scan_frame", frame, frame_ld, channels, metric, nullptr, dets, keys, best_slot, rows,
+                         nullptr, nullptr, flags);
+}
+
+int ef_scan_frame_gated(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
+                        const float* gate, ef_scan_det* dets, int64_t* keys, int32_t* best_slot, uint8_t* rows,
+                        float* dffs2, float* energy, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (!gate) return set_err(c, EF_E_INVALID, "ef_scan_frame_gated: bad arguments");
+  return scan_frame_call(c, "ef_scan_frame_gated", frame, frame_ld, channels, metric, gate, dets, keys, best_slot, rows,
+                         dffs2, energy, flags);
 }
 
 }  // extern "C"

@@ -286,6 +286,25 @@ struct BankSlot {
   DevBuf mean;  // float[d]
   DevBuf W;     // float[d][kpw]
   Gallery g;    // k, kp and the rows; gmax2 is read on the device
+  // the way back (ef_bank_recon_set): published together, once completely built
+  bool recon = false;
+  DevBuf recon_R;  // float[kp][recon_dpad(d)], zero past k and past d
+  DevBuf recon_w;  // float[d] per-pixel weight (ones when the caller gave none)
+};
+// One slot's operands of the grouped residual (ef_bank_recon.hip); R null: the slot has none.
+struct BankReconDev {
+  const float* R;
+  const float* mean;
+  const float* wgt;
+  int kp;
+  int64_t kp_off;  // the slot's feature block is q + bpad * kp_off, [bpad][kp]
+};
+// The face gate of one gated call: device pointers.
+struct BankGate {
+  const float* gate;  // [slots]
+  bool relative;      // bound = gate[m] * energy[p][m]
+  float* dffs2;       // [b][slots]
+  float* energy;      // [b][slots]: required here (the scratch of a call that does not return it)
 };
 // The slots, their device tables (rebuilt on the first recognize after a change) and the
 // per-call scratch.  A slot is built completely before it is appended.
@@ -297,6 +316,10 @@ struct Bank {
   bool tables_valid = false;
   DevBuf proj_items;  // BankProjItem[column tiles]
   DevBuf slot_tab;    // BankSlotDev[slots]
+  DevBuf recon_tab;   // BankReconDev[slots]
+  int recon_rk = 32;       // stage depth of the grouped residual: 16 when any slot has kp = 16
+  DevBuf recon_part;  // float[2][nsplit][slots][bpad] partial eps^2 and E
+  DevBuf recon_out;   // dffs2, energy (and the gate) of a host call; the energy of a call that has no use for it
   DevBuf part;        // float[nsplit][bpad][total_kpw] partial slabs
   DevBuf q;           // per slot float[bpad][kp], slot m at bpad * sum_{j<m} kp_j
   DevBuf ws;          // search scratch (per row slice and probe)
@@ -308,8 +331,27 @@ struct Bank {
 // Pd[b][bank.d] -> kdev[b][slots] and, each optional, mdev[b][slots], sdev[b] (best slot) and
 // fdev[b][sum k].  Everything is queued on c->stream; only the table upload after the bank
 // changed waits.  The caller has checked the bank's state and the arguments.
+// gate non-null: the grouped residual and its reduce are queued between the projection's reduce
+// and the search (-> gate->dffs2, gate->energy, from the same features), and the walk over models
+// skips the slots the gate rejects; null: exactly the launches described above.
 int bank_recognize_dev(ef_ctx* c, const void* Pd, int p_dtype, int64_t b, int metric, long long* kdev, ef_match* mdev,
-                       int* sdev, float* fdev);
+                       int* sdev, float* fdev, const BankGate* gate = nullptr);
+// EF_OK when every slot has reconstruction state, else EF_E_STATE naming the first without (ef_bank.hip)
+int bank_recon_complete(ef_ctx* c, const char* who);
+// The grouped residual's plan (ef_bank_recon.hip): what ef_bank_recon_schedule reports and
+// launch_bank_recon launches.
+struct BankReconPlan {
+  int nsplit = 1, tiles_per_split = 1;
+  int64_t n_workgroups = 0, scratch_bytes = 0;
+};
+BankReconPlan bank_recon_plan(int64_t b, int64_t d, int64_t n_slots);
+// q: the bank's feature blocks (slot m at q + bpad * kp_off_m, [bpad][kp_m], zero past b and past
+// k_m); P[b][d] pixels; part[2][nsplit][n_slots][bpad] -> launch_bank_recon_reduce ->
+// dffs2[b][n_slots], energy[b][n_slots] (optional).  rk: 16 | 32, dividing every slot's kp.
+hipError_t launch_bank_recon(hipStream_t s, const BankReconDev* tab, int n_slots, int rk, int p_dtype, const float* q,
+                             const void* P, int64_t b, int64_t bpad, int64_t d, float* part, const BankReconPlan& pl);
+hipError_t launch_bank_recon_reduce(hipStream_t s, const float* part, int nsplit, int n_slots, int64_t b, int64_t bpad,
+                                    float* dffs2, float* energy);
 
 struct TmState;    // template-localiser state (ef_image.hip)
 struct HaarState;  // Haar cascade state (ef_haar.hip)

@@ -5,9 +5,10 @@ Drop-in for the PCA / recognition hot path of saladbkp/face-detection-recognizat
 hand-written gfx950 HIP kernels in ``_lib/libeigenface.so`` (no CPU fallback).
 """
 from ._native import EigenfaceError, NativeLibraryError, LIB_PATH  # noqa: F401
-from .engine import Engine, FitResult, decode_keys, device_count, merge_matches_host, merge_topk_host  # noqa: F401
+from .engine import (Engine, FitResult, bank_recon_schedule, decode_keys, device_count,  # noqa: F401
+                     merge_matches_host, merge_topk_host)
 from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_face_to_eigenspace  # noqa: F401
-from .bank import ModelBank, best_over_models  # noqa: F401
+from .bank import ModelBank, best_over_models, face_gate_mask  # noqa: F401
 from .scanner import FrameScanner, decide  # noqa: F401
 from .compat import face_space_distance, reconstruct_faces  # noqa: F401
 from .pca import (  # noqa: F401
@@ -33,5 +34,5 @@ __all__ = [
     "recognize_face_candidates_with_model", "EigenfaceError",
     "NativeLibraryError", "LIB_PATH", "save_gallery_cache", "load_gallery_cache", "ManualPCA",
     "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity", "ModelBank", "best_over_models",
-    "FrameScanner", "decide", "reconstruct_faces", "face_space_distance",
+    "FrameScanner", "decide", "reconstruct_faces", "face_space_distance", "face_gate_mask", "bank_recon_schedule",
 ]

@@ -22,6 +22,7 @@ EF_MODEL_BF16 = 0x2
 EF_MEM_DEVICE = 0x100
 EF_IMG_RGB = 0x200
 EF_ROI_RECTS_DEVICE = 0x400
+EF_BANK_GATE_RELATIVE = 0x800
 EF_KERNEL_SEARCH, EF_KERNEL_PROJECT, EF_KERNEL_TMATCH, EF_KERNEL_INGEST, EF_KERNEL_HAAR, EF_KERNEL_JPEG, \
     EF_KERNEL_SYRK, EF_KERNEL_JPEG_HOST = 0, 1, 2, 3, 4, 5, 6, 7
 EF_KERNEL_SCAN = 8
@@ -154,6 +155,13 @@ _SIGS = {
     "ef_recon_set": ([vp, vp, vp, i64, i32, u32], C.c_int),
     "ef_reconstruct": ([vp, vp, i64, i32, vp, u32], C.c_int),
     "ef_face_distance": ([vp, vp, i32, i64, vp, vp, vp, u32], C.c_int),
+    # model bank: distance from face space per slot and the face gate, bound by symbol too
+    "ef_bank_recon_set": ([vp, i32, vp, vp, u32], C.c_int),
+    "ef_bank_face_distance": ([vp, vp, i32, i64, vp, vp, vp, u32], C.c_int),
+    "ef_bank_recognize_gated": ([vp, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, u32], C.c_int),
+    "ef_scan_frame_gated": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, u32], C.c_int),
+    "ef_bank_recon_schedule": ([i64, i64, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)],
+                               C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -985,6 +985,154 @@ class Engine:
         offs = np.concatenate([[0], np.cumsum(ks)])
         return out + ([np.ascontiguousarray(f[:, offs[m]:offs[m + 1]]) for m in range(len(ks))],)
 
+    def bank_set_reconstruction(self, slot, R, weight=None):
+        """The way back of bank slot ``slot`` (ef_bank_recon_set): R (k, d) and an optional
+        per-pixel weight (d,), as :meth:`set_reconstruction` takes them.  A failed call leaves the
+        slot's previous state."""
+        if _is_dev(R):
+            import torch
+            r, rp = _dev(R, torch.float32)
+            w, wp = _dev(weight, torch.float32) if weight is not None else (None, None)
+            flags = N.EF_MEM_DEVICE
+        else:
+            r, rp = _host(R, np.float32)
+            w, wp = _host(weight, np.float32) if weight is not None else (None, None)
+            flags = 0
+        if r.ndim != 2:
+            raise ValueError("R must be 2-D (k, d)")
+        ks, d = self.bank_slot_widths(), self.bank_info()[1]
+        if 0 <= int(slot) < len(ks) and tuple(r.shape) != (ks[int(slot)], d):  # (the library rejects a bad slot)
+            raise ValueError(f"R must be ({ks[int(slot)]}, {d}), got {tuple(r.shape)}")
+        if w is not None and tuple(w.shape) != (int(r.shape[1]),):
+            raise ValueError("weight and R disagree on d")
+        self._chk(self._lib.ef_bank_recon_set(self._h, int(slot), rp, wp, flags))
+
+    def _bank_pixels(self, P, d):
+        """(array or tensor, pointer, dtype code, b, on_device) of the probes of a bank call."""
+        if _is_dev(P):
+            import torch
+            if P.dtype not in (torch.uint8, torch.float32):
+                raise TypeError(f"probe pixels must be uint8 or float32, got {P.dtype}")
+            if P.ndim != 2 or P.shape[1] != d:
+                raise ValueError(f"P must be (b, {d}), got {tuple(P.shape)}")
+            p, pp = _dev(P, P.dtype)
+            return p, pp, (N.EF_U8 if P.dtype == torch.uint8 else N.EF_F32), int(p.shape[0]), True
+        p = np.asarray(P)
+        dtype = N.EF_U8 if p.dtype == np.uint8 else N.EF_F32
+        p, pp = _host(p, np.uint8 if dtype == N.EF_U8 else np.float32)
+        if p.ndim != 2 or p.shape[1] != d:
+            raise ValueError(f"P must be (b, {d}), got {p.shape}")
+        return p, pp, dtype, int(p.shape[0]), False
+
+    def _split_feats(self, f):
+        ks = self.bank_slot_widths()
+        offs = np.concatenate([[0], np.cumsum(ks)]).astype(np.int64)
+        return [np.ascontiguousarray(f[:, offs[m]:offs[m + 1]]) for m in range(len(ks))]
+
+    def bank_face_distance(self, P, return_energy=False, return_features=False):
+        """Distance from face space of pixels P (b, d) against every slot of the bank
+        (ef_bank_face_distance): eps2 (b, M) float32 and, when asked, the energy (b, M) and the
+        features, in that order.  Host pixels give NumPy arrays (features as a list of M (b, k_m)
+        arrays, the ones :meth:`bank_recognize` returns); device pixels give device tensors
+        (features (b, sum k)), stream-ordered.  At most EF_BANK_MAX_PROBES probes per call."""
+        M, d, tk, _ = self.bank_info()
+        if M == 0:  # the library reports the state error
+            self._chk(self._lib.ef_bank_face_distance(self._h, None, N.EF_U8, 0, None, None, None, 0))
+        p, pp, dtype, b, dev = self._bank_pixels(P, d)
+        if dev:
+            import torch
+
+            def alloc(shape):
+                return torch.empty(shape, dtype=torch.float32, device=p.device)
+
+            def ptr(a):
+                return a.data_ptr() if a is not None else None
+        else:
+            def alloc(shape):
+                return np.empty(shape, dtype=np.float32)
+
+            def ptr(a):
+                return a.ctypes.data if a is not None else None
+        out = alloc((b, M))
+        en = alloc((b, M)) if return_energy else None
+        ft = alloc((b, tk)) if return_features else None
+        ctx = self._torch_order(p, out, en, ft) if dev else contextlib.nullcontext()
+        with ctx:
+            self._chk(self._lib.ef_bank_face_distance(self._h, pp, dtype, b, ptr(out), ptr(en), ptr(ft),
+                                                      N.EF_MEM_DEVICE if dev else 0))
+        if ft is not None and not dev:
+            ft = self._split_feats(ft)
+        res = (out,) + ((en,) if return_energy else ()) + ((ft,) if return_features else ())
+        return res[0] if len(res) == 1 else res
+
+    def bank_recognize_gated_raw(self, P, gate, metric="cosine", relative=True, matches=False, features=False):
+        """ef_bank_recognize_gated on at most EF_BANK_MAX_PROBES probes: (keys, records or None,
+        best_slot, feats or None, dffs2[b, M], energy[b, M]) as :meth:`bank_recognize_raw` gives
+        its four.  ``gate`` is (M,) float32: NumPy for host pixels, a device tensor (or an array,
+        uploaded here) for device pixels."""
+        mt = _metric(metric)
+        M, d, tk, _ = self.bank_info()
+        if M == 0:  # the library reports the state error
+            one = np.zeros(1, np.float32)
+            self._chk(self._lib.ef_bank_recognize_gated(self._h, None, N.EF_U8, 0, mt, one.ctypes.data, None, None, None,
+                                                        None, None, None, 0))
+        p, pp, dtype, b, dev = self._bank_pixels(P, d)
+        flags = N.EF_BANK_GATE_RELATIVE if relative else 0
+        if dev:
+            import torch
+            g = gate if _is_dev(gate) else torch.as_tensor(np.asarray(gate, np.float32), device=p.device)
+            g, gp = _dev(g, torch.float32)
+            if tuple(g.shape) != (M,):
+                raise ValueError(f"gate must be ({M},), got {tuple(g.shape)}")
+            keys = torch.empty((b, M), dtype=torch.int64, device=p.device)
+            rec = torch.empty((b, M, 3), dtype=torch.int64, device=p.device) if matches else None
+            best = torch.empty(b, dtype=torch.int32, device=p.device)
+            feats = torch.empty((b, tk), dtype=torch.float32, device=p.device) if features else None
+            eps = torch.empty((b, M), dtype=torch.float32, device=p.device)
+            en = torch.empty((b, M), dtype=torch.float32, device=p.device)
+            with self._torch_order(p, g, keys, rec, best, feats, eps, en):
+                self._chk(self._lib.ef_bank_recognize_gated(
+                    self._h, pp, dtype, b, mt, gp, keys.data_ptr(), rec.data_ptr() if matches else None,
+                    best.data_ptr(), eps.data_ptr(), en.data_ptr(), feats.data_ptr() if features else None,
+                    flags | N.EF_MEM_DEVICE))
+            return keys, rec, best, feats, eps, en
+        g, gp = _host(gate, np.float32)
+        if g.shape != (M,):
+            raise ValueError(f"gate must be ({M},), got {g.shape}")
+        keys = np.empty((b, M), dtype=np.int64)
+        rec = np.empty((b, M), dtype=N.MATCH_DTYPE) if matches else None
+        best = np.empty(b, dtype=np.int32)
+        feats = np.empty((b, tk), dtype=np.float32) if features else None
+        eps = np.empty((b, M), dtype=np.float32)
+        en = np.empty((b, M), dtype=np.float32)
+        self._chk(self._lib.ef_bank_recognize_gated(self._h, pp, dtype, b, mt, gp, keys.ctypes.data,
+                                                    rec.ctypes.data if matches else None, best.ctypes.data,
+                                                    eps.ctypes.data, en.ctypes.data,
+                                                    feats.ctypes.data if features else None, flags))
+        return keys, rec, best, feats, eps, en
+
+    def bank_recognize_gated(self, P, gate, metric="cosine", relative=True, return_features=False):
+        """:meth:`bank_recognize` with a face gate: (idx[b, M], score[b, M], best_slot[b][, feats],
+        dffs2[b, M], energy[b, M]) as NumPy arrays.  idx, score and feats are bit-identical to
+        :meth:`bank_recognize`'s; best_slot's walk over models skips slot m for probe p when
+        ``dffs2[p, m] > gate[m]`` (``relative``: ``> gate[m] * energy[p, m]``, one float32 multiply)
+        is true, so +inf or NaN gate nothing.  Batches over EF_BANK_MAX_PROBES run in chunks."""
+        b = int(P.shape[0])
+        chunk = N.EF_BANK_MAX_PROBES
+        parts = [self.bank_recognize_gated_raw(P[o:o + chunk], gate, metric, relative, features=return_features)
+                 for o in range(0, max(b, 1), chunk)]
+        if _is_dev(P):
+            parts = [tuple(None if t is None else t.cpu().numpy() for t in part) for part in parts]
+        keys = np.concatenate([part[0] for part in parts])
+        best = np.concatenate([part[2] for part in parts])
+        eps = np.concatenate([part[4] for part in parts])
+        en = np.concatenate([part[5] for part in parts])
+        idx, score = decode_keys(keys.reshape(-1), metric)
+        out = (idx.reshape(keys.shape), score.reshape(keys.shape), best)
+        if return_features:
+            out = out + (self._split_feats(np.concatenate([part[3] for part in parts])),)
+        return out + (eps, en)
+
     def bank_slot_widths(self):
         """k of every slot added through this Engine since the last bank_clear."""
         return list(getattr(self, "_bank_k", []))
@@ -1261,6 +1409,54 @@ class Engine:
                                           best.ctypes.data, rows.ctypes.data, flags))
         return dets, keys, best, rows
 
+    def scan_frame_gated(self, frame, gate, metric="cosine", relative=True, rgb=False):
+        """:meth:`scan_frame` whose recognition step is :meth:`bank_recognize_gated`
+        (ef_scan_frame_gated): (dets, keys, best_slot, rows, dffs2[G, M], energy[G, M]).  dets, keys
+        and rows are :meth:`scan_frame`'s, bit for bit; best_slot skips the slots ``gate`` (M,)
+        rejects."""
+        mt = _metric(metric)
+        if getattr(self, "_tm", None) is None or getattr(self, "_scan", None) is None:
+            one = np.zeros(1, np.float32)  # the library reports the state error
+            self._chk(self._lib.ef_scan_frame_gated(self._h, None, 0, 1, mt, one.ctypes.data, None, None, None, None,
+                                                    None, None, 0))
+            raise RuntimeError("call scan_prepare first")
+        (G, fh, fw), H, W = self._scan, self._tm[1], self._tm[2]
+        f, fp, ld, h, w, ch, dev = self._frame_view(frame)
+        if (h, w) != (H, W):
+            raise ValueError(f"frame must be {(H, W)}, got {(h, w)}")
+        M = self.bank_info()[0]
+        flags = (N.EF_IMG_RGB if rgb else 0) | (N.EF_BANK_GATE_RELATIVE if relative else 0)
+        if dev:
+            import torch
+            g = gate if _is_dev(gate) else torch.as_tensor(np.asarray(gate, np.float32), device=f.device)
+            g, gp = _dev(g, torch.float32)
+            if tuple(g.shape) != (M,):
+                raise ValueError(f"gate must be ({M},), got {tuple(g.shape)}")
+            dets = torch.empty((G, 8), dtype=torch.int32, device=f.device)
+            keys = torch.empty((G, M), dtype=torch.int64, device=f.device)
+            best = torch.empty(G, dtype=torch.int32, device=f.device)
+            rows = torch.empty((G, fh * fw), dtype=torch.uint8, device=f.device)
+            eps = torch.empty((G, M), dtype=torch.float32, device=f.device)
+            en = torch.empty((G, M), dtype=torch.float32, device=f.device)
+            with self._torch_order(f, g, dets, keys, best, rows, eps, en):
+                self._chk(self._lib.ef_scan_frame_gated(self._h, fp, ld, ch, mt, gp, dets.data_ptr(), keys.data_ptr(),
+                                                        best.data_ptr(), rows.data_ptr(), eps.data_ptr(),
+                                                        en.data_ptr(), flags | N.EF_MEM_DEVICE))
+            return dets, keys, best, rows, eps, en
+        g, gp = _host(gate, np.float32)
+        if g.shape != (M,):
+            raise ValueError(f"gate must be ({M},), got {g.shape}")
+        dets = np.empty(G, dtype=N.SCAN_DET_DTYPE)
+        keys = np.empty((G, M), dtype=np.int64)
+        best = np.empty(G, dtype=np.int32)
+        rows = np.empty((G, fh * fw), dtype=np.uint8)
+        eps = np.empty((G, M), dtype=np.float32)
+        en = np.empty((G, M), dtype=np.float32)
+        self._chk(self._lib.ef_scan_frame_gated(self._h, fp, ld, ch, mt, gp, dets.ctypes.data, keys.ctypes.data,
+                                                best.ctypes.data, rows.ctypes.data, eps.ctypes.data, en.ctypes.data,
+                                                flags))
+        return dets, keys, best, rows, eps, en
+
     # --------------------------------------------------------------------- timing
     def timing(self, on=True):
         self._chk(self._lib.ef_timing_enable(self._h, 1 if on else 0))
@@ -1277,6 +1473,18 @@ class Engine:
         n = C.c_int64(0)
         self._chk(self._lib.ef_timing_get(self._h, kid, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
+
+
+def bank_recon_schedule(b, d, n_models):
+    """ef_bank_recon_schedule (host only): the grouped residual's plan for b probes of d pixels
+    against n_models slots, as a dict of nsplit, tiles_per_split, n_workgroups, scratch_bytes."""
+    ns, tps, nwg, sb = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    rc = N.lib().ef_bank_recon_schedule(int(b), int(d), int(n_models), C.byref(ns), C.byref(tps), C.byref(nwg),
+                                        C.byref(sb))
+    if rc != N.EF_OK:
+        raise N.EigenfaceError(rc, "ef_bank_recon_schedule: bad arguments")
+    return {"nsplit": int(ns.value), "tiles_per_split": int(tps.value), "n_workgroups": int(nwg.value),
+            "scratch_bytes": int(sb.value)}
 
 
 def decode_keys(keys, metric="l2"):

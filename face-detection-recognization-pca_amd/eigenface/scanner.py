@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .bank import ModelBank
+from .bank import ModelBank, face_gate_mask
 from .engine import decode_keys
 from .image import SCALES, TemplateLocaliser
 from .pca import get_engine
@@ -74,9 +74,14 @@ class FrameScanner:
 
     A person without templates (or whose ``detection_data`` is present and empty, :146) is
     never detected; a person whose ``model_data`` is None or unusable has no slot in the bank,
-    as in :class:`ModelBank`.  At least one usable model is required."""
+    as in :class:`ModelBank`.  At least one usable model is required.
 
-    def __init__(self, models, frame_shape, device=0, threshold=0.6, recognize_threshold=0.8, scales=SCALES):
+    ``face_gate`` is :class:`ModelBank`'s: with it the frame goes through ``ef_scan_frame_gated``,
+    and a detection whose crop no model accepts as a face reaches :func:`decide` as
+    ``(-1, "unknown", 0.0)``."""
+
+    def __init__(self, models, frame_shape, device=0, threshold=0.6, recognize_threshold=0.8, scales=SCALES,
+                 face_gate=None):
         self.device = device
         self.models = models
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
@@ -92,7 +97,7 @@ class FrameScanner:
         self.persons = self.localiser.persons
         group = {p: g for g, p in enumerate(self.persons)}
         self.prob_group = np.array([group[m[0]] for m in self.localiser.meta], np.int32)
-        self.bank = ModelBank(models, device)
+        self.bank = ModelBank(models, device, face_gate)
         if not len(self.bank):
             raise ValueError("FrameScanner needs at least one usable model")
 
@@ -110,14 +115,20 @@ class FrameScanner:
         return eng
 
     def scan_raw(self, frame, rgb=False):
-        """``Engine.scan_frame`` on this scanner's plan: (dets, keys, best_slot, rows)."""
-        return self._prepare().scan_frame(frame, "cosine", rgb=rgb)
+        """``Engine.scan_frame`` on this scanner's plan: (dets, keys, best_slot, rows); with a
+        face gate ``Engine.scan_frame_gated``: the same and (dffs2, energy)."""
+        eng = self._prepare()
+        if self.bank.gate is None:
+            return eng.scan_frame(frame, "cosine", rgb=rgb)
+        if not self.bank._recon_up:
+            self.bank._upload_reconstruction(eng)
+        return eng.scan_frame_gated(frame, self.bank.gate, "cosine", relative=True, rgb=rgb)
 
     def scan(self, frame, rgb=False):
         """(detections, pca_results) of one BGR (or grey) frame: the dicts of
         ``template_match_all_models`` (:176-184) in model order, and per detection the
         ``(person_id, name, confidence)`` of ``recognize_face_all_models`` on its crop."""
-        dets, keys, _, _ = self.scan_raw(frame, rgb)
+        dets, keys, _, _, *gate_out = self.scan_raw(frame, rgb)
         found = np.flatnonzero(dets["found"])
         detections = []
         for g in found:
@@ -129,7 +140,8 @@ class FrameScanner:
             return detections, []
         k = np.ascontiguousarray(keys[found])
         idx, sim = decode_keys(k.reshape(-1), "cosine")
-        return detections, self.bank.label(idx.reshape(k.shape), sim.reshape(k.shape), self.recognize_threshold)
+        allowed = face_gate_mask(gate_out[0][found], gate_out[1][found], self.bank.gate) if gate_out else None
+        return detections, self.bank.label(idx.reshape(k.shape), sim.reshape(k.shape), self.recognize_threshold, allowed)
 
     decide = staticmethod(decide)
 

@@ -54,6 +54,7 @@ extern "C" {
 #define EF_MEM_DEVICE 0x100u    /* pointer args are device pointers, call is asynchronous    */
 #define EF_IMG_RGB 0x200u       /* ef_preprocess: 3/4-channel pixels are RGB(A), not BGR(A)  */
 #define EF_ROI_RECTS_DEVICE 0x400u /* ef_preprocess_rois: rects is a device pointer          */
+#define EF_BANK_GATE_RELATIVE 0x800u /* gated bank calls: gate[m] bounds eps2 / E, not eps2     */
 
 /* kernels whose device time can be queried with ef_timing_get */
 #define EF_KERNEL_SEARCH 0  /* distance GEMM + fused arg-best   */
@@ -70,8 +71,10 @@ extern "C" {
                                 EF_KERNEL_SEARCH (one launch each per frame, as in ef_bank_recognize), and their
                                 two event pairs are recorded inside the scan's span; EF_KERNEL_TMATCH and
                                 EF_KERNEL_INGEST do not count scans */
-#define EF_KERNEL_RECON 9   /* back-projection GEMM of ef_reconstruct / ef_face_distance with its epilogue */
-#define EF_KERNEL_RECON_REDUCE 10 /* ef_face_distance: the fixed-order sum of the pixel splits' partials */
+#define EF_KERNEL_RECON 9   /* back-projection GEMM of ef_reconstruct / ef_face_distance with its epilogue; the
+                               bank's grouped residual GEMM (ef_bank_face_distance and the gated calls) too */
+#define EF_KERNEL_RECON_REDUCE 10 /* ef_face_distance: the fixed-order sum of the pixel splits' partials; the
+                                     bank's grouped reduce too */
 
 /* No-result sentinel in a key array (empty gallery). */
 #define EF_KEY_NONE INT64_MAX
@@ -361,6 +364,64 @@ int ef_bank_recognize(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, in
 int ef_bank_schedule(int64_t b, int64_t d, const int32_t* k, int32_t n_models, int32_t* nsplit,
                      int64_t* pix_per_split, int64_t* n_workgroups, int64_t* scratch_bytes);
 
+/* --------------------------------- model bank: distance from face space and a face gate
+ * Added the same way (by symbol, EF_API_VERSION stays 7).  Turk-Pentland's face / non-face test
+ * (ef_face_distance) for every slot of the bank at once: per (probe, slot)
+ *   dffs2  = sum_j (s_j (p_j - mean_j - (f . R)_j))^2     the distance from slot m's face space
+ *   energy = sum_j (s_j (p_j - mean_j))^2
+ * at slot m's own features f of the probe, the ones ef_bank_recognize returns.
+ *
+ * ef_bank_recon_set gives slot `slot` its way back: R[k*d] and weight[d] (NULL: ones) mean what
+ *   they mean in ef_recon_set, for the slot's k and the bank's d; host pointers, or device
+ *   pointers with EF_MEM_DEVICE.  EF_E_INVALID for a slot outside the bank.  The new state is
+ *   built completely, then published: a failed call (EF_E_NOMEM included) leaves the slot's
+ *   previous state and the bank as they were.  Synchronous on return in both forms.  A later
+ *   ef_bank_add keeps the earlier slots' state; ef_bank_clear and ef_destroy free it.
+ *
+ * ef_bank_face_distance: P[b*d] pixels (EF_U8 or EF_F32), b <= EF_BANK_MAX_PROBES -> dffs2[b][M]
+ *   and, each optional, energy[b][M] and feats[b][sum k] (as ef_bank_recognize lays them out,
+ *   and the same bits: they are the features the residual consumed).  Four launches whatever M
+ *   is: the grouped projection, its reduce, the grouped residual GEMM (timer EF_KERNEL_RECON)
+ *   and its reduce (EF_KERNEL_RECON_REDUCE); no search.  No floating-point atomics: the same
+ *   inputs on the same bank give the same bits on every call.  EF_E_STATE for an empty bank,
+ *   for a bank in which a slot has no reconstruction state (ef_last_error names the first such
+ *   slot), or with a communicator of more than one rank attached.  b = 0 is EF_OK.
+ *
+ * ef_bank_recognize_gated: ef_bank_recognize and ef_bank_face_distance from one projection.
+ *   keys, matches and feats are bit-identical to ef_bank_recognize on the same bank, rows and
+ *   b; dffs2 (required) and energy to ef_bank_face_distance.  Only best_slot differs: the walk
+ *   over models skips slot m for probe p when dffs2[p][m] > bound is true, where bound is
+ *   gate[m], or gate[m] * energy[p][m] (one fp32 multiply) with EF_BANK_GATE_RELATIVE.  The
+ *   comparison is made on the fp32 values returned and is false for NaN, so a gate of +inf or
+ *   NaN rejects nothing and the host can reproduce the decision exactly.  gate[M] is a host
+ *   pointer, or a device pointer with EF_MEM_DEVICE.
+ *
+ * ef_scan_frame_gated: ef_scan_frame whose step e is ef_bank_recognize_gated on the same rows
+ *   (bit-identical to that call with b = n_groups); dets, keys and rows are ef_scan_frame's.
+ *   dffs2[n_groups][M] is required, energy optional.  Host pointers: still one upload of the
+ *   frame (the gate stays resident with the scan plan and travels again only when its values
+ *   change), one download of one pinned result block (it grows only in this call) and one
+ *   synchronisation; EF_MEM_DEVICE: nothing waits on the host.
+ *
+ * ef_bank_recon_schedule (host only, no ctx, no GPU): the grouped residual's plan for b probes
+ * of d pixels against n_models slots: one pixel-split count for the launch (*nsplit, 1 .. 64,
+ * chosen so that ceil(b / 128) x n_models x nsplit is about 512 workgroups, capped at the
+ * number of 128-pixel tiles) of *tiles_per_split tiles each, *n_workgroups = ceil(b / 128) x
+ * n_models x nsplit, and *scratch_bytes = 2 x nsplit x n_models x round_up(b, 128) x 4 of
+ * partials.  Each output is optional; EF_E_INVALID for the sizes ef_bank_schedule rejects. */
+int ef_bank_recon_set(ef_ctx* ctx, int32_t slot, const float* R /* [k*d] */, const float* weight /* [d] or NULL */,
+                      uint32_t flags);
+int ef_bank_face_distance(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, float* dffs2 /* [b][M] */,
+                          float* energy /* [b][M], optional */, float* feats /* [b][sum k], optional */,
+                          uint32_t flags);
+int ef_bank_recognize_gated(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, int32_t metric,
+                            const float* gate /* [M] */, int64_t* keys /* [b][M] */,
+                            ef_match* matches /* [b][M], optional */, int32_t* best_slot /* [b], optional */,
+                            float* dffs2 /* [b][M] */, float* energy /* [b][M], optional */,
+                            float* feats /* [b][sum k], optional */, uint32_t flags);
+int ef_bank_recon_schedule(int64_t b, int64_t d, int32_t n_models, int32_t* nsplit, int32_t* tiles_per_split,
+                           int64_t* n_workgroups, int64_t* scratch_bytes);
+
 /* ------------------------------------------------------------- multi-GPU (RCCL)
  * Row-sharded gallery across the ranks of one job, one process per GPU:
  * rank r sets its shard with ef_gallery_set(..., global_offset = first global row).
@@ -572,6 +633,11 @@ int ef_scan_frame(ef_ctx* ctx, const uint8_t* frame, int64_t frame_ld, int32_t c
                   ef_scan_det* dets /* [n_groups] */, int64_t* keys /* [n_groups][M] */,
                   int32_t* best_slot /* [n_groups], optional */, uint8_t* rows /* [n_groups][face_h*face_w], optional */,
                   uint32_t flags);
+/* the gated form: see ef_bank_recognize_gated above */
+int ef_scan_frame_gated(ef_ctx* ctx, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
+                        const float* gate /* [M] */, ef_scan_det* dets, int64_t* keys, int32_t* best_slot,
+                        uint8_t* rows, float* dffs2 /* [n_groups][M] */, float* energy /* [n_groups][M], optional */,
+                        uint32_t flags);
 
 /* --------------------------------------------------------- Haar cascade detector
  * Replaces face_cascade.detectMultiScale(gray, scaleFactor, minNeighbors, minSize)
