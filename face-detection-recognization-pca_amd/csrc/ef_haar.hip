@@ -29,17 +29,25 @@
 // Float arithmetic follows predictOrderedStump: feature = w0*S0 + w1*S1 (+ w2*S2) in
 // float (no contraction), times the float normalisation factor, compared with the stump
 // threshold; the stage sum accumulates the float leaves in double.
+//
+// ef_haar_scan_frame (the Haar live loop of useless/scan.py:168-290 in one call) queues the
+// same kernels from a plan made once by ef_haar_scan_prepare (`haar_geometry`; the queue-only
+// parts `haar_queue_front` and `haar_queue_groups` serve both entries), then the grouping on
+// the device (ef_haar_group.hip), the crops' resize read in place from the grey plane and the
+// model bank's recognise: one upload, one download, one wait.
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
-#include "ef_internal.hpp"
+#include "ef_haar.hpp"
 
 namespace ef {
 
@@ -70,15 +78,6 @@ struct HaarStage {
   int first, count;
   float thr;
   int pad;
-};
-struct HaarLayer {
-  int w, h, nx, ny, step;
-  float scale;
-  int64_t pix_off, ii_off, res_off;
-};
-struct HaarCand {
-  int layer, y, x;
-  float vnf;  // the window's normalisation factor (stage 0's haar_norm), carried along the lists
 };
 
 // ------------------------------------------------------------------ integral images
@@ -432,11 +431,41 @@ __global__ __launch_bounds__(NQ * 64) void haar_cascade_split_kernel(const HaarL
 }
 
 // ------------------------------------------------------------------ host side
+// What a frame size and the detectMultiScale parameters fix: the pyramid's layers, the row
+// table of the scan walk and the sizes of every buffer.  ef_haar_detect derives it per call,
+// ef_haar_scan_prepare once.
+struct HaarGeom {
+  int H = 0, W = 0, nl = 0, cap = 0, maxh = 0, maxw = 0;
+  int64_t pix = 0, ii = 0, resn = 0, maxpos = 0, max_out = 0, visitable = 0;
+  std::vector<HaarLayer> layers;
+  std::vector<int> row_start;
+  std::vector<char> desc;  // one resize descriptor per layer (img_desc_fill)
+};
+
+// ef_haar_scan_prepare's plan.  It owns its copies of the layer, row and descriptor tables (an
+// ef_haar_detect call in between rewrites the state's own); the pyramid, integral images and
+// lists are the state's, shared with ef_haar_detect.  The result block of one frame is one
+// device allocation [head | rects | keys | best slots | rows | dffs2 | energy] (each piece
+// 256-byte aligned) with a pinned mirror, so a host call downloads it with one copy.
+struct HaarScanPlan {
+  HaarGeom g;
+  int min_neighbors = 0, face_h = 0, face_w = 0, max_faces = 0, max_cand = 0;
+  DevBuf layers, rowstart, desc;
+  DevBuf frame_in;  // a host call's frame, H rows of W * channels bytes
+  DevBuf gray;      // the grey plane of a colour frame (or a strided grey one), round_up(H * W, 4) bytes
+  DevBuf group;     // HaarGroupWs carve-out for max_cand rectangles
+  DevBuf out;       // the result block
+  PinnedBuf host;   // its pinned mirror
+  DevBuf gate;      // a host call's gate stays resident (uploaded again when its values change)
+  std::vector<float> gate_host;
+};
+
 struct HaarState {
   int ww = 0, wh = 0, nstages = 0;
   bool order_free = false;  // every stage sum is exact in double in any order (see set_cascade)
   DevBuf stages, recs;
   DevBuf pix, ii1, ii2, res, vn, layers, rowstart, work, cand, counters, frame, desc;
+  std::unique_ptr<HaarScanPlan> scan;  // null until ef_haar_scan_prepare
 };
 
 void haar_release(ef_ctx* c) {
@@ -517,6 +546,199 @@ static std::vector<RectI> group_rectangles(const std::vector<RectI>& rects, int 
     if (j == nc) out.push_back(r1);
   }
   return out;
+}
+
+// detectMultiScaleNoGrouping's scale list and FeatureEvaluator::updateScaleData's layers for an
+// H x W frame, with the row table, the resize descriptors and the buffer sizes.  g.nl = 0: no
+// layer holds a window.
+static int haar_geometry(ef_ctx* c, const HaarState* h, const std::string& who, int H, int W, double scale_factor,
+                         int min_w, int min_h, int max_w, int max_h, HaarGeom& g) {
+  g = HaarGeom{};
+  g.H = H;
+  g.W = W;
+  const int mw = (max_w > 0 && max_h > 0) ? max_w : W, mh = (max_w > 0 && max_h > 0) ? max_h : H;
+  std::vector<float> scales;
+  for (double factor = 1.0;; factor *= scale_factor) {
+    const int sw = cv_round(h->ww * factor), sh = cv_round(h->wh * factor);
+    if (sw > mw || sh > mh) break;
+    if (sw < min_w || sh < min_h) continue;
+    scales.push_back((float)factor);
+  }
+  for (float sc : scales) {
+    HaarLayer ly{};
+    ly.w = cv_round((float)W / sc);
+    ly.h = cv_round((float)H / sc);
+    ly.nx = std::max(ly.w + 1 - h->ww, 0);
+    ly.ny = std::max(ly.h + 1 - h->wh, 0);
+    ly.step = sc >= 2.f ? 1 : 2;
+    ly.scale = sc;
+    ly.pix_off = g.pix;
+    ly.ii_off = g.ii;
+    ly.res_off = g.resn;
+    g.pix += (int64_t)ly.w * ly.h;
+    g.ii += (int64_t)(ly.w + 1) * (ly.h + 1);
+    g.resn += (int64_t)ly.nx * ly.ny;
+    if (ly.nx > 0 && ly.ny > 0) g.layers.push_back(ly);
+  }
+  g.nl = (int)g.layers.size();
+  if (g.nl == 0) return EF_OK;
+  if (g.nl > kHaarMaxLayers)
+    return set_err(c, EF_E_INVALID, who + ": more than " + std::to_string(kHaarMaxLayers) +
+                                        " pyramid layers (scale factor too close to 1)");
+  g.row_start.assign(g.nl + 1, 0);
+  for (int i = 0; i < g.nl; ++i)
+    g.row_start[i + 1] = g.row_start[i] + (g.layers[i].ny + g.layers[i].step - 1) / g.layers[i].step;
+  // candidate / work-list capacity: every window origin the invoker can visit (a 1080p
+  // frame at minSize 30 has ~3.5 M; a cascade whose stage 0 passes most of them must not
+  // overflow a fixed list)
+  for (const auto& ly : g.layers) {
+    const int64_t pos = (int64_t)((ly.nx + ly.step - 1) / ly.step) * ((ly.ny + ly.step - 1) / ly.step);
+    g.visitable += pos;
+    g.maxpos = std::max(g.maxpos, pos);
+    g.maxh = std::max(g.maxh, ly.h);
+    g.maxw = std::max(g.maxw, ly.w);
+  }
+  if (g.visitable > INT_MAX / 2) return set_err(c, EF_E_INVALID, who + ": frame too large");
+  g.cap = (int)std::max<int64_t>(g.visitable, 1024);
+  g.desc.resize(g.layers.size() * img_desc_size());
+  for (int i = 0; i < g.nl; ++i) {
+    img_desc_fill(g.desc.data() + i * img_desc_size(), 0, g.layers[i].pix_off, H, W, 1, g.layers[i].h, g.layers[i].w);
+    g.max_out = std::max<int64_t>(g.max_out, (int64_t)g.layers[i].w * g.layers[i].h);
+  }
+  return EF_OK;
+}
+
+// the state's per-frame buffers, grown to g's sizes
+static int haar_ensure(ef_ctx* c, HaarState* h, const HaarGeom& g) {
+  EF_TRY(ensure(c, h->pix, g.pix));
+  EF_TRY(ensure(c, h->ii1, g.ii * 4));
+  EF_TRY(ensure(c, h->ii2, g.ii * 4));
+  EF_TRY(ensure(c, h->res, std::max<int64_t>(g.resn, 16)));
+  EF_TRY(ensure(c, h->vn, std::max<int64_t>(g.resn * 4, 16)));
+  EF_TRY(ensure(c, h->work, (size_t)g.cap * sizeof(HaarCand)));
+  EF_TRY(ensure(c, h->cand, (size_t)g.cap * sizeof(HaarCand)));
+  EF_TRY(ensure(c, h->counters, 64));
+  return EF_OK;
+}
+
+// Queue-only, shared by ef_haar_detect and ef_haar_scan_frame: the pyramid of the packed grey
+// frame src (rows of g.W bytes), the integral images, stage 0 and the scan walk, which leaves
+// the stage-0 survivors in h->work and their count in counters[0] (zeroed by the caller).
+// dl, drows, ddesc: g's layer, row and descriptor tables on the device.
+static int haar_queue_front(ef_ctx* c, HaarState* h, const HaarGeom& g, const uint8_t* src, const HaarLayer* dl,
+                            const int* drows, const void* ddesc) {
+  hipStream_t s = c->stream;
+  const int nl = g.nl;
+  EF_HIP(c, launch_resize_gray(s, src, ddesc, nl, g.max_out, static_cast<uint8_t*>(h->pix.p)), "pyramid");
+  int* ii1 = static_cast<int*>(h->ii1.p);
+  unsigned* ii2 = static_cast<unsigned*>(h->ii2.p);
+  const uint8_t* lp = static_cast<const uint8_t*>(h->pix.p);
+  hipLaunchKernelGGL(haar_rows_ii_kernel, dim3((unsigned)((g.maxh + 1 + 3) / 4), (unsigned)nl), dim3(256), 0, s, lp, dl,
+                     ii1, ii2);
+  hipLaunchKernelGGL(haar_cols_ii_kernel, dim3((unsigned)((g.maxw + 1 + 63) / 64), (unsigned)nl), dim3(1024), 0, s, dl,
+                     ii1, ii2);
+  const HaarStage* dst = static_cast<const HaarStage*>(h->stages.p);
+  const HaarRec* drc = static_cast<const HaarRec*>(h->recs.p);
+  signed char* res = static_cast<signed char*>(h->res.p);
+  hipLaunchKernelGGL(haar_stage0_kernel, dim3((unsigned)((g.maxpos + 255) / 256), (unsigned)nl), dim3(256), 0, s, dl, ii1,
+                     ii2, dst, drc, h->ww, h->wh, res, static_cast<float*>(h->vn.p));
+  hipLaunchKernelGGL(haar_rows_kernel, dim3((unsigned)((g.row_start[nl] + kHaarRowWaves - 1) / kHaarRowWaves)),
+                     dim3(64 * kHaarRowWaves), 0, s, dl, nl, drows, res, static_cast<const float*>(h->vn.p),
+                     static_cast<HaarCand*>(h->work.p), static_cast<int*>(h->counters.p), g.cap);
+  return EF_OK;
+}
+
+// Queue-only, shared likewise: the stage groups over the stage-0 survivors.  live: an upper
+// bound of every group's input, which sizes the grids (the workgroups past a list's device
+// count leave at once); the lists ping-pong between h->work and h->cand, group gi reads
+// counters[gi] and writes counters[gi + 1].  *last_gi: the counter of the final list, *last:
+// that list (all of stage 0's survivors when the cascade has one stage).
+static void haar_queue_groups(ef_ctx* c, HaarState* h, const HaarLayer* dl, int live, int cap, int* last_gi,
+                              HaarCand** last) {
+  hipStream_t s = c->stream;
+  int* ii1 = static_cast<int*>(h->ii1.p);
+  unsigned* ii2 = static_cast<unsigned*>(h->ii2.p);
+  const HaarStage* dst = static_cast<const HaarStage*>(h->stages.p);
+  const HaarRec* drc = static_cast<const HaarRec*>(h->recs.p);
+  int* cnt = static_cast<int*>(h->counters.p);
+  // stage groups; the lists ping-pong between work and cand, counters cnt[g]
+  // EF_HAAR_GROUPS="1,4,8,14" (experiments): first stage of each group, ascending, <= 14.
+  // Default {1, 4, 8, 14} (tools/haar_groups.sh, 640x480 synthetic frontal cascade, ms per
+  // frame): 1,3,6,10,15 0.532; 1,4,8,14 0.490; 1,6,12 0.487; 1,4,9 0.497; eleven or twelve
+  // groups 0.61-0.64 — fewer, longer groups win until the dead lanes of a long group cost
+  // more than a launch and a compaction.
+  static const std::vector<int> groups = [] {
+    std::vector<int> g;
+#ifdef EF_DIAGNOSTICS
+    if (const char* e = getenv("EF_HAAR_GROUPS")) {
+      for (const char* p = e; *p;) {
+        const int v = atoi(p);
+        if (v >= 1 && (g.empty() || v > g.back()) && g.size() < 14) g.push_back(v);
+        while (*p && *p != ',') ++p;
+        if (*p == ',') ++p;
+      }
+    }
+#endif
+    if (g.empty() || g[0] != 1) g = {1, 4, 8, 14};
+    g.push_back(1 << 30);
+    return g;
+  }();
+  // every group takes the split form when the cascade's stage sums are order-free
+  // (measured, 640x480 synthetic frontal cascade with LDS stump records and 8 waves: split
+  // from group 1 0.637 ms, from stage 3 0.652, from stage 6 0.673 per frame)
+#ifdef EF_DIAGNOSTICS  // experiments: first split-form stage group, waves per split workgroup
+  static const int kHaarSplitFrom = [] { const char* e = getenv("EF_HAAR_SPLIT_FROM"); return e ? atoi(e) : 1; }();
+  static const int split_waves = [] {
+    const char* e = getenv("EF_HAAR_SPLITW");
+    const int v = e ? atoi(e) : 8;
+    return v == 4 || v == 16 ? v : 8;
+  }();
+#else
+  constexpr int kHaarSplitFrom = 1, split_waves = 8;
+#endif
+  int gi = 0;
+  HaarCand* bin = static_cast<HaarCand*>(h->work.p);
+  HaarCand* bout = static_cast<HaarCand*>(h->cand.p);
+  for (; groups[gi] < h->nstages; ++gi) {
+    const int s0 = groups[gi], s1 = std::min(groups[gi + 1], h->nstages);
+    if (live > 0 && h->order_free && s0 >= kHaarSplitFrom) {
+      const dim3 g((unsigned)((live + 63) / 64));
+      if (split_waves == 16)
+        hipLaunchKernelGGL(haar_cascade_split_kernel<16>, g, dim3(1024), 0, s, dl, ii1, ii2, dst, s0, s1, drc, h->ww,
+                           h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
+      else if (split_waves == 8)
+        hipLaunchKernelGGL(haar_cascade_split_kernel<8>, g, dim3(512), 0, s, dl, ii1, ii2, dst, s0, s1, drc, h->ww,
+                           h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
+      else
+        hipLaunchKernelGGL(haar_cascade_split_kernel<4>, g, dim3(256), 0, s, dl, ii1, ii2, dst, s0, s1, drc, h->ww,
+                           h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
+    } else if (live > 0)
+      hipLaunchKernelGGL(haar_cascade_kernel, dim3((unsigned)((live + 255) / 256)), dim3(256), 0, s, dl, ii1, ii2, dst,
+                         s0, s1, drc, h->ww, h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
+    std::swap(bin, bout);
+  }
+  *last_gi = gi;
+  *last = bin;
+}
+
+// The pieces of a Haar scan's result block for g faces, M bank slots and d face pixels.
+struct HaarScanOut {
+  ef_haar_scan_head* head;
+  int* rects;
+  long long* keys;
+  int* best;
+  uint8_t* rows;
+  float* dffs2;
+  float* energy;
+};
+static HaarScanOut carve_haar_scan_out(Carve& cv, size_t g, size_t M, size_t d, bool gated) {
+  HaarScanOut o{cv.take<ef_haar_scan_head>(1), cv.take<int>(g * 4), cv.take<long long>(g * M), cv.take<int>(g),
+                cv.take<uint8_t>(g * d),       nullptr,             nullptr};
+  if (gated) {
+    o.dffs2 = cv.take<float>(g * M);
+    o.energy = cv.take<float>(g * M);
+  }
+  return o;
 }
 
 }  // namespace ef
@@ -638,61 +860,17 @@ int ef_haar_detect(ef_ctx* c, const uint8_t* gray, int32_t H, int32_t W, int64_t
     return set_err(c, EF_E_INVALID, "ef_haar_detect: bad arguments");
   EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
   hipStream_t s = c->stream;
-  const int mw = (max_w > 0 && max_h > 0) ? max_w : W, mh = (max_w > 0 && max_h > 0) ? max_h : H;
-  // detectMultiScaleNoGrouping's scale list and FeatureEvaluator::updateScaleData's layers
-  std::vector<HaarLayer> layers;
-  std::vector<float> scales;
-  for (double factor = 1.0;; factor *= scale_factor) {
-    const int sw = cv_round(h->ww * factor), sh = cv_round(h->wh * factor);
-    if (sw > mw || sh > mh) break;
-    if (sw < min_w || sh < min_h) continue;
-    scales.push_back((float)factor);
-  }
-  int64_t pix = 0, ii = 0, resn = 0;
-  for (float sc : scales) {
-    HaarLayer ly{};
-    ly.w = cv_round((float)W / sc);
-    ly.h = cv_round((float)H / sc);
-    ly.nx = std::max(ly.w + 1 - h->ww, 0);
-    ly.ny = std::max(ly.h + 1 - h->wh, 0);
-    ly.step = sc >= 2.f ? 1 : 2;
-    ly.scale = sc;
-    ly.pix_off = pix;
-    ly.ii_off = ii;
-    ly.res_off = resn;
-    pix += (int64_t)ly.w * ly.h;
-    ii += (int64_t)(ly.w + 1) * (ly.h + 1);
-    resn += (int64_t)ly.nx * ly.ny;
-    if (ly.nx > 0 && ly.ny > 0) layers.push_back(ly);
-  }
+  HaarGeom g;
   *n_rects = 0;
   if (n_cand) *n_cand = 0;
-  if (layers.empty()) return EF_OK;
-  const int nl = (int)layers.size();
-  if (nl > kHaarMaxLayers)
-    return set_err(c, EF_E_INVALID, "ef_haar_detect: more than " + std::to_string(kHaarMaxLayers) +
-                                        " pyramid layers (scale factor too close to 1)");
-  std::vector<int> row_start(nl + 1, 0);
-  for (int i = 0; i < nl; ++i) row_start[i + 1] = row_start[i] + (layers[i].ny + layers[i].step - 1) / layers[i].step;
-  // candidate / work-list capacity: every window origin the invoker can visit (a 1080p
-  // frame at minSize 30 has ~3.5 M; a cascade whose stage 0 passes most of them must not
-  // overflow a fixed list)
-  int64_t visitable = 0;
-  for (const auto& ly : layers)
-    visitable += (int64_t)((ly.nx + ly.step - 1) / ly.step) * ((ly.ny + ly.step - 1) / ly.step);
-  if (visitable > INT_MAX / 2) return set_err(c, EF_E_INVALID, "ef_haar_detect: frame too large");
-  const int cap = (int)std::max<int64_t>(visitable, 1024);
-  EF_TRY(ensure(c, h->pix, pix));
-  EF_TRY(ensure(c, h->ii1, ii * 4));
-  EF_TRY(ensure(c, h->ii2, ii * 4));
-  EF_TRY(ensure(c, h->res, std::max<int64_t>(resn, 16)));
-  EF_TRY(ensure(c, h->vn, std::max<int64_t>(resn * 4, 16)));
+  EF_TRY(haar_geometry(c, h, "ef_haar_detect", H, W, scale_factor, min_w, min_h, max_w, max_h, g));
+  if (g.nl == 0) return EF_OK;
+  const int cap = g.cap;
+  const std::vector<HaarLayer>& layers = g.layers;
+  EF_TRY(haar_ensure(c, h, g));
   EF_TRY(ensure(c, h->layers, layers.size() * sizeof(HaarLayer)));
-  EF_TRY(ensure(c, h->rowstart, row_start.size() * sizeof(int)));
-  EF_TRY(ensure(c, h->work, (size_t)cap * sizeof(HaarCand)));
-  EF_TRY(ensure(c, h->cand, (size_t)cap * sizeof(HaarCand)));
-  EF_TRY(ensure(c, h->counters, 64));
-  EF_TRY(ensure(c, h->desc, layers.size() * img_desc_size()));
+  EF_TRY(ensure(c, h->rowstart, g.row_start.size() * sizeof(int)));
+  EF_TRY(ensure(c, h->desc, g.desc.size()));
   const uint8_t* src = gray;
   if (!(flags & EF_MEM_DEVICE) || ld != W) {
     EF_TRY(ensure(c, h->frame, (size_t)H * W));
@@ -701,109 +879,24 @@ int ef_haar_detect(ef_ctx* c, const uint8_t* gray, int32_t H, int32_t W, int64_t
            "frame");
     src = static_cast<const uint8_t*>(h->frame.p);
   }
-  std::vector<char> desc(layers.size() * img_desc_size());
-  int64_t max_out = 0;
-  for (int i = 0; i < nl; ++i) {
-    img_desc_fill(desc.data() + i * img_desc_size(), 0, layers[i].pix_off, H, W, 1, layers[i].h, layers[i].w);
-    max_out = std::max<int64_t>(max_out, (int64_t)layers[i].w * layers[i].h);
-  }
-  EF_HIP(c, hipMemcpyAsync(h->desc.p, desc.data(), desc.size(), hipMemcpyHostToDevice, s), "H2D desc");
+  EF_HIP(c, hipMemcpyAsync(h->desc.p, g.desc.data(), g.desc.size(), hipMemcpyHostToDevice, s), "H2D desc");
   EF_HIP(c, hipMemcpyAsync(h->layers.p, layers.data(), layers.size() * sizeof(HaarLayer), hipMemcpyHostToDevice, s),
          "H2D layers");
-  EF_HIP(c, hipMemcpyAsync(h->rowstart.p, row_start.data(), row_start.size() * sizeof(int), hipMemcpyHostToDevice, s),
+  EF_HIP(c, hipMemcpyAsync(h->rowstart.p, g.row_start.data(), g.row_start.size() * sizeof(int), hipMemcpyHostToDevice, s),
          "H2D rows");
   EF_HIP(c, hipMemsetAsync(h->counters.p, 0, 64, s), "memset");
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_HAAR, &tev);
-  EF_HIP(c, launch_resize_gray(s, src, h->desc.p, nl, max_out, static_cast<uint8_t*>(h->pix.p)), "pyramid");
   const HaarLayer* dl = static_cast<const HaarLayer*>(h->layers.p);
-  int* ii1 = static_cast<int*>(h->ii1.p);
-  unsigned* ii2 = static_cast<unsigned*>(h->ii2.p);
-  int maxh = 0, maxw = 0;
-  int64_t maxpos = 0;
-  for (auto& ly : layers) {
-    maxh = std::max(maxh, ly.h);
-    maxw = std::max(maxw, ly.w);
-    maxpos = std::max<int64_t>(maxpos, (int64_t)((ly.nx + ly.step - 1) / ly.step) * ((ly.ny + ly.step - 1) / ly.step));
-  }
-  const uint8_t* lp = static_cast<const uint8_t*>(h->pix.p);
-  hipLaunchKernelGGL(haar_rows_ii_kernel, dim3((unsigned)((maxh + 1 + 3) / 4), (unsigned)nl), dim3(256), 0, s, lp, dl,
-                     ii1, ii2);
-  hipLaunchKernelGGL(haar_cols_ii_kernel, dim3((unsigned)((maxw + 1 + 63) / 64), (unsigned)nl), dim3(1024), 0, s, dl,
-                     ii1, ii2);
-  const HaarStage* dst = static_cast<const HaarStage*>(h->stages.p);
-  const HaarRec* drc = static_cast<const HaarRec*>(h->recs.p);
-  signed char* res = static_cast<signed char*>(h->res.p);
-  hipLaunchKernelGGL(haar_stage0_kernel, dim3((unsigned)((maxpos + 255) / 256), (unsigned)nl), dim3(256), 0, s, dl, ii1,
-                     ii2, dst, drc, h->ww, h->wh, res, static_cast<float*>(h->vn.p));
+  EF_TRY(haar_queue_front(c, h, g, src, dl, static_cast<const int*>(h->rowstart.p), h->desc.p));
   int* cnt = static_cast<int*>(h->counters.p);
-  HaarCand* work = static_cast<HaarCand*>(h->work.p);
-  HaarCand* cand = static_cast<HaarCand*>(h->cand.p);
-  hipLaunchKernelGGL(haar_rows_kernel, dim3((unsigned)((row_start[nl] + kHaarRowWaves - 1) / kHaarRowWaves)),
-                     dim3(64 * kHaarRowWaves), 0, s, dl, nl,
-                     static_cast<const int*>(h->rowstart.p), res, static_cast<const float*>(h->vn.p), work, cnt,
-                     cap);
   int hc[16] = {0};
   EF_HIP(c, hipMemcpyAsync(hc, cnt, sizeof(int), hipMemcpyDeviceToHost, s), "D2H work count");
   EF_HIP(c, hipStreamSynchronize(s), "sync");
   if (hc[0] > cap) return set_err(c, EF_E_INVALID, "ef_haar_detect: work-list capacity exceeded");
-  // stage groups; the lists ping-pong between work and cand, counters cnt[g]
-  // EF_HAAR_GROUPS="1,4,8,14" (experiments): first stage of each group, ascending, <= 14.
-  // Default {1, 4, 8, 14} (tools/haar_groups.sh, 640x480 synthetic frontal cascade, ms per
-  // frame): 1,3,6,10,15 0.532; 1,4,8,14 0.490; 1,6,12 0.487; 1,4,9 0.497; eleven or twelve
-  // groups 0.61-0.64 — fewer, longer groups win until the dead lanes of a long group cost
-  // more than a launch and a compaction.
-  static const std::vector<int> groups = [] {
-    std::vector<int> g;
-#ifdef EF_DIAGNOSTICS
-    if (const char* e = getenv("EF_HAAR_GROUPS")) {
-      for (const char* p = e; *p;) {
-        const int v = atoi(p);
-        if (v >= 1 && (g.empty() || v > g.back()) && g.size() < 14) g.push_back(v);
-        while (*p && *p != ',') ++p;
-        if (*p == ',') ++p;
-      }
-    }
-#endif
-    if (g.empty() || g[0] != 1) g = {1, 4, 8, 14};
-    g.push_back(1 << 30);
-    return g;
-  }();
-  // every group takes the split form when the cascade's stage sums are order-free
-  // (measured, 640x480 synthetic frontal cascade with LDS stump records and 8 waves: split
-  // from group 1 0.637 ms, from stage 3 0.652, from stage 6 0.673 per frame)
-#ifdef EF_DIAGNOSTICS  // experiments: first split-form stage group, waves per split workgroup
-  static const int kHaarSplitFrom = [] { const char* e = getenv("EF_HAAR_SPLIT_FROM"); return e ? atoi(e) : 1; }();
-  static const int split_waves = [] {
-    const char* e = getenv("EF_HAAR_SPLITW");
-    const int v = e ? atoi(e) : 8;
-    return v == 4 || v == 16 ? v : 8;
-  }();
-#else
-  constexpr int kHaarSplitFrom = 1, split_waves = 8;
-#endif
   int gi = 0;
-  const int live = hc[0];  // upper bound of every group's input
-  HaarCand* bin = work;
-  HaarCand* bout = cand;
-  for (; groups[gi] < h->nstages; ++gi) {
-    const int s0 = groups[gi], s1 = std::min(groups[gi + 1], h->nstages);
-    if (live > 0 && h->order_free && s0 >= kHaarSplitFrom) {
-      const dim3 g((unsigned)((live + 63) / 64));
-      if (split_waves == 16)
-        hipLaunchKernelGGL(haar_cascade_split_kernel<16>, g, dim3(1024), 0, s, dl, ii1, ii2, dst, s0, s1, drc, h->ww,
-                           h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
-      else if (split_waves == 8)
-        hipLaunchKernelGGL(haar_cascade_split_kernel<8>, g, dim3(512), 0, s, dl, ii1, ii2, dst, s0, s1, drc, h->ww,
-                           h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
-      else
-        hipLaunchKernelGGL(haar_cascade_split_kernel<4>, g, dim3(256), 0, s, dl, ii1, ii2, dst, s0, s1, drc, h->ww,
-                           h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
-    } else if (live > 0)
-      hipLaunchKernelGGL(haar_cascade_kernel, dim3((unsigned)((live + 255) / 256)), dim3(256), 0, s, dl, ii1, ii2, dst,
-                         s0, s1, drc, h->ww, h->wh, bin, cnt + gi, cap, bout, cnt + gi + 1);
-    std::swap(bin, bout);
-  }
+  HaarCand* cand = nullptr;
+  haar_queue_groups(c, h, dl, hc[0], cap, &gi, &cand);  // hc[0]: upper bound of every group's input
   timer_end(c, &tev);
   EF_HIP(c, hipGetLastError(), "haar kernels");
   EF_HIP(c, hipMemcpyAsync(hc, cnt, 16 * sizeof(int), hipMemcpyDeviceToHost, s), "D2H counts");
@@ -811,12 +904,11 @@ int ef_haar_detect(ef_ctx* c, const uint8_t* gray, int32_t H, int32_t W, int64_t
 #ifdef EF_DIAGNOSTICS
   if (getenv("EF_HAAR_DEBUG")) {
     fprintf(stderr, "[ef_haar] stage-group inputs:");
-    for (int g = 0; g <= gi; ++g) fprintf(stderr, " %d", hc[g]);
+    for (int q = 0; q <= gi; ++q) fprintf(stderr, " %d", hc[q]);
     fprintf(stderr, "\n");
   }
 #endif
   hc[1] = hc[gi];  // survivors of the last group (all of stage 0's when the cascade has 1 stage)
-  cand = bin;
   if (hc[1] > cap) return set_err(c, EF_E_INVALID, "ef_haar_detect: candidate capacity exceeded");
   std::vector<HaarCand> hcand((size_t)hc[1]);
   if (hc[1] > 0)
@@ -838,11 +930,185 @@ int ef_haar_detect(ef_ctx* c, const uint8_t* gray, int32_t H, int32_t W, int64_t
       cand_out[4 * i] = rects[i].x, cand_out[4 * i + 1] = rects[i].y;
       cand_out[4 * i + 2] = rects[i].w, cand_out[4 * i + 3] = rects[i].h;
     }
-  const std::vector<RectI> g = group_rectangles(rects, min_neighbors, 0.2);
-  *n_rects = (int32_t)g.size();
-  for (int i = 0; i < (int)g.size() && i < max_rects; ++i) {
-    rects_out[4 * i] = g[i].x, rects_out[4 * i + 1] = g[i].y, rects_out[4 * i + 2] = g[i].w, rects_out[4 * i + 3] = g[i].h;
+  const std::vector<RectI> gr = group_rectangles(rects, min_neighbors, 0.2);
+  *n_rects = (int32_t)gr.size();
+  for (int i = 0; i < (int)gr.size() && i < max_rects; ++i) {
+    rects_out[4 * i] = gr[i].x, rects_out[4 * i + 1] = gr[i].y, rects_out[4 * i + 2] = gr[i].w, rects_out[4 * i + 3] = gr[i].h;
   }
+  return EF_OK;
+}
+
+int ef_haar_scan_prepare(ef_ctx* c, int32_t frame_h, int32_t frame_w, double scale_factor, int32_t min_neighbors,
+                         int32_t min_w, int32_t min_h, int32_t max_w, int32_t max_h, int32_t face_h, int32_t face_w,
+                         int32_t max_faces, int32_t max_candidates) {
+  if (!c) return EF_E_INVALID;
+  HaarState* h = c->haar;
+  if (!h) return set_err(c, EF_E_STATE, "ef_haar_scan_prepare: call ef_haar_set_cascade first");
+  if (frame_h < 1 || frame_w < 1 || !(scale_factor > 1.0) || min_neighbors < 1 || face_h <= 0 || face_w <= 0 ||
+      max_faces < 1 || max_faces > EF_BANK_MAX_PROBES || max_candidates < 1 || max_candidates > kHaarGroupMax)
+    return set_err(c, EF_E_INVALID, "ef_haar_scan_prepare: bad arguments");
+  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+  // the stream may still run a frame of the old plan
+  EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  h->scan.reset();
+  std::unique_ptr<HaarScanPlan> sp(new HaarScanPlan());
+  EF_TRY(haar_geometry(c, h, "ef_haar_scan_prepare", frame_h, frame_w, scale_factor, min_w, min_h, max_w, max_h, sp->g));
+  const HaarGeom& g = sp->g;
+  sp->min_neighbors = min_neighbors;
+  sp->face_h = face_h;
+  sp->face_w = face_w;
+  sp->max_faces = max_faces;
+  sp->max_cand = max_candidates;
+  if (g.nl == 0) sp->g.cap = 1024;  // no layer holds a window: the lists stay empty
+  EF_TRY(haar_ensure(c, h, g));
+  EF_TRY(ensure(c, sp->gray, (size_t)round_up((int64_t)frame_h * frame_w, 4)));
+  Carve gw;
+  carve_haar_group_ws(gw, (size_t)max_candidates);
+  EF_TRY(ensure(c, sp->group, gw.total));
+  if (g.nl > 0) {
+    EF_TRY(ensure(c, sp->layers, g.layers.size() * sizeof(HaarLayer)));
+    EF_TRY(ensure(c, sp->rowstart, g.row_start.size() * sizeof(int)));
+    EF_TRY(ensure(c, sp->desc, g.desc.size()));
+    EF_HIP(c, hipMemcpyAsync(sp->desc.p, g.desc.data(), g.desc.size(), hipMemcpyHostToDevice, c->stream), "H2D desc");
+    EF_HIP(c, hipMemcpyAsync(sp->layers.p, g.layers.data(), g.layers.size() * sizeof(HaarLayer), hipMemcpyHostToDevice,
+                             c->stream), "H2D layers");
+    EF_HIP(c, hipMemcpyAsync(sp->rowstart.p, g.row_start.data(), g.row_start.size() * sizeof(int), hipMemcpyHostToDevice,
+                             c->stream), "H2D rows");
+    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  }
+  h->scan = std::move(sp);
+  return EF_OK;
+}
+
+int ef_haar_scan_info(ef_ctx* c, int32_t* n_layers, int64_t* visitable, int32_t* max_faces, int32_t* max_candidates) {
+  if (!c) return EF_E_INVALID;
+  const HaarScanPlan* sp = c->haar ? c->haar->scan.get() : nullptr;
+  if (!sp) return set_err(c, EF_E_STATE, "ef_haar_scan_info: no plan (call ef_haar_set_cascade, then ef_haar_scan_prepare)");
+  if (n_layers) *n_layers = sp->g.nl;
+  if (visitable) *visitable = sp->g.visitable;
+  if (max_faces) *max_faces = sp->max_faces;
+  if (max_candidates) *max_candidates = sp->max_cand;
+  return EF_OK;
+}
+
+int ef_haar_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
+                       const float* gate, ef_haar_scan_head* head, int32_t* rects, int64_t* keys, int32_t* best_slot,
+                       uint8_t* rows, float* dffs2, float* energy, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  const std::string w("ef_haar_scan_frame");
+  HaarState* h = c->haar;
+  HaarScanPlan* sp = h ? h->scan.get() : nullptr;
+  if (!sp) return set_err(c, EF_E_STATE, w + ": no plan (call ef_haar_set_cascade, then ef_haar_scan_prepare)");
+  Bank& bk = c->bank;
+  if (bk.slots.empty()) return set_err(c, EF_E_STATE, w + ": the bank is empty (call ef_bank_add)");
+  const int64_t d = (int64_t)sp->face_h * sp->face_w;
+  if (bk.d != d)
+    return set_err(c, EF_E_STATE, w + ": the bank's models take " + std::to_string(bk.d) +
+                                      " pixels, the plan's faces have " + std::to_string(d));
+  if (c->comm && c->comm_size > 1) return set_err(c, EF_E_STATE, w + ": not available with a communicator attached");
+  if (gate) EF_TRY(bank_recon_complete(c, w.c_str()));
+  const HaarGeom& g = sp->g;
+  const int H = g.H, W = g.W, F = sp->max_faces;
+  if (!frame || !head || !rects || !keys || (channels != 1 && channels != 3 && channels != 4) ||
+      frame_ld < (int64_t)W * channels || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE) || (gate && !dffs2))
+    return set_err(c, EF_E_INVALID, w + ": bad arguments");
+  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+  const bool dev = flags & EF_MEM_DEVICE;
+  hipStream_t s = c->stream;
+  const size_t M = bk.slots.size();
+  // an ef_haar_detect of a larger frame in between may have regrown (moved) the state's buffers:
+  // growing them here is a no-op otherwise
+  EF_TRY(haar_ensure(c, h, g));
+
+  // where the kernels write: the caller's device arrays, or the result block; the rows always
+  // exist (the bank reads them)
+  Carve size_out, cv;
+  const bool gated = gate != nullptr;
+  carve_haar_scan_out(size_out, (size_t)F, M, (size_t)d, gated);
+  HaarScanOut o{head, rects, reinterpret_cast<long long*>(keys), best_slot, rows, dffs2, energy};
+  if (!dev || !rows || (gated && !energy)) {
+    EF_TRY(ensure(c, sp->out, size_out.total));
+    cv.base = sp->out.p;
+    const HaarScanOut blk = carve_haar_scan_out(cv, (size_t)F, M, (size_t)d, gated);
+    if (!dev) {
+      o = blk;
+    } else {
+      if (!rows) o.rows = blk.rows;
+      if (!energy) o.energy = blk.energy;
+    }
+  }
+  BankGate bg{gate, (flags & EF_BANK_GATE_RELATIVE) != 0, o.dffs2, o.energy};
+  if (gated && !dev) {
+    if (sp->gate_host.size() != M || std::memcmp(sp->gate_host.data(), gate, M * sizeof(float)) != 0) {
+      try {
+        sp->gate_host.assign(gate, gate + M);
+      } catch (const std::bad_alloc&) {
+        return set_err(c, EF_E_NOMEM, w + ": host allocation failed");
+      }
+      const hipError_t e = [&] {
+        if (ensure(c, sp->gate, M * sizeof(float)) != EF_OK) return hipErrorOutOfMemory;
+        return hipMemcpyAsync(sp->gate.p, sp->gate_host.data(), M * sizeof(float), hipMemcpyHostToDevice, s);
+      }();
+      if (e != hipSuccess) {
+        sp->gate_host.clear();  // nothing resident: the next call uploads again
+        return hip_err(c, e, "H2D gate");
+      }
+    }
+    bg.gate = static_cast<const float*>(sp->gate.p);
+  }
+  if (!dev && sp->host.bytes < size_out.total) EF_HIP(c, pinned_alloc(sp->host, size_out.total), "pinned results");
+  const uint8_t* f = frame;
+  if (!dev) {
+    const int64_t row_bytes = (int64_t)W * channels;
+    EF_TRY(ensure(c, sp->frame_in, (size_t)H * row_bytes));
+    EF_HIP(c, hipMemcpy2DAsync(sp->frame_in.p, row_bytes, frame, frame_ld, row_bytes, H, hipMemcpyHostToDevice, s),
+           "H2D frame");
+    f = static_cast<const uint8_t*>(sp->frame_in.p);
+    frame_ld = row_bytes;
+  }
+  EF_HIP(c, hipMemsetAsync(h->counters.p, 0, 64, s), "memset");
+  TimerEvt tev;
+  timer_begin(c, EF_KERNEL_HAAR_SCAN, &tev);
+  if (channels != 1) {
+    EF_HIP(c, launch_frame_gray(s, f, frame_ld, H, W, channels, flags & EF_IMG_RGB, sp->gray.p), "frame grey kernel");
+    f = static_cast<const uint8_t*>(sp->gray.p);
+  } else if (frame_ld != W) {  // the pyramid reads packed rows
+    EF_HIP(c, hipMemcpy2DAsync(sp->gray.p, W, f, frame_ld, W, H, hipMemcpyDeviceToDevice, s), "pack grey frame");
+    f = static_cast<const uint8_t*>(sp->gray.p);
+  }
+  int gi = 0;
+  HaarCand* cand = static_cast<HaarCand*>(h->work.p);
+  const HaarLayer* dl = static_cast<const HaarLayer*>(sp->layers.p);
+  if (g.nl > 0) {
+    EF_TRY(haar_queue_front(c, h, g, f, dl, static_cast<const int*>(sp->rowstart.p), sp->desc.p));
+    // no count comes back to the host: the stage groups' grids cover the plan's bound
+    haar_queue_groups(c, h, dl, g.cap, g.cap, &gi, &cand);
+    EF_HIP(c, hipGetLastError(), "haar kernels");
+  }
+  Carve gw;
+  gw.base = sp->group.p;
+  const HaarGroupWs ws = carve_haar_group_ws(gw, (size_t)sp->max_cand);
+  EF_HIP(c, launch_haar_group(s, cand, dl, h->ww, h->wh, static_cast<const int*>(h->counters.p) + gi, 0, sp->max_cand,
+                              sp->min_neighbors, ws, o.head, nullptr, o.rects, F),
+         "grouping kernels");
+  // grey of a crop == crop of the grey: the first max_faces grouped rectangles, read where the
+  // grouping left them (a zero rectangle behind the last one: a zero row)
+  EF_HIP(c, launch_roi_resize(s, f, W, H, W, 1, o.rects, 4, F, sp->face_h, sp->face_w, false, o.rows), "ROI resize kernel");
+  EF_TRY(bank_recognize_dev(c, o.rows, EF_U8, F, metric, o.keys, nullptr, o.best, nullptr, gated ? &bg : nullptr));
+  timer_end(c, &tev);
+  if (dev) return EF_OK;
+  EF_HIP(c, hipMemcpyAsync(sp->host.p, sp->out.p, size_out.total, hipMemcpyDeviceToHost, s), "D2H results");
+  EF_HIP(c, hipStreamSynchronize(s), "sync");
+  Carve hv;
+  hv.base = sp->host.p;
+  const HaarScanOut r = carve_haar_scan_out(hv, (size_t)F, M, (size_t)d, gated);
+  *head = *r.head;
+  std::memcpy(rects, r.rects, (size_t)F * 16);
+  std::memcpy(keys, r.keys, (size_t)F * M * sizeof(long long));
+  if (best_slot) std::memcpy(best_slot, r.best, (size_t)F * sizeof(int));
+  if (rows) std::memcpy(rows, r.rows, (size_t)F * d);
+  if (gated) std::memcpy(dffs2, r.dffs2, (size_t)F * M * sizeof(float));
+  if (gated && energy) std::memcpy(energy, r.energy, (size_t)F * M * sizeof(float));
   return EF_OK;
 }
 

@@ -136,9 +136,8 @@ __global__ __launch_bounds__(256) void roi_resize_kernel(const uint8_t* __restri
   *out = (uint8_t)resize_px(gray, h, w, oh, ow, dy, dx);
 }
 
-static hipError_t launch_roi_resize(hipStream_t s, const uint8_t* frame, int64_t ld, int fh, int fw, int c,
-                                    const int* rects, int rect_stride, int64_t n, int oh, int ow, bool rgb,
-                                    uint8_t* dst) {
+hipError_t launch_roi_resize(hipStream_t s, const uint8_t* frame, int64_t ld, int fh, int fw, int c, const int* rects,
+                             int rect_stride, int64_t n, int oh, int ow, bool rgb, uint8_t* dst) {
   if (n == 0) return hipSuccess;
   const dim3 grid((unsigned)(((int64_t)oh * ow + 255) / 256), (unsigned)n);
   if (rgb)
@@ -171,6 +170,17 @@ __global__ __launch_bounds__(256) void frame_gray_kernel(const uint8_t* __restri
     }
   }
   dst[i0 >> 2] = v;
+}
+
+hipError_t launch_frame_gray(hipStream_t s, const uint8_t* src, int64_t ld, int H, int W, int c, bool rgb, void* dst) {
+  const int64_t quads = ((int64_t)H * W + 3) / 4;
+  const dim3 grid((unsigned)((quads + 255) / 256));
+  uint32_t* g32 = static_cast<uint32_t*>(dst);
+  if (rgb)
+    hipLaunchKernelGGL(frame_gray_kernel<true>, grid, dim3(256), 0, s, src, ld, H, W, c, g32);
+  else
+    hipLaunchKernelGGL(frame_gray_kernel<false>, grid, dim3(256), 0, s, src, ld, H, W, c, g32);
+  return hipGetLastError();
 }
 
 // Interface used by the Haar pyramid (ef_haar.hip): grey single-channel ragged resize.
@@ -1528,14 +1538,7 @@ static int scan_frame_call(ef_ctx* c, const char* who, const uint8_t* frame, int
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_SCAN, &tev);
   if (channels != 1) {
-    const int64_t quads = ((int64_t)H * W + 3) / 4;
-    const dim3 grid((unsigned)((quads + 255) / 256));
-    uint32_t* g32 = static_cast<uint32_t*>(sp->gray.p);
-    if (flags & EF_IMG_RGB)
-      hipLaunchKernelGGL(frame_gray_kernel<true>, grid, dim3(256), 0, s, f, frame_ld, H, W, channels, g32);
-    else
-      hipLaunchKernelGGL(frame_gray_kernel<false>, grid, dim3(256), 0, s, f, frame_ld, H, W, channels, g32);
-    EF_HIP(c, hipGetLastError(), "frame grey kernel");
+    EF_HIP(c, launch_frame_gray(s, f, frame_ld, H, W, channels, flags & EF_IMG_RGB, sp->gray.p), "frame grey kernel");
     f = static_cast<const uint8_t*>(sp->gray.p);
     frame_ld = W;
   }

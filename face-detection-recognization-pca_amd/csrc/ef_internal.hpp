@@ -41,7 +41,7 @@ inline int proj_pad(int kp) { return kp <= 64 ? 64 : (kp + 127) / 128 * 128; }
 constexpr int kSearchProbeTile = 256;   // probes per search workgroup (4 waves x 64)
 constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
-constexpr int kTimers = 11;             // EF_KERNEL_* ids (include/eigenface.h)
+constexpr int kTimers = 12;             // EF_KERNEL_* ids (include/eigenface.h)
 constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
 
 // Workspace of one search call (device pointers).
@@ -447,6 +447,7 @@ struct ef_ctx {
   // published only once completely built (ef_tm_prepare, ef_haar_set_cascade); null otherwise
   ef::TmState* tm = nullptr;
   ef::HaarState* haar = nullptr;
+  ef::DevBuf haar_group_ws;  // ef_haar_group's scratch (ef::HaarGroupWs carve-out, header, staged results)
 
   // multi-GPU: RCCL communicator (ef_comm_init), null when single-rank
   void* comm = nullptr;
@@ -554,6 +555,13 @@ void comm_release(ef_ctx* c);
 hipError_t launch_resize_gray(hipStream_t s, const uint8_t* src, const void* desc_dev, int count, int64_t max_out,
                               uint8_t* dst);
 size_t img_desc_size();
+// grey plane of an H x W x c (3, 4) frame, rows ld bytes apart -> dst, round_up(H * W, 4) bytes,
+// 4-byte aligned (ef_image.hip frame_gray_kernel): ef_scan_frame and ef_haar_scan_frame
+hipError_t launch_frame_gray(hipStream_t s, const uint8_t* src, int64_t ld, int H, int W, int c, bool rgb, void* dst);
+// ef_preprocess_rois on device pointers (ef_image.hip roi_resize_kernel): rectangle i is the four
+// ints at rects + i * rect_stride, clipped to the frame by the kernel
+hipError_t launch_roi_resize(hipStream_t s, const uint8_t* frame, int64_t ld, int fh, int fw, int c, const int* rects,
+                             int rect_stride, int64_t n, int oh, int ow, bool rgb, uint8_t* dst);
 void img_desc_fill(void* d, int64_t src_off, int64_t dst_off, int h, int w, int c, int oh, int ow);
 // wait for every queued JPEG upload and decode of the context (ef_jpeg.hip)
 hipError_t jpeg_quiesce(ef_ctx* c);

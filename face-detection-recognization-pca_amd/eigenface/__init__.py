@@ -9,7 +9,7 @@ from .engine import (Engine, FitResult, bank_recon_schedule, decode_keys, device
                      merge_matches_host, merge_topk_host)
 from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_face_to_eigenspace  # noqa: F401
 from .bank import ModelBank, best_over_models, face_gate_mask  # noqa: F401
-from .scanner import FrameScanner, decide  # noqa: F401
+from .scanner import FrameScanner, HaarScanner, decide, label_bank, label_one, label_pair  # noqa: F401
 from .compat import face_space_distance, reconstruct_faces  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
@@ -34,5 +34,5 @@ __all__ = [
     "recognize_face_candidates_with_model", "EigenfaceError",
     "NativeLibraryError", "LIB_PATH", "save_gallery_cache", "load_gallery_cache", "ManualPCA",
     "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity", "ModelBank", "best_over_models",
-    "FrameScanner", "decide", "reconstruct_faces", "face_space_distance", "face_gate_mask", "bank_recon_schedule",
+    "FrameScanner", "HaarScanner", "decide", "label_one", "label_pair", "label_bank", "reconstruct_faces", "face_space_distance", "face_gate_mask", "bank_recon_schedule",
 ]

@@ -27,6 +27,9 @@ EF_KERNEL_SEARCH, EF_KERNEL_PROJECT, EF_KERNEL_TMATCH, EF_KERNEL_INGEST, EF_KERN
     EF_KERNEL_SYRK, EF_KERNEL_JPEG_HOST = 0, 1, 2, 3, 4, 5, 6, 7
 EF_KERNEL_SCAN = 8
 EF_KERNEL_RECON, EF_KERNEL_RECON_REDUCE = 9, 10
+EF_KERNEL_HAAR_SCAN = 11
+EF_HAAR_GROUP_MAX = 16384  # rectangles per grouping; the ceiling of a Haar scan plan's max_candidates
+EF_HAAR_SCAN_OVERFLOW, EF_HAAR_SCAN_UNCONVERGED = 0x1, 0x2  # ef_haar_scan_head.status bits
 EF_JPEG_GRAY, EF_JPEG_BGR = 0, 1
 EF_JPEG_E_UNSUPPORTED, EF_JPEG_E_CORRUPT = -10, -11
 EF_KEY_NONE = (1 << 63) - 1
@@ -52,6 +55,9 @@ class ef_scan_det(C.Structure):
     _fields_ = [("found", C.c_int32), ("problem", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32),
                 ("h", C.c_int32), ("confidence", C.c_float), ("pad", C.c_int32)]
 
+
+# numpy view of an ef_haar_scan_head
+HAAR_SCAN_HEAD_DTYPE = [("status", "<i4"), ("n_candidates", "<i4"), ("n_rects", "<i4"), ("n_faces", "<i4")]
 
 # numpy view of an ef_scan_det array
 SCAN_DET_DTYPE = [("found", "<i4"), ("problem", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"),
@@ -162,6 +168,11 @@ _SIGS = {
     "ef_scan_frame_gated": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, u32], C.c_int),
     "ef_bank_recon_schedule": ([i64, i64, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)],
                                C.c_int),
+    # Haar route in one call: rectangle grouping on the GPU and the fused frame, bound by symbol
+    "ef_haar_group": ([vp, vp, i32, i32, vp, i32, vp, u32], C.c_int),
+    "ef_haar_scan_prepare": ([vp, i32, i32, C.c_double, i32, i32, i32, i32, i32, i32, i32, i32, i32], C.c_int),
+    "ef_haar_scan_info": ([vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)], C.c_int),
+    "ef_haar_scan_frame": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, u32], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

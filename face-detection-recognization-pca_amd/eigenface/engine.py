@@ -1457,6 +1457,124 @@ class Engine:
                                                 flags))
         return dets, keys, best, rows, eps, en
 
+    # ------------------------------------------------------ Haar route in one call
+    def haar_group(self, rects, min_neighbors=3, max_rects=None):
+        """cv2.groupRectangles(rects, min_neighbors, 0.2) on the GPU (ef_haar_group): the grouped
+        rectangles of ``rects`` (n, 4) int32 ``x, y, w, h`` in OpenCV's order, value for value what
+        the detector's host grouping returns.  ``min_neighbors`` must be at least 1.  A host array
+        gives a NumPy (m, 4) array; a device tensor gives ``(out, n_rects)`` device tensors, ``out``
+        (max_rects, 4) zero behind the first ``n_rects`` rows, stream-ordered with no host wait.
+        More than N.EF_HAAR_GROUP_MAX rectangles raise (EF_HAAR_SCAN_OVERFLOW)."""
+        if _is_dev(rects):
+            import torch
+            r, rp = _dev(rects, torch.int32)
+        else:
+            r, rp = _host(rects, np.int32)
+        n = int(r.shape[0])
+        if n and (r.ndim != 2 or r.shape[1] != 4):
+            raise ValueError("rects must be (n, 4): x, y, w, h")
+        cap = n if max_rects is None else int(max_rects)
+        if _is_dev(rects):
+            out = torch.empty((cap, 4), dtype=torch.int32, device=r.device)
+            cnt = torch.empty(1, dtype=torch.int32, device=r.device)
+            with self._torch_order(r, out, cnt):
+                self._chk(self._lib.ef_haar_group(self._h, rp if n else None, n, int(min_neighbors),
+                                                  out.data_ptr() if cap else None, cap, cnt.data_ptr(),
+                                                  N.EF_MEM_DEVICE))
+            return out, cnt
+        out = np.zeros((cap, 4), np.int32)
+        cnt = C.c_int32(0)
+        self._chk(self._lib.ef_haar_group(self._h, rp if n else None, n, int(min_neighbors),
+                                          out.ctypes.data if cap else None, cap, C.byref(cnt), 0))
+        return out[:min(cnt.value, cap)].copy()
+
+    def haar_scan_prepare(self, frame_shape, scale_factor=1.1, min_neighbors=5, min_size=(30, 30), max_size=(),
+                          face_size=(64, 64), max_faces=8, max_candidates=4096):
+        """The Haar frame scan's plan (ef_haar_scan_prepare) for frames of ``frame_shape`` (H, W)
+        over the loaded cascade: the detectMultiScale parameters, cv2's ``face_size`` (width,
+        height) of the recognised crops, the ``max_faces`` rectangles a frame is recognised for and
+        the ``max_candidates`` the grouping kernels take.  A new cascade drops the plan."""
+        H, W = int(frame_shape[0]), int(frame_shape[1])
+        mn = tuple(min_size) if min_size else (0, 0)
+        mx = tuple(max_size) if max_size else (0, 0)
+        fw, fh = int(face_size[0]), int(face_size[1])
+        self._haar_scan = None
+        self._chk(self._lib.ef_haar_scan_prepare(self._h, H, W, float(scale_factor), int(min_neighbors), int(mn[0]),
+                                                 int(mn[1]), int(mx[0]), int(mx[1]), fh, fw, int(max_faces),
+                                                 int(max_candidates)))
+        self._haar_scan = (H, W, fh, fw, int(max_faces))
+
+    def haar_scan_info(self):
+        """(pyramid layers, visitable-window bound, max_faces, max_candidates) of the plan."""
+        nl, vis, mf, mc = C.c_int32(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.ef_haar_scan_info(self._h, C.byref(nl), C.byref(vis), C.byref(mf), C.byref(mc)))
+        return int(nl.value), int(vis.value), int(mf.value), int(mc.value)
+
+    def haar_scan_frame(self, frame, metric="cosine", gate=None, relative=True, rgb=False):
+        """One frame through grey, the Haar detector, the rectangle grouping, the ROI rows and
+        the model bank (ef_haar_scan_frame): (head, rects[F, 4] int32, keys[F, M] int64,
+        best_slot[F] int32, rows[F, h*w] uint8) for the plan's F = max_faces and the bank's M
+        slots, and with ``gate`` (M,) also (dffs2[F, M], energy[F, M]) as
+        :meth:`bank_recognize_gated` gives them.  ``head`` holds status, n_candidates, n_rects and
+        n_faces = min(n_rects, F); rows and rectangles behind n_faces are zero.  A status with
+        N.EF_HAAR_SCAN_OVERFLOW means nothing was grouped: redo the frame with the separate calls.
+        A host frame gives NumPy arrays (head a record of N.HAAR_SCAN_HEAD_DTYPE) after one
+        upload, one download and one synchronisation; a device tensor gives device tensors (head
+        as (4,) int32), stream-ordered with no host wait."""
+        mt = _metric(metric)
+        plan = getattr(self, "_haar_scan", None)
+        if plan is None:  # the library reports the state error
+            hd = np.zeros(4, np.int32)
+            self._chk(self._lib.ef_haar_scan_frame(self._h, hd.ctypes.data, 1, 1, mt, None, hd.ctypes.data,
+                                                   hd.ctypes.data, hd.ctypes.data, None, None, None, None, 0))
+            raise RuntimeError("call haar_scan_prepare first")
+        H, W, fh, fw, F = plan
+        f, fp, ld, h, w, ch, dev = self._frame_view(frame)
+        if (h, w) != (H, W):
+            raise ValueError(f"frame must be {(H, W)}, got {(h, w)}")
+        M = self.bank_info()[0]
+        gated = gate is not None
+        flags = (N.EF_IMG_RGB if rgb else 0) | (N.EF_BANK_GATE_RELATIVE if gated and relative else 0)
+        if dev:
+            import torch
+            t = {"device": f.device}
+            gp = None
+            if gated:
+                g = gate if _is_dev(gate) else torch.as_tensor(np.asarray(gate, np.float32), device=f.device)
+                g, gp = _dev(g, torch.float32)
+                if tuple(g.shape) != (M,):
+                    raise ValueError(f"gate must be ({M},), got {tuple(g.shape)}")
+            head = torch.empty(4, dtype=torch.int32, **t)
+            rects = torch.empty((F, 4), dtype=torch.int32, **t)
+            keys = torch.empty((F, M), dtype=torch.int64, **t)
+            best = torch.empty(F, dtype=torch.int32, **t)
+            rows = torch.empty((F, fh * fw), dtype=torch.uint8, **t)
+            eps = torch.empty((F, M), dtype=torch.float32, **t) if gated else None
+            en = torch.empty((F, M), dtype=torch.float32, **t) if gated else None
+            with self._torch_order(f, g if gated else None, head, rects, keys, best, rows, eps, en):
+                self._chk(self._lib.ef_haar_scan_frame(self._h, fp, ld, ch, mt, gp, head.data_ptr(), rects.data_ptr(),
+                                                       keys.data_ptr(), best.data_ptr(), rows.data_ptr(),
+                                                       eps.data_ptr() if gated else None,
+                                                       en.data_ptr() if gated else None, flags | N.EF_MEM_DEVICE))
+            return (head, rects, keys, best, rows) + ((eps, en) if gated else ())
+        gp = None
+        if gated:
+            g, gp = _host(gate, np.float32)
+            if g.shape != (M,):
+                raise ValueError(f"gate must be ({M},), got {g.shape}")
+        head = np.zeros(1, dtype=N.HAAR_SCAN_HEAD_DTYPE)
+        rects = np.empty((F, 4), dtype=np.int32)
+        keys = np.empty((F, M), dtype=np.int64)
+        best = np.empty(F, dtype=np.int32)
+        rows = np.empty((F, fh * fw), dtype=np.uint8)
+        eps = np.empty((F, M), dtype=np.float32) if gated else None
+        en = np.empty((F, M), dtype=np.float32) if gated else None
+        self._chk(self._lib.ef_haar_scan_frame(self._h, fp, ld, ch, mt, gp, head.ctypes.data, rects.ctypes.data,
+                                               keys.ctypes.data, best.ctypes.data, rows.ctypes.data,
+                                               eps.ctypes.data if gated else None, en.ctypes.data if gated else None,
+                                               flags))
+        return (head[0], rects, keys, best, rows) + ((eps, en) if gated else ())
+
     # --------------------------------------------------------------------- timing
     def timing(self, on=True):
         self._chk(self._lib.ef_timing_enable(self._h, 1 if on else 0))
@@ -1468,7 +1586,8 @@ class Engine:
         kid = {"search": N.EF_KERNEL_SEARCH, "project": N.EF_KERNEL_PROJECT, "tmatch": N.EF_KERNEL_TMATCH,
                "ingest": N.EF_KERNEL_INGEST, "haar": N.EF_KERNEL_HAAR, "jpeg": N.EF_KERNEL_JPEG,
                "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST, "scan": N.EF_KERNEL_SCAN,
-               "recon": N.EF_KERNEL_RECON, "recon_reduce": N.EF_KERNEL_RECON_REDUCE}[kernel]
+               "recon": N.EF_KERNEL_RECON, "recon_reduce": N.EF_KERNEL_RECON_REDUCE,
+               "haar_scan": N.EF_KERNEL_HAAR_SCAN}[kernel]
         ms = C.c_double(0)
         n = C.c_int64(0)
         self._chk(self._lib.ef_timing_get(self._h, kid, C.byref(ms), C.byref(n)))

@@ -93,6 +93,7 @@ class CascadeClassifier:
         sl = np.array([p[2] for p in st], np.float32)
         sr = np.array([p[3] for p in st], np.float32)
         e = self.engine
+        e._haar_scan = e.haar_scan_owner = None  # a new cascade drops the Haar frame scan's plan
         e._chk(e._lib.ef_haar_set_cascade(e._h, int(cascade["win"][0]), int(cascade["win"][1]), nf, rects.ctypes.data,
                                           wts.ctypes.data, len(counts), counts.ctypes.data, sthr.ctypes.data, len(st),
                                           sf.ctypes.data, st_thr.ctypes.data, sl.ctypes.data, sr.ctypes.data))

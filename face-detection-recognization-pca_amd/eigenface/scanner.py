@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _native as N
 from .bank import ModelBank, face_gate_mask
 from .engine import decode_keys
 from .image import SCALES, TemplateLocaliser
@@ -58,6 +59,164 @@ def decide(detections, pca_results):
                         "pca_confidence": pca_conf, "final_confidence": final_conf,
                         "x": det["x"], "y": det["y"], "width": det["width"], "height": det["height"]})
     return records
+
+
+def label_one(person_name, similarity, threshold=0.7):
+    """useless/scan.py:126-132, :205-213 for one model: ``(name, confidence, recognized)`` from the
+    model's person name and its best cosine similarity; recognised on ``>=``.  A pure host function."""
+    s = float(similarity)
+    return person_name, s, bool(s >= threshold)
+
+
+def label_pair(dark_name, dark_similarity, light_name, light_similarity, threshold=0.7):
+    """``recognize_face_dual_model``'s rule (useless/scan.py:147-166): recognised when either
+    model is (OR), the larger similarity, the dark model's name on ``>=``.  A pure host function."""
+    _, ds, dr = label_one(dark_name, dark_similarity, threshold)
+    _, ls, lr = label_one(light_name, light_similarity, threshold)
+    return (dark_name if ds >= ls else light_name), max(ds, ls), dr or lr
+
+
+def label_bank(bank, idx, sim, threshold=0.8, allowed=None):
+    """``ModelBank.label`` in the Haar loop's record layout: ``[(name, confidence, recognized)]``,
+    recognised where the winning model's row carries a label (person id other than -1)."""
+    return [(name, conf, pid != -1) for pid, name, conf in bank.label(idx, sim, threshold, allowed)]
+
+
+def _bank_layout(md, fallback_name):
+    """A model dict as :class:`ModelBank` reads it.  A ``models/*_pca_model.pkl`` dict
+    (``eigenfaces``, ``mean_face``, ``projected_data``, ``person_name``) gets its gallery under
+    ``face_features``, one label for every row and its person name for that label."""
+    if md is None or "face_features" in md or "projected_data" not in md:
+        return md
+    g = np.asarray(md["projected_data"])
+    name = md.get("person_name", fallback_name)
+    return {**md, "face_features": g, "face_labels": np.zeros(len(g), np.int64), "person_id_map": {name: 0}}
+
+
+def _is_model(m):
+    return isinstance(m, dict) and ("eigenfaces" in m or "pca" in m)
+
+
+class HaarScanner:
+    """The Haar live loop (useless/scan.py:168-290, detection-v4.py:47-60: ``cvtColor`` ->
+    ``detectMultiScale`` -> crop -> resize -> recognise) with one GPU call per frame
+    (``ef_haar_scan_frame``): one upload of the frame, one download of the results, one
+    synchronisation; the rectangles are grouped on the card.
+
+    ``cascade``: a cascade dict (``haar.load_cascade``) or the path of OpenCV's XML.  ``models``:
+    one model dict, a ``(dark, light)`` pair, or the ``{name: model}`` dict :class:`ModelBank`
+    takes; both on-disk layouts are accepted (``face_model.pkl``, ``models/*_pca_model.pkl``).
+    Faces are resized to ``int(sqrt(face_dimensions))`` squared (the models' pixel count).  At
+    most ``max_faces`` rectangles of a frame are recognised, the first in OpenCV's order.  A
+    frame with more than ``max_candidates`` ungrouped candidates goes through the separate calls
+    (``CascadeClassifier.detect``, ``preprocess_rois``, the bank) instead, with the same result.
+    ``face_gate`` is :class:`ModelBank`'s."""
+
+    def __init__(self, cascade, models, frame_shape, device=0, scale_factor=1.1, min_neighbors=5, min_size=(30, 30),
+                 max_size=(), max_faces=8, threshold=0.7, face_gate=None, max_candidates=4096):
+        from .haar import CascadeClassifier, load_cascade
+        self.device = device
+        self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
+        self.scale_factor, self.min_neighbors = float(scale_factor), int(min_neighbors)
+        self.min_size, self.max_size = tuple(min_size) if min_size else (), tuple(max_size) if max_size else ()
+        self.max_faces, self.max_candidates, self.threshold = int(max_faces), int(max_candidates), float(threshold)
+        self.cascade = load_cascade(cascade) if isinstance(cascade, str) else cascade
+        if _is_model(models):
+            self.mode, named = "one", {models.get("person_name", "person"): models}
+        elif isinstance(models, (tuple, list)):
+            if len(models) != 2:
+                raise ValueError("a model pair is (dark, light)")
+            self.mode, named = "pair", {"dark": models[0], "light": models[1]}
+        else:
+            self.mode, named = "bank", dict(models)
+        self.model_names = []
+        layout = {}
+        for key, info in named.items():
+            wrapped = isinstance(info, dict) and "model_data" in info
+            md = _bank_layout(info["model_data"] if wrapped else info, key)
+            layout[key] = {**info, "model_data": md} if wrapped else md
+            self.model_names.append(md.get("person_name", key) if isinstance(md, dict) else key)
+        self.bank = ModelBank(layout, device, face_gate)
+        if not len(self.bank) or (self.mode != "bank" and len(self.bank) != len(named)):
+            raise ValueError("HaarScanner needs usable models")
+        eng = get_engine(device)
+        d = eng.bank_info()[1]
+        first = next(iter(named.values()))
+        first = first["model_data"] if isinstance(first, dict) and "model_data" in first else first
+        side = int(np.sqrt(first.get("face_dimensions", d))) if isinstance(first, dict) else int(np.sqrt(d))
+        if side * side != d:
+            raise ValueError(f"the models take {d} pixels, not a square face")
+        self.face_size = (side, side)
+        self.classifier = CascadeClassifier(cascade=self.cascade, device=device)
+
+    def _prepare(self):
+        """The cascade, the plan and the bank's slots, (re-)uploaded when someone else used the
+        shared engine's cascade or bank in between."""
+        eng = get_engine(self.device)
+        if getattr(eng, "haar_scan_owner", None) is not self or getattr(eng, "_haar_scan", None) is None:
+            self.classifier.set_cascade(self.cascade)
+            eng.haar_scan_prepare(self.frame_shape, self.scale_factor, self.min_neighbors, self.min_size, self.max_size,
+                                  self.face_size, self.max_faces, self.max_candidates)
+            eng.haar_scan_owner = self
+        if getattr(eng, "bank_owner", None) is not self.bank:
+            self.bank.refresh()
+        if self.bank.gate is not None and not self.bank._recon_up:
+            self.bank._upload_reconstruction(eng)
+        return eng
+
+    def _separate_calls(self, eng, frame, rgb):
+        """The frame through the calls ef_haar_scan_frame fuses, in its result layout."""
+        f = frame.cpu().numpy() if hasattr(frame, "cpu") else np.asarray(frame)
+        H, W = self.frame_shape
+        gray = f if f.ndim == 2 else eng.preprocess([np.ascontiguousarray(f)], (W, H), rgb=rgb)[0].reshape(H, W)
+        found, cand = self.classifier.detect(gray, self.scale_factor, self.min_neighbors, self.min_size, self.max_size,
+                                             return_candidates=True)
+        F = self.max_faces
+        rects = np.zeros((F, 4), np.int32)
+        rects[:min(len(found), F)] = found[:F]
+        rows = np.zeros((F, self.face_size[0] * self.face_size[1]), np.uint8)
+        if len(found):
+            rows[:min(len(found), F)] = eng.preprocess_rois(gray, found[:F], self.face_size)
+        head = np.zeros(1, dtype=N.HAAR_SCAN_HEAD_DTYPE)[0]
+        head["status"], head["n_candidates"] = N.EF_HAAR_SCAN_OVERFLOW, len(cand)
+        head["n_rects"], head["n_faces"] = len(found), min(len(found), F)
+        if self.bank.gate is None:
+            keys, _, best, _ = eng.bank_recognize_raw(rows, "cosine")
+            return head, rects, keys, best, rows
+        keys, _, best, _, eps, en = eng.bank_recognize_gated_raw(rows, self.bank.gate, "cosine", relative=True)
+        return head, rects, keys, best, rows, eps, en
+
+    def scan_raw(self, frame, rgb=False):
+        """``Engine.haar_scan_frame`` on this scanner's plan: (head, rects, keys, best_slot, rows)
+        and, with a face gate, (dffs2, energy).  A frame whose candidates overflow the plan comes
+        from the separate calls, as NumPy arrays, with EF_HAAR_SCAN_OVERFLOW left in head."""
+        eng = self._prepare()
+        out = eng.haar_scan_frame(frame, "cosine", gate=self.bank.gate, relative=True, rgb=rgb)
+        status = int(out[0][0]) if hasattr(out[0], "cpu") else int(out[0]["status"])
+        if status & N.EF_HAAR_SCAN_OVERFLOW:
+            out = self._separate_calls(eng, frame, rgb)
+        return out
+
+    def scan(self, frame, rgb=False):
+        """The reference's list ``[(x, y, w, h, name, confidence, recognized)]`` for one frame:
+        :func:`label_one` for one model, :func:`label_pair` for a pair, :func:`label_bank` for a
+        bank, on the similarities the bank call returned."""
+        out = [t.cpu().numpy() if hasattr(t, "cpu") else t for t in self.scan_raw(frame, rgb)]
+        head, rects, keys = out[0], out[1], out[2]
+        nf = int(head[3]) if isinstance(head, np.ndarray) and head.dtype.names is None else int(head["n_faces"])
+        if nf == 0:
+            return []
+        k = np.ascontiguousarray(keys[:nf])
+        idx, sim = decode_keys(k.reshape(-1), "cosine")
+        idx, sim = idx.reshape(k.shape), sim.reshape(k.shape)
+        if self.mode == "one":
+            labels = [label_one(self.model_names[0], s[0], self.threshold) for s in sim]
+        elif self.mode == "pair":
+            labels = [label_pair(self.model_names[0], s[0], self.model_names[1], s[1], self.threshold) for s in sim]
+        else:
+            allowed = face_gate_mask(out[5][:nf], out[6][:nf], self.bank.gate) if len(out) > 5 else None
+            labels = label_bank(self.bank, idx, sim, self.threshold, allowed)
+        return [(int(x), int(y), int(w), int(h), *lab) for (x, y, w, h), lab in zip(rects[:nf], labels)]
 
 
 def corner_integers(frame_width, frame_height, corner_threshold=0.15, border_threshold=0.05):

@@ -75,6 +75,7 @@ extern "C" {
                                bank's grouped residual GEMM (ef_bank_face_distance and the gated calls) too */
 #define EF_KERNEL_RECON_REDUCE 10 /* ef_face_distance: the fixed-order sum of the pixel splits' partials; the
                                      bank's grouped reduce too */
+/* 11: EF_KERNEL_HAAR_SCAN, defined with ef_haar_scan_frame below */
 
 /* No-result sentinel in a key array (empty gallery). */
 #define EF_KEY_NONE INT64_MAX
@@ -662,6 +663,70 @@ int ef_haar_detect(ef_ctx* ctx, const uint8_t* gray, int32_t h, int32_t w, int64
                    int32_t min_neighbors, int32_t min_w, int32_t min_h, int32_t max_w, int32_t max_h,
                    int32_t* rects_out, int32_t max_rects, int32_t* n_rects, int32_t* cand_out, int32_t max_cand,
                    int32_t* n_cand, uint32_t flags);
+
+/* ------------------------------------------------------- Haar route in one call
+ * Added after API v7 without a version bump (purely additive): detect by symbol.
+ *
+ * One frame of the Haar live loop (useless/scan.py:168-290, detection-v4.py:47-60:
+ * cvtColor -> detectMultiScale -> crop -> resize -> recognise) as one stream-ordered sequence,
+ * with cv::groupRectangles on the GPU.
+ *
+ * ef_haar_group: cv::groupRectangles(rects, min_neighbors, 0.2) on the GPU for n rectangles
+ *   {x, y, w, h} in list order -> the grouped rectangles in OpenCV's order (classes numbered by
+ *   their first member), value for value what ef_haar_detect's host grouping gives.  rects_out
+ *   takes up to max_rects of them, *n_rects the total.  min_neighbors <= 0 is EF_E_INVALID (the
+ *   host function returns its input there).  n > EF_HAAR_GROUP_MAX: the kernels group nothing,
+ *   *n_rects is 0 and the call returns EF_E_INVALID naming EF_HAAR_SCAN_OVERFLOW.  Host pointers
+ *   (synchronous), or device pointers with EF_MEM_DEVICE (stream-ordered, n_rects too).  Needs no
+ *   cascade.  The same input gives the same bits on every call.
+ *
+ * ef_haar_scan_prepare: needs a cascade (ef_haar_set_cascade), else EF_E_STATE; a new cascade
+ *   drops the plan.  Fixes, for frames of frame_h x frame_w, everything ef_haar_detect derives
+ *   per call from (scale_factor, min_w/h, max_w/h; max <= 0: the frame size): the scale list, the
+ *   pyramid layers, the row table, the resize descriptors and the buffer sizes.  min_neighbors
+ *   >= 1; faces are resized to face_h x face_w; 1 <= max_faces <= EF_BANK_MAX_PROBES;
+ *   1 <= max_candidates <= EF_HAAR_GROUP_MAX.  Synchronous.
+ *
+ * ef_haar_scan_frame: frame is frame_h x frame_w x channels (1 grey; 3, 4 BGR(A), or RGB(A) with
+ *   EF_IMG_RGB), row stride frame_ld bytes.  On the ctx's stream it queues
+ *     a. channels 3, 4: the grey plane, BT.601 fixed point as ef_preprocess;
+ *     b. ef_haar_detect's kernels on that plane (stage-group grids sized by the plan's bound);
+ *     c. the grouping kernels -> rects[max_faces] (zeros behind the grouped rectangles) and
+ *        head = {status, n_candidates, n_rects, n_faces = min(n_rects, max_faces)}: the rectangles
+ *        and n_rects are ef_haar_detect's on the grey plane.  More than max_candidates
+ *        candidates: nothing is grouped, status has EF_HAAR_SCAN_OVERFLOW and n_rects = 0 (the
+ *        caller redoes the frame with ef_haar_detect);
+ *     d. ef_preprocess_rois of rects on the grey plane -> rows[max_faces] (zero behind n_rects);
+ *     e. ef_bank_recognize of those rows (EF_U8, b = max_faces, `metric`), or with gate non-null
+ *        ef_bank_recognize_gated (EF_BANK_GATE_RELATIVE as there; dffs2 is then required) ->
+ *        keys, best_slot, dffs2, energy with exactly that call's meaning and bits.
+ *   best_slot, rows and energy are optional.  EF_E_STATE without a plan, with an empty bank, when
+ *   the bank's d is not face_h * face_w, or with a communicator of more than one rank attached.
+ *   Host pointers: one upload of the frame, one download of one pinned result block, one stream
+ *   synchronisation.  EF_MEM_DEVICE: every array is a device pointer and nothing waits on the host
+ *   (apart from the bank's one-time table upload after the bank changed). */
+#define EF_HAAR_GROUP_MAX 16384       /* rectangles per grouping; the ceiling of max_candidates */
+#define EF_HAAR_SCAN_OVERFLOW 0x1     /* head.status: more candidates than the plan's max_candidates */
+#define EF_HAAR_SCAN_UNCONVERGED 0x2  /* head.status: a grouping loop reached its iteration bound */
+#define EF_KERNEL_HAAR_SCAN 11 /* everything one ef_haar_scan_frame queues; the bank's launches inside it also
+                                  count under EF_KERNEL_PROJECT and EF_KERNEL_SEARCH; EF_KERNEL_HAAR and
+                                  EF_KERNEL_INGEST do not count these frames */
+typedef struct ef_haar_scan_head {
+  int32_t status, n_candidates, n_rects, n_faces;
+} ef_haar_scan_head;
+int ef_haar_group(ef_ctx* ctx, const int32_t* rects /* [n][4] */, int32_t n, int32_t min_neighbors,
+                  int32_t* rects_out /* [max_rects][4] */, int32_t max_rects, int32_t* n_rects, uint32_t flags);
+int ef_haar_scan_prepare(ef_ctx* ctx, int32_t frame_h, int32_t frame_w, double scale_factor, int32_t min_neighbors,
+                         int32_t min_w, int32_t min_h, int32_t max_w, int32_t max_h, int32_t face_h, int32_t face_w,
+                         int32_t max_faces, int32_t max_candidates);
+/* the plan's pyramid layers, its bound on the windows one frame can visit (what the stage-group
+ * grids and lists are sized by), max_faces and max_candidates; each optional; EF_E_STATE without a plan */
+int ef_haar_scan_info(ef_ctx* ctx, int32_t* n_layers, int64_t* visitable, int32_t* max_faces, int32_t* max_candidates);
+int ef_haar_scan_frame(ef_ctx* ctx, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,
+                       const float* gate /* [M] or NULL */, ef_haar_scan_head* head,
+                       int32_t* rects /* [max_faces][4] */, int64_t* keys /* [max_faces][M] */,
+                       int32_t* best_slot /* optional */, uint8_t* rows /* [max_faces][face_h*face_w], optional */,
+                       float* dffs2 /* [max_faces][M], with gate */, float* energy /* optional */, uint32_t flags);
 
 /* ------------------------------------------------------------------ timing
  * Device time of each launch of a kernel, measured with hipEvents on the
