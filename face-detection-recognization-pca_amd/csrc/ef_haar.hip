@@ -33,8 +33,9 @@
 // ef_haar_scan_frame (the Haar live loop of useless/scan.py:168-290 in one call) queues the
 // same kernels from a plan made once by ef_haar_scan_prepare (`haar_geometry`; the queue-only
 // parts `haar_queue_front` and `haar_queue_groups` serve both entries), then the grouping on
-// the device (ef_haar_group.hip), the crops' resize read in place from the grey plane and the
-// model bank's recognise: one upload, one download, one wait.
+// the device (ef_haar_group.hip), as its step of `frame_call` (ef_image.hip), which adds the
+// grey plane in front and the crops' resize read in place from the grey plane and the model
+// bank's recognise behind: one upload, one download, one wait.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -444,20 +445,15 @@ struct HaarGeom {
 
 // ef_haar_scan_prepare's plan.  It owns its copies of the layer, row and descriptor tables (an
 // ef_haar_detect call in between rewrites the state's own); the pyramid, integral images and
-// lists are the state's, shared with ef_haar_detect.  The result block of one frame is one
-// device allocation [head | rects | keys | best slots | rows | dffs2 | energy] (each piece
-// 256-byte aligned) with a pinned mirror, so a host call downloads it with one copy.
+// lists are the state's, shared with ef_haar_detect.  The result block of one frame is [head |
+// rects | keys | best slots | rows | dffs2 | energy] (carve_frame_out behind a front of
+// ef_haar_scan_head[1] and int[max_faces * 4]).
 struct HaarScanPlan {
   HaarGeom g;
   int min_neighbors = 0, face_h = 0, face_w = 0, max_faces = 0, max_cand = 0;
   DevBuf layers, rowstart, desc;
-  DevBuf frame_in;  // a host call's frame, H rows of W * channels bytes
-  DevBuf gray;      // the grey plane of a colour frame (or a strided grey one), round_up(H * W, 4) bytes
-  DevBuf group;     // HaarGroupWs carve-out for max_cand rectangles
-  DevBuf out;       // the result block
-  PinnedBuf host;   // its pinned mirror
-  DevBuf gate;      // a host call's gate stays resident (uploaded again when its values change)
-  std::vector<float> gate_host;
+  DevBuf group;  // HaarGroupWs carve-out for max_cand rectangles
+  FrameIo io;
 };
 
 struct HaarState {
@@ -721,26 +717,6 @@ static void haar_queue_groups(ef_ctx* c, HaarState* h, const HaarLayer* dl, int 
   *last = bin;
 }
 
-// The pieces of a Haar scan's result block for g faces, M bank slots and d face pixels.
-struct HaarScanOut {
-  ef_haar_scan_head* head;
-  int* rects;
-  long long* keys;
-  int* best;
-  uint8_t* rows;
-  float* dffs2;
-  float* energy;
-};
-static HaarScanOut carve_haar_scan_out(Carve& cv, size_t g, size_t M, size_t d, bool gated) {
-  HaarScanOut o{cv.take<ef_haar_scan_head>(1), cv.take<int>(g * 4), cv.take<long long>(g * M), cv.take<int>(g),
-                cv.take<uint8_t>(g * d),       nullptr,             nullptr};
-  if (gated) {
-    o.dffs2 = cv.take<float>(g * M);
-    o.energy = cv.take<float>(g * M);
-  }
-  return o;
-}
-
 }  // namespace ef
 
 using namespace ef;
@@ -961,7 +937,7 @@ int ef_haar_scan_prepare(ef_ctx* c, int32_t frame_h, int32_t frame_w, double sca
   sp->max_cand = max_candidates;
   if (g.nl == 0) sp->g.cap = 1024;  // no layer holds a window: the lists stay empty
   EF_TRY(haar_ensure(c, h, g));
-  EF_TRY(ensure(c, sp->gray, (size_t)round_up((int64_t)frame_h * frame_w, 4)));
+  EF_TRY(ensure(c, sp->io.gray, (size_t)round_up((int64_t)frame_h * frame_w, 4)));
   Carve gw;
   carve_haar_group_ws(gw, (size_t)max_candidates);
   EF_TRY(ensure(c, sp->group, gw.total));
@@ -995,121 +971,49 @@ int ef_haar_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_
                        const float* gate, ef_haar_scan_head* head, int32_t* rects, int64_t* keys, int32_t* best_slot,
                        uint8_t* rows, float* dffs2, float* energy, uint32_t flags) {
   if (!c) return EF_E_INVALID;
-  const std::string w("ef_haar_scan_frame");
   HaarState* h = c->haar;
   HaarScanPlan* sp = h ? h->scan.get() : nullptr;
-  if (!sp) return set_err(c, EF_E_STATE, w + ": no plan (call ef_haar_set_cascade, then ef_haar_scan_prepare)");
-  Bank& bk = c->bank;
-  if (bk.slots.empty()) return set_err(c, EF_E_STATE, w + ": the bank is empty (call ef_bank_add)");
-  const int64_t d = (int64_t)sp->face_h * sp->face_w;
-  if (bk.d != d)
-    return set_err(c, EF_E_STATE, w + ": the bank's models take " + std::to_string(bk.d) +
-                                      " pixels, the plan's faces have " + std::to_string(d));
-  if (c->comm && c->comm_size > 1) return set_err(c, EF_E_STATE, w + ": not available with a communicator attached");
-  if (gate) EF_TRY(bank_recon_complete(c, w.c_str()));
+  if (!sp) return set_err(c, EF_E_STATE, "ef_haar_scan_frame: no plan (call ef_haar_set_cascade, then ef_haar_scan_prepare)");
   const HaarGeom& g = sp->g;
   const int H = g.H, W = g.W, F = sp->max_faces;
-  if (!frame || !head || !rects || !keys || (channels != 1 && channels != 3 && channels != 4) ||
-      frame_ld < (int64_t)W * channels || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE) || (gate && !dffs2))
-    return set_err(c, EF_E_INVALID, w + ": bad arguments");
-  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
-  const bool dev = flags & EF_MEM_DEVICE;
   hipStream_t s = c->stream;
-  const size_t M = bk.slots.size();
+  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
   // an ef_haar_detect of a larger frame in between may have regrown (moved) the state's buffers:
   // growing them here is a no-op otherwise
   EF_TRY(haar_ensure(c, h, g));
-
-  // where the kernels write: the caller's device arrays, or the result block; the rows always
-  // exist (the bank reads them)
-  Carve size_out, cv;
-  const bool gated = gate != nullptr;
-  carve_haar_scan_out(size_out, (size_t)F, M, (size_t)d, gated);
-  HaarScanOut o{head, rects, reinterpret_cast<long long*>(keys), best_slot, rows, dffs2, energy};
-  if (!dev || !rows || (gated && !energy)) {
-    EF_TRY(ensure(c, sp->out, size_out.total));
-    cv.base = sp->out.p;
-    const HaarScanOut blk = carve_haar_scan_out(cv, (size_t)F, M, (size_t)d, gated);
-    if (!dev) {
-      o = blk;
-    } else {
-      if (!rows) o.rows = blk.rows;
-      if (!energy) o.energy = blk.energy;
+  EF_HIP(c, hipMemsetAsync(h->counters.p, 0, 64, s), "memset");  // ahead of the call's timed span
+  const FrameMiddle detect = [&](const uint8_t*& f, int64_t& ld, void* const* front, FrameRects& rects) -> int {
+    if (ld != W) {  // the pyramid reads packed rows
+      EF_HIP(c, hipMemcpy2DAsync(sp->io.gray.p, W, f, ld, W, H, hipMemcpyDeviceToDevice, s), "pack grey frame");
+      f = static_cast<const uint8_t*>(sp->io.gray.p);
+      ld = W;
     }
-  }
-  BankGate bg{gate, (flags & EF_BANK_GATE_RELATIVE) != 0, o.dffs2, o.energy};
-  if (gated && !dev) {
-    if (sp->gate_host.size() != M || std::memcmp(sp->gate_host.data(), gate, M * sizeof(float)) != 0) {
-      try {
-        sp->gate_host.assign(gate, gate + M);
-      } catch (const std::bad_alloc&) {
-        return set_err(c, EF_E_NOMEM, w + ": host allocation failed");
-      }
-      const hipError_t e = [&] {
-        if (ensure(c, sp->gate, M * sizeof(float)) != EF_OK) return hipErrorOutOfMemory;
-        return hipMemcpyAsync(sp->gate.p, sp->gate_host.data(), M * sizeof(float), hipMemcpyHostToDevice, s);
-      }();
-      if (e != hipSuccess) {
-        sp->gate_host.clear();  // nothing resident: the next call uploads again
-        return hip_err(c, e, "H2D gate");
-      }
+    int gi = 0;
+    HaarCand* cand = static_cast<HaarCand*>(h->work.p);
+    const HaarLayer* dl = static_cast<const HaarLayer*>(sp->layers.p);
+    if (g.nl > 0) {
+      EF_TRY(haar_queue_front(c, h, g, f, dl, static_cast<const int*>(sp->rowstart.p), sp->desc.p));
+      // no count comes back to the host: the stage groups' grids cover the plan's bound
+      haar_queue_groups(c, h, dl, g.cap, g.cap, &gi, &cand);
+      EF_HIP(c, hipGetLastError(), "haar kernels");
     }
-    bg.gate = static_cast<const float*>(sp->gate.p);
-  }
-  if (!dev && sp->host.bytes < size_out.total) EF_HIP(c, pinned_alloc(sp->host, size_out.total), "pinned results");
-  const uint8_t* f = frame;
-  if (!dev) {
-    const int64_t row_bytes = (int64_t)W * channels;
-    EF_TRY(ensure(c, sp->frame_in, (size_t)H * row_bytes));
-    EF_HIP(c, hipMemcpy2DAsync(sp->frame_in.p, row_bytes, frame, frame_ld, row_bytes, H, hipMemcpyHostToDevice, s),
-           "H2D frame");
-    f = static_cast<const uint8_t*>(sp->frame_in.p);
-    frame_ld = row_bytes;
-  }
-  EF_HIP(c, hipMemsetAsync(h->counters.p, 0, 64, s), "memset");
-  TimerEvt tev;
-  timer_begin(c, EF_KERNEL_HAAR_SCAN, &tev);
-  if (channels != 1) {
-    EF_HIP(c, launch_frame_gray(s, f, frame_ld, H, W, channels, flags & EF_IMG_RGB, sp->gray.p), "frame grey kernel");
-    f = static_cast<const uint8_t*>(sp->gray.p);
-  } else if (frame_ld != W) {  // the pyramid reads packed rows
-    EF_HIP(c, hipMemcpy2DAsync(sp->gray.p, W, f, frame_ld, W, H, hipMemcpyDeviceToDevice, s), "pack grey frame");
-    f = static_cast<const uint8_t*>(sp->gray.p);
-  }
-  int gi = 0;
-  HaarCand* cand = static_cast<HaarCand*>(h->work.p);
-  const HaarLayer* dl = static_cast<const HaarLayer*>(sp->layers.p);
-  if (g.nl > 0) {
-    EF_TRY(haar_queue_front(c, h, g, f, dl, static_cast<const int*>(sp->rowstart.p), sp->desc.p));
-    // no count comes back to the host: the stage groups' grids cover the plan's bound
-    haar_queue_groups(c, h, dl, g.cap, g.cap, &gi, &cand);
-    EF_HIP(c, hipGetLastError(), "haar kernels");
-  }
-  Carve gw;
-  gw.base = sp->group.p;
-  const HaarGroupWs ws = carve_haar_group_ws(gw, (size_t)sp->max_cand);
-  EF_HIP(c, launch_haar_group(s, cand, dl, h->ww, h->wh, static_cast<const int*>(h->counters.p) + gi, 0, sp->max_cand,
-                              sp->min_neighbors, ws, o.head, nullptr, o.rects, F),
-         "grouping kernels");
-  // grey of a crop == crop of the grey: the first max_faces grouped rectangles, read where the
-  // grouping left them (a zero rectangle behind the last one: a zero row)
-  EF_HIP(c, launch_roi_resize(s, f, W, H, W, 1, o.rects, 4, F, sp->face_h, sp->face_w, false, o.rows), "ROI resize kernel");
-  EF_TRY(bank_recognize_dev(c, o.rows, EF_U8, F, metric, o.keys, nullptr, o.best, nullptr, gated ? &bg : nullptr));
-  timer_end(c, &tev);
-  if (dev) return EF_OK;
-  EF_HIP(c, hipMemcpyAsync(sp->host.p, sp->out.p, size_out.total, hipMemcpyDeviceToHost, s), "D2H results");
-  EF_HIP(c, hipStreamSynchronize(s), "sync");
-  Carve hv;
-  hv.base = sp->host.p;
-  const HaarScanOut r = carve_haar_scan_out(hv, (size_t)F, M, (size_t)d, gated);
-  *head = *r.head;
-  std::memcpy(rects, r.rects, (size_t)F * 16);
-  std::memcpy(keys, r.keys, (size_t)F * M * sizeof(long long));
-  if (best_slot) std::memcpy(best_slot, r.best, (size_t)F * sizeof(int));
-  if (rows) std::memcpy(rows, r.rows, (size_t)F * d);
-  if (gated) std::memcpy(dffs2, r.dffs2, (size_t)F * M * sizeof(float));
-  if (gated && energy) std::memcpy(energy, r.energy, (size_t)F * M * sizeof(float));
-  return EF_OK;
+    Carve gw{sp->group.p};
+    const HaarGroupWs ws = carve_haar_group_ws(gw, (size_t)sp->max_cand);
+    // the first max_faces grouped rectangles, read where the grouping leaves them (a zero
+    // rectangle behind the last one: a zero row)
+    int* out = static_cast<int*>(front[1]);
+    EF_HIP(c, launch_haar_group(s, cand, dl, h->ww, h->wh, static_cast<const int*>(h->counters.p) + gi, 0, sp->max_cand,
+                                sp->min_neighbors, ws, static_cast<ef_haar_scan_head*>(front[0]), nullptr, out, F),
+           "grouping kernels");
+    rects = FrameRects{out, 4};
+    return EF_OK;
+  };
+  return frame_call(c, "ef_haar_scan_frame", EF_KERNEL_HAAR_SCAN, FrameShape{H, W, sp->face_h, sp->face_w, F}, sp->io,
+                    FrameFront{2, {sizeof(ef_haar_scan_head), (size_t)F * 4 * sizeof(int)}},
+                    FrameArgs{frame, frame_ld, channels, metric, gate,
+                              FrameOut{{head, rects}, reinterpret_cast<long long*>(keys), best_slot, rows, dffs2, energy},
+                              flags},
+                    detect);
 }
 
 }  // extern "C"

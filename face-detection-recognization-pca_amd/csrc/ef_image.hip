@@ -36,11 +36,12 @@
 // Frame scan — scan-template-v4.py:340-391, one frame of process_live_camera:
 //     gray = cvtColor(frame, BGR2GRAY); template_match_all_models(gray); per detection
 //     recognize_face_all_models(frame[y:y+h, x:x+w])
-//   `ef_scan_frame` queues the grey plane (`frame_gray_kernel`), the localiser's kernels
-//   (`tm_queue`, shared with ef_tm_match), the per-person choice with the corner rule
-//   (`scan_select_kernel`), the crops' grey + resize read in place from the grey plane
-//   (`roi_resize_kernel`, also ef_preprocess_rois) and the model bank's recognise
-//   (ef_bank.hip `bank_recognize_dev`) on one stream: one upload, one download, one wait.
+//   `frame_call`, shared with ef_haar_scan_frame (ef_haar.hip), queues the grey plane
+//   (`frame_gray_kernel`), the route's own step, the crops' grey + resize read in place from
+//   the grey plane (`roi_resize_kernel`, also ef_preprocess_rois) and the model bank's
+//   recognise (ef_bank.hip `bank_recognize_dev`) on one stream: one upload, one download, one
+//   wait.  `ef_scan_frame`'s step is the localiser's kernels (`tm_queue`, shared with
+//   ef_tm_match) and the per-person choice with the corner rule (`scan_select_kernel`).
 #include <algorithm>
 #include <climits>
 #include <cstddef>
@@ -950,22 +951,14 @@ __global__ __launch_bounds__(256) void scan_select_kernel(const unsigned long lo
 }
 
 // ------------------------------------------------------------------ ctx state
-// ef_scan_prepare's plan.  The result block of one frame is one device allocation
-// [dets | keys | best slots | rows] (each piece 256-byte aligned) with a pinned mirror, so a
-// host call downloads it with one copy.
+// ef_scan_prepare's plan.  The result block of one frame is [dets | keys | best slots | rows |
+// dffs2 | energy] (carve_frame_out behind a front of ef_scan_det[n_groups]).
 struct ScanPlan {
   int n_groups = 0, face_h = 0, face_w = 0;
   double threshold = 0.0;
   ScanCorner corner{};
   DevBuf prob_group;  // int[nprob]
-  DevBuf frame_in;    // a host call's frame, H rows of W * channels bytes
-  DevBuf gray;        // the grey plane of a colour frame, round_up(H * W, 4) bytes
-  DevBuf out;         // the result block
-  PinnedBuf host;     // its pinned mirror
-  // ef_scan_frame_gated, host form: the gate stays resident and is uploaded again only when its
-  // values change, so a frame still costs one upload
-  DevBuf gate;
-  std::vector<float> gate_host;
+  FrameIo io;
 };
 
 struct TmState {
@@ -1409,24 +1402,108 @@ int ef_preprocess_rois(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_
   return EF_OK;
 }
 
-// The pieces of a scan's result block for g groups, M bank slots and d face pixels.
-// gated: the distances from face space and the energies too, behind the ungated pieces
-struct ScanOut {
-  ef_scan_det* dets;
-  long long* keys;
-  int* best;
-  uint8_t* rows;
-  float* dffs2;
-  float* energy;
-};
-static ScanOut carve_scan_out(Carve& cv, size_t g, size_t M, size_t d, bool gated) {
-  ScanOut o{cv.take<ef_scan_det>(g), cv.take<long long>(g * M), cv.take<int>(g), cv.take<uint8_t>(g * d), nullptr, nullptr};
-  if (gated) {
-    o.dffs2 = cv.take<float>(g * M);
-    o.energy = cv.take<float>(g * M);
+}  // extern "C"
+
+namespace ef {
+
+// A host call's gate in io.gate: uploaded when its values differ from the resident copy's
+static int frame_gate_resident(ef_ctx* c, const std::string& w, FrameIo& io, const float* gate, size_t M) {
+  if (io.gate_host.size() == M && std::memcmp(io.gate_host.data(), gate, M * sizeof(float)) == 0) return EF_OK;
+  try {
+    io.gate_host.assign(gate, gate + M);
+  } catch (const std::bad_alloc&) {
+    return set_err(c, EF_E_NOMEM, w + ": host allocation failed");
   }
-  return o;
+  const hipError_t e = [&] {
+    if (ensure(c, io.gate, M * sizeof(float)) != EF_OK) return hipErrorOutOfMemory;
+    return hipMemcpyAsync(io.gate.p, io.gate_host.data(), M * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  }();
+  if (e != hipSuccess) {
+    io.gate_host.clear();  // nothing resident: the next call uploads again
+    return hip_err(c, e, "H2D gate");
+  }
+  return EF_OK;
 }
+
+int frame_call(ef_ctx* c, const char* who, int timer, const FrameShape& fs, FrameIo& io, const FrameFront& front,
+               const FrameArgs& a, const FrameMiddle& middle) {
+  const std::string w(who);
+  Bank& bk = c->bank;
+  if (bk.slots.empty()) return set_err(c, EF_E_STATE, w + ": the bank is empty (call ef_bank_add)");
+  const int64_t d = (int64_t)fs.face_h * fs.face_w;
+  if (bk.d != d)
+    return set_err(c, EF_E_STATE, w + ": the bank's models take " + std::to_string(bk.d) +
+                                      " pixels, the plan's faces have " + std::to_string(d));
+  if (c->comm && c->comm_size > 1) return set_err(c, EF_E_STATE, w + ": not available with a communicator attached");
+  const bool gated = a.gate != nullptr;
+  if (gated) EF_TRY(bank_recon_complete(c, who));
+  const int H = fs.H, W = fs.W, channels = a.channels;
+  bool outs = a.out.keys && (!gated || a.out.dffs2);
+  for (int i = 0; i < front.n; ++i) outs = outs && a.out.front[i];
+  if (!a.frame || !outs || (channels != 1 && channels != 3 && channels != 4) || a.frame_ld < (int64_t)W * channels ||
+      (a.metric != EF_METRIC_L2 && a.metric != EF_METRIC_COSINE))
+    return set_err(c, EF_E_INVALID, w + ": bad arguments");
+  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
+  const bool dev = a.flags & EF_MEM_DEVICE;
+  hipStream_t s = c->stream;
+  const size_t n = (size_t)fs.n, M = bk.slots.size();
+
+  // where the kernels write: the size pass says whether the result block is needed
+  Carve size_out;
+  FrameRoute rt = frame_route(a.out, dev, gated, carve_frame_out(size_out, front, n, M, (size_t)d, gated));
+  if (rt.need) {
+    EF_TRY(ensure(c, io.out, size_out.total));
+    Carve cv{io.out.p};
+    rt = frame_route(a.out, dev, gated, carve_frame_out(cv, front, n, M, (size_t)d, gated));
+  }
+  const FrameOut& o = rt.o;
+  BankGate bg{a.gate, (a.flags & EF_BANK_GATE_RELATIVE) != 0, o.dffs2, o.energy};
+  if (gated && !dev) {
+    EF_TRY(frame_gate_resident(c, w, io, a.gate, M));
+    bg.gate = static_cast<const float*>(io.gate.p);
+  }
+  if (!dev && io.host.bytes < size_out.total) EF_HIP(c, pinned_alloc(io.host, size_out.total), "pinned results");
+  const uint8_t* f = a.frame;
+  int64_t ld = a.frame_ld;
+  if (!dev) {
+    const int64_t row_bytes = (int64_t)W * channels;
+    EF_TRY(ensure(c, io.frame_in, (size_t)H * row_bytes));
+    EF_HIP(c, hipMemcpy2DAsync(io.frame_in.p, row_bytes, a.frame, a.frame_ld, row_bytes, H, hipMemcpyHostToDevice, s),
+           "H2D frame");
+    f = static_cast<const uint8_t*>(io.frame_in.p);
+    ld = row_bytes;
+  }
+  TimerEvt tev;
+  timer_begin(c, timer, &tev);
+  if (channels != 1) {
+    EF_HIP(c, launch_frame_gray(s, f, ld, H, W, channels, a.flags & EF_IMG_RGB, io.gray.p), "frame grey kernel");
+    f = static_cast<const uint8_t*>(io.gray.p);
+    ld = W;
+  }
+  FrameRects rects{};
+  EF_TRY(middle(f, ld, o.front, rects));
+  // grey of a crop == crop of the grey: the rows come straight from the route's rectangles
+  EF_HIP(c, launch_roi_resize(s, f, ld, H, W, 1, rects.p, rects.stride, fs.n, fs.face_h, fs.face_w, false, o.rows),
+         "ROI resize kernel");
+  EF_TRY(bank_recognize_dev(c, o.rows, EF_U8, fs.n, a.metric, o.keys, nullptr, o.best, nullptr, gated ? &bg : nullptr));
+  timer_end(c, &tev);
+  if (dev) return EF_OK;
+  EF_HIP(c, hipMemcpyAsync(io.host.p, io.out.p, size_out.total, hipMemcpyDeviceToHost, s), "D2H results");
+  EF_HIP(c, hipStreamSynchronize(s), "sync");
+  Carve hv{io.host.p};
+  const FrameOut h = carve_frame_out(hv, front, n, M, (size_t)d, gated);
+  for (int i = 0; i < front.n; ++i) std::memcpy(a.out.front[i], h.front[i], front.bytes[i]);
+  std::memcpy(a.out.keys, h.keys, n * M * sizeof(long long));
+  if (a.out.best) std::memcpy(a.out.best, h.best, n * sizeof(int));
+  if (a.out.rows) std::memcpy(a.out.rows, h.rows, n * (size_t)d);
+  if (gated) std::memcpy(a.out.dffs2, h.dffs2, n * M * sizeof(float));
+  if (gated && a.out.energy) std::memcpy(a.out.energy, h.energy, n * M * sizeof(float));
+  return EF_OK;
+}
+
+}  // namespace ef
+
+extern "C" {
 
 int ef_scan_prepare(ef_ctx* c, const int32_t* prob_group, int32_t n_groups, int32_t face_h, int32_t face_w,
                     double threshold) {
@@ -1452,7 +1529,7 @@ int ef_scan_prepare(ef_ctx* c, const int32_t* prob_group, int32_t n_groups, int3
   sp->corner = ScanCorner{t->W, t->H, (int)((double)t->W * 0.15), (int)((double)t->H * 0.15),
                           (int)((double)t->W * 0.05), (int)((double)t->H * 0.05)};
   EF_TRY(ensure(c, sp->prob_group, std::max<size_t>((size_t)t->nprob * sizeof(int), 16)));
-  EF_TRY(ensure(c, sp->gray, (size_t)round_up((int64_t)t->H * t->W, 4)));
+  EF_TRY(ensure(c, sp->io.gray, (size_t)round_up((int64_t)t->H * t->W, 4)));
   if (t->nprob > 0) {
     EF_HIP(c, hipMemcpyAsync(sp->prob_group.p, prob_group, (size_t)t->nprob * sizeof(int), hipMemcpyHostToDevice,
                              c->stream), "H2D groups");
@@ -1467,106 +1544,30 @@ static int scan_frame_call(ef_ctx* c, const char* who, const uint8_t* frame, int
                            int32_t metric, const float* gate, ef_scan_det* dets, int64_t* keys, int32_t* best_slot,
                            uint8_t* rows, float* dffs2, float* energy, uint32_t flags) {
   if (!c) return EF_E_INVALID;
-  const std::string w(who);
   TmState* t = c->tm;
   ScanPlan* sp = t ? t->scan.get() : nullptr;
-  if (!sp) return set_err(c, EF_E_STATE, w + ": no scan plan (call ef_tm_prepare, then ef_scan_prepare)");
-  Bank& bk = c->bank;
-  if (bk.slots.empty()) return set_err(c, EF_E_STATE, w + ": the bank is empty (call ef_bank_add)");
-  const int64_t d = (int64_t)sp->face_h * sp->face_w;
-  if (bk.d != d)
-    return set_err(c, EF_E_STATE, w + ": the bank's models take " + std::to_string(bk.d) +
-                                      " pixels, the scan plan's faces have " + std::to_string(d));
-  if (c->comm && c->comm_size > 1)
-    return set_err(c, EF_E_STATE, w + ": not available with a communicator attached");
-  if (gate) EF_TRY(bank_recon_complete(c, who));
-  if (!frame || !dets || !keys || (channels != 1 && channels != 3 && channels != 4) ||
-      frame_ld < (int64_t)t->W * channels || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE) || (gate && !dffs2))
-    return set_err(c, EF_E_INVALID, w + ": bad arguments");
-  EF_HIP(c, hipSetDevice(c->device), "hipSetDevice");
-  const bool dev = flags & EF_MEM_DEVICE;
-  hipStream_t s = c->stream;
-  const int H = t->H, W = t->W, G = sp->n_groups;
-  const size_t M = bk.slots.size();
-
-  // where the kernels write: the caller's device arrays, or the result block; the rows always
-  // exist (the bank reads them)
-  Carve size_out, cv;
-  const bool gated = gate != nullptr;
-  carve_scan_out(size_out, (size_t)G, M, (size_t)d, gated);
-  ScanOut o{dets, reinterpret_cast<long long*>(keys), best_slot, rows, dffs2, energy};
-  if (!dev || !rows || (gated && !energy)) {
-    EF_TRY(ensure(c, sp->out, size_out.total));
-    cv.base = sp->out.p;
-    const ScanOut blk = carve_scan_out(cv, (size_t)G, M, (size_t)d, gated);
-    if (!dev) {
-      o = blk;
-    } else {
-      if (!rows) o.rows = blk.rows;
-      if (!energy) o.energy = blk.energy;
-    }
-  }
-  BankGate bg{gate, (flags & EF_BANK_GATE_RELATIVE) != 0, o.dffs2, o.energy};
-  if (gated && !dev) {
-    if (sp->gate_host.size() != M || std::memcmp(sp->gate_host.data(), gate, M * sizeof(float)) != 0) {
-      try {
-        sp->gate_host.assign(gate, gate + M);
-      } catch (const std::bad_alloc&) {
-        return set_err(c, EF_E_NOMEM, w + ": host allocation failed");
-      }
-      const hipError_t e = [&] {
-        if (ensure(c, sp->gate, M * sizeof(float)) != EF_OK) return hipErrorOutOfMemory;
-        return hipMemcpyAsync(sp->gate.p, sp->gate_host.data(), M * sizeof(float), hipMemcpyHostToDevice, s);
-      }();
-      if (e != hipSuccess) {
-        sp->gate_host.clear();  // nothing resident: the next call uploads again
-        return hip_err(c, e, "H2D gate");
-      }
-    }
-    bg.gate = static_cast<const float*>(sp->gate.p);
-  }
-  if (!dev && sp->host.bytes < size_out.total) EF_HIP(c, pinned_alloc(sp->host, size_out.total), "pinned results");
-  const uint8_t* f = frame;
-  if (!dev) {
-    const int64_t row_bytes = (int64_t)W * channels;
-    EF_TRY(ensure(c, sp->frame_in, (size_t)H * row_bytes));
-    EF_HIP(c, hipMemcpy2DAsync(sp->frame_in.p, row_bytes, frame, frame_ld, row_bytes, H, hipMemcpyHostToDevice, s),
-           "H2D frame");
-    f = static_cast<const uint8_t*>(sp->frame_in.p);
-    frame_ld = row_bytes;
-  }
-  TimerEvt tev;
-  timer_begin(c, EF_KERNEL_SCAN, &tev);
-  if (channels != 1) {
-    EF_HIP(c, launch_frame_gray(s, f, frame_ld, H, W, channels, flags & EF_IMG_RGB, sp->gray.p), "frame grey kernel");
-    f = static_cast<const uint8_t*>(sp->gray.p);
-    frame_ld = W;
-  }
-  EF_TRY(tm_queue(c, t, f, frame_ld, nullptr, nullptr));
-  hipLaunchKernelGGL(scan_select_kernel, dim3((unsigned)G), dim3(256), 0, s,
-                     static_cast<const unsigned long long*>(t->keys.p), static_cast<const TmProblem*>(t->d_probs.p),
-                     static_cast<const int*>(sp->prob_group.p), t->nprob, sp->corner, sp->threshold, o.dets);
-  EF_HIP(c, hipGetLastError(), "scan selection kernel");
-  // grey of a crop == crop of the grey: the rectangles come straight from the dets (x, y, w, h
-  // are four consecutive ints of a 32-byte record; found = 0 leaves w = h = 0: a zero row)
-  static_assert(sizeof(ef_scan_det) == 32 && offsetof(ef_scan_det, x) == 8, "ef_scan_det layout");
-  EF_HIP(c, launch_roi_resize(s, f, frame_ld, H, W, 1, &o.dets->x, 8, G, sp->face_h, sp->face_w, false, o.rows),
-         "ROI resize kernel");
-  EF_TRY(bank_recognize_dev(c, o.rows, EF_U8, G, metric, o.keys, nullptr, o.best, nullptr, gated ? &bg : nullptr));
-  timer_end(c, &tev);
-  if (dev) return EF_OK;
-  EF_HIP(c, hipMemcpyAsync(sp->host.p, sp->out.p, size_out.total, hipMemcpyDeviceToHost, s), "D2H results");
-  EF_HIP(c, hipStreamSynchronize(s), "sync");
-  Carve hv;
-  hv.base = sp->host.p;
-  const ScanOut h = carve_scan_out(hv, (size_t)G, M, (size_t)d, gated);
-  std::memcpy(dets, h.dets, (size_t)G * sizeof(ef_scan_det));
-  std::memcpy(keys, h.keys, (size_t)G * M * sizeof(long long));
-  if (best_slot) std::memcpy(best_slot, h.best, (size_t)G * sizeof(int));
-  if (rows) std::memcpy(rows, h.rows, (size_t)G * d);
-  if (gated) std::memcpy(dffs2, h.dffs2, (size_t)G * M * sizeof(float));
-  if (gated && energy) std::memcpy(energy, h.energy, (size_t)G * M * sizeof(float));
-  return EF_OK;
+  if (!sp)
+    return set_err(c, EF_E_STATE, std::string(who) + ": no scan plan (call ef_tm_prepare, then ef_scan_prepare)");
+  const int G = sp->n_groups;
+  // the localiser reads the grey plane at its own stride: a strided grey frame is not copied
+  const FrameMiddle select = [&](const uint8_t*& f, int64_t& ld, void* const* front, FrameRects& rects) -> int {
+    ef_scan_det* out = static_cast<ef_scan_det*>(front[0]);
+    EF_TRY(tm_queue(c, t, f, ld, nullptr, nullptr));
+    hipLaunchKernelGGL(scan_select_kernel, dim3((unsigned)G), dim3(256), 0, c->stream,
+                       static_cast<const unsigned long long*>(t->keys.p), static_cast<const TmProblem*>(t->d_probs.p),
+                       static_cast<const int*>(sp->prob_group.p), t->nprob, sp->corner, sp->threshold, out);
+    EF_HIP(c, hipGetLastError(), "scan selection kernel");
+    // the rectangles come straight from the dets (x, y, w, h are four consecutive ints of a
+    // 32-byte record; found = 0 leaves w = h = 0: a zero row)
+    static_assert(sizeof(ef_scan_det) == 32 && offsetof(ef_scan_det, x) == 8, "ef_scan_det layout");
+    rects = FrameRects{&out->x, 8};
+    return EF_OK;
+  };
+  return frame_call(c, who, EF_KERNEL_SCAN, FrameShape{t->H, t->W, sp->face_h, sp->face_w, G}, sp->io,
+                    FrameFront{1, {(size_t)G * sizeof(ef_scan_det)}},
+                    FrameArgs{frame, frame_ld, channels, metric, gate,
+                              FrameOut{{dets}, reinterpret_cast<long long*>(keys), best_slot, rows, dffs2, energy}, flags},
+                    select);
 }
 
 int ef_scan_frame(ef_ctx* c, const uint8_t* frame, int64_t frame_ld, int32_t channels, int32_t metric,

@@ -227,6 +227,66 @@ inline PrefixWs carve_prefix_ws(Carve& cv, size_t bpad, int k1, int kp) {
                   cv.take<long long>(bpad), cv.take<ef_match>(bpad)};
 }
 
+// ---- one frame of a scan: what the template and the Haar route share (frame_call below) ----
+// A plan's buffers for a frame's way in and out.  The result block of one frame is one device
+// allocation with a pinned mirror, so a host call downloads it with one copy.
+struct FrameIo {
+  DevBuf frame_in;  // a host call's frame, H rows of W * channels bytes
+  DevBuf gray;      // the grey plane of a colour frame (Haar: or of a strided grey one), round_up(H * W, 4) bytes
+  DevBuf out;       // the result block
+  PinnedBuf host;   // its pinned mirror
+  // a gated host call's gate stays resident and is uploaded again only when its values change,
+  // so a frame still costs one upload
+  DevBuf gate;
+  std::vector<float> gate_host;
+};
+// The front of a result block is the route's own, one or two pieces of so many bytes: the
+// template route's ef_scan_det[g]; the Haar route's ef_haar_scan_head[1], then int[g * 4].
+constexpr int kFrameFrontMax = 2;
+struct FrameFront {
+  int n;
+  size_t bytes[kFrameFrontMax];
+};
+// The pieces of a result block for g rectangles, M bank slots and d face pixels: the front and,
+// behind it, what every route returns.  gated: the distances from face space and the energies
+// too, last, so the ungated block is a prefix of the gated one.  Also how a call's own output
+// arrays are passed around (front[i]: the caller's array for piece i).
+struct FrameOut {
+  void* front[kFrameFrontMax];
+  long long* keys;  // [g][M]
+  int* best;        // [g]
+  uint8_t* rows;    // [g][d]
+  float* dffs2;     // [g][M]
+  float* energy;    // [g][M]
+};
+inline FrameOut carve_frame_out(Carve& cv, const FrameFront& fr, size_t g, size_t M, size_t d, bool gated) {
+  FrameOut o{};
+  for (int i = 0; i < fr.n; ++i) o.front[i] = cv.take<char>(fr.bytes[i]);
+  o.keys = cv.take<long long>(g * M);
+  o.best = cv.take<int>(g);
+  o.rows = cv.take<uint8_t>(g * d);
+  if (gated) {
+    o.dffs2 = cv.take<float>(g * M);
+    o.energy = cv.take<float>(g * M);
+  }
+  return o;
+}
+// Where a frame's kernels write.  The host form: everything into the block.  The device form:
+// the caller's arrays, except that the rows (the bank reads them) and, gated, the energy (the
+// gate's kernels write it) fall back to the block when the caller passes none.  need: the block
+// is used at all; a size pass's null block answers that before anything is allocated.
+struct FrameRoute {
+  FrameOut o;
+  bool need;
+};
+inline FrameRoute frame_route(const FrameOut& caller, bool dev, bool gated, const FrameOut& blk) {
+  if (!dev) return FrameRoute{blk, true};
+  FrameRoute r{caller, false};
+  if (!caller.rows) r.o.rows = blk.rows, r.need = true;
+  if (gated && !caller.energy) r.o.energy = blk.energy, r.need = true;
+  return r;
+}
+
 // ---- the plan of one search (host only: no HIP call) --------------------------------
 // What a search of b probes against n rows of padded width kp launches: the pieces
 // (search_pieces), every piece's plan built from that piece's own bpad (a shorter last piece's
@@ -563,6 +623,36 @@ hipError_t launch_frame_gray(hipStream_t s, const uint8_t* src, int64_t ld, int 
 hipError_t launch_roi_resize(hipStream_t s, const uint8_t* frame, int64_t ld, int fh, int fw, int c, const int* rects,
                              int rect_stride, int64_t n, int oh, int ow, bool rgb, uint8_t* dst);
 void img_desc_fill(void* d, int64_t src_off, int64_t dst_off, int h, int w, int c, int oh, int ow);
+// One frame through grey, a route's own kernels, the ROI rows and the model bank (ef_image.hip):
+// the body of ef_scan_frame, ef_scan_frame_gated and ef_haar_scan_frame behind their "no plan"
+// checks.  It checks the bank's state and the arguments (messages prefixed with `who`), routes
+// the outputs (frame_route), keeps a host call's gate resident, and queues on c->stream: the
+// host form's upload, then between timer_begin(timer) and timer_end the grey plane, `middle`,
+// the ROI rows and the bank; the host form then downloads the block once, synchronises once and
+// copies the pieces out.
+struct FrameShape {
+  int H, W, face_h, face_w;
+  int n;  // rectangles recognised per frame: the template route's groups, the Haar route's max_faces
+};
+struct FrameArgs {  // as the entry point got them; out.front[i]: the caller's array for front piece i
+  const uint8_t* frame;
+  int64_t frame_ld;
+  int32_t channels, metric;
+  const float* gate;  // null: ungated
+  FrameOut out;
+  uint32_t flags;
+};
+struct FrameRects {  // what launch_roi_resize reads
+  const int* p;
+  int stride;
+};
+// The route's step: f is the grey plane on the device, rows ld bytes apart (packed for a colour
+// frame; a route that needs packed rows packs a strided grey frame itself and updates f and ld).
+// It queues the route's kernels, which write the front pieces at front[i], and names the
+// rectangles they leave.
+using FrameMiddle = std::function<int(const uint8_t*& f, int64_t& ld, void* const* front, FrameRects& rects)>;
+int frame_call(ef_ctx* c, const char* who, int timer, const FrameShape& fs, FrameIo& io, const FrameFront& front,
+               const FrameArgs& a, const FrameMiddle& middle);
 // wait for every queued JPEG upload and decode of the context (ef_jpeg.hip)
 hipError_t jpeg_quiesce(ef_ctx* c);
 // hipFuncSetAttribute(fn, MaxDynamicSharedMemorySize, bytes) once per (kernel, device),

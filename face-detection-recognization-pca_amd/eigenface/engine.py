@@ -36,6 +36,41 @@ def _dev(x, torch_dtype):
     return x, x.data_ptr()
 
 
+def _ptr(a):
+    return None if a is None else a.data_ptr() if _is_dev(a) else a.ctypes.data
+
+
+def _empty(shape, dtype, device):
+    """An uninitialised output: a NumPy array for ``device`` None, else a tensor on ``device``."""
+    if device is None:
+        return np.empty(shape, dtype)
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=device)
+
+
+def _gate_arg(gate, device, M):
+    """(array or tensor, pointer) of a face gate (M,) float32: NumPy for ``device`` None, else a
+    tensor on ``device`` (an array is uploaded)."""
+    if device is None:
+        g, gp = _host(gate, np.float32)
+    else:
+        import torch
+        g = gate if _is_dev(gate) else torch.as_tensor(np.asarray(gate, np.float32), device=device)
+        g, gp = _dev(g, torch.float32)
+    if tuple(g.shape) != (M,):
+        raise ValueError(f"gate must be ({M},), got {tuple(g.shape)}")
+    return g, gp
+
+
+def _frame_outputs(n, M, d, gated, device):
+    """What every frame scan returns behind its route's own outputs: [keys (n, M) int64, best_slot
+    (n,) int32, rows (n, d) uint8] and, gated, [dffs2, energy] (n, M) float32."""
+    out = [_empty((n, M), np.int64, device), _empty(n, np.int32, device), _empty((n, d), np.uint8, device)]
+    if gated:
+        out += [_empty((n, M), np.float32, device), _empty((n, M), np.float32, device)]
+    return out
+
+
 _OPTIONS = {"fit_max_iters": N.EF_OPT_FIT_MAX_ITERS, "fit_fp32_coarse": N.EF_OPT_FIT_FP32_COARSE,
             "cov_slab_bytes": N.EF_OPT_COV_SLAB_BYTES, "tm_int64_sums": N.EF_OPT_TM_INT64_SUMS,
             "haar_ordered": N.EF_OPT_HAAR_ORDERED, "jpeg_chunk_bits": N.EF_OPT_JPEG_CHUNK_BITS,
@@ -1078,12 +1113,9 @@ class Engine:
                                                         None, None, None, 0))
         p, pp, dtype, b, dev = self._bank_pixels(P, d)
         flags = N.EF_BANK_GATE_RELATIVE if relative else 0
+        g, gp = _gate_arg(gate, p.device if dev else None, M)
         if dev:
             import torch
-            g = gate if _is_dev(gate) else torch.as_tensor(np.asarray(gate, np.float32), device=p.device)
-            g, gp = _dev(g, torch.float32)
-            if tuple(g.shape) != (M,):
-                raise ValueError(f"gate must be ({M},), got {tuple(g.shape)}")
             keys = torch.empty((b, M), dtype=torch.int64, device=p.device)
             rec = torch.empty((b, M, 3), dtype=torch.int64, device=p.device) if matches else None
             best = torch.empty(b, dtype=torch.int32, device=p.device)
@@ -1096,9 +1128,6 @@ class Engine:
                     best.data_ptr(), eps.data_ptr(), en.data_ptr(), feats.data_ptr() if features else None,
                     flags | N.EF_MEM_DEVICE))
             return keys, rec, best, feats, eps, en
-        g, gp = _host(gate, np.float32)
-        if g.shape != (M,):
-            raise ValueError(f"gate must be ({M},), got {g.shape}")
         keys = np.empty((b, M), dtype=np.int64)
         rec = np.empty((b, M), dtype=N.MATCH_DTYPE) if matches else None
         best = np.empty(b, dtype=np.int32)
@@ -1385,29 +1414,28 @@ class Engine:
             # the library reports the state error
             self._chk(self._lib.ef_scan_frame(self._h, None, 0, 1, mt, None, None, None, None, 0))
             raise RuntimeError("call scan_prepare first")
+        return self._scan_frame(frame, mt, False, None, False, rgb)
+
+    def _scan_frame(self, frame, mt, gated, gate, relative, rgb):
+        """scan_frame (ef_scan_frame) and, ``gated``, scan_frame_gated (ef_scan_frame_gated)."""
         (G, fh, fw), H, W = self._scan, self._tm[1], self._tm[2]
         f, fp, ld, h, w, ch, dev = self._frame_view(frame)
         if (h, w) != (H, W):
             raise ValueError(f"frame must be {(H, W)}, got {(h, w)}")
         M = self.bank_info()[0]
-        flags = N.EF_IMG_RGB if rgb else 0
-        if dev:
-            import torch
-            dets = torch.empty((G, 8), dtype=torch.int32, device=f.device)
-            keys = torch.empty((G, M), dtype=torch.int64, device=f.device)
-            best = torch.empty(G, dtype=torch.int32, device=f.device)
-            rows = torch.empty((G, fh * fw), dtype=torch.uint8, device=f.device)
-            with self._torch_order(f, dets, keys, best, rows):
-                self._chk(self._lib.ef_scan_frame(self._h, fp, ld, ch, mt, dets.data_ptr(), keys.data_ptr(),
-                                                  best.data_ptr(), rows.data_ptr(), flags | N.EF_MEM_DEVICE))
-            return dets, keys, best, rows
-        dets = np.empty(G, dtype=N.SCAN_DET_DTYPE)
-        keys = np.empty((G, M), dtype=np.int64)
-        best = np.empty(G, dtype=np.int32)
-        rows = np.empty((G, fh * fw), dtype=np.uint8)
-        self._chk(self._lib.ef_scan_frame(self._h, fp, ld, ch, mt, dets.ctypes.data, keys.ctypes.data,
-                                          best.ctypes.data, rows.ctypes.data, flags))
-        return dets, keys, best, rows
+        device = f.device if dev else None
+        flags = ((N.EF_IMG_RGB if rgb else 0) | (N.EF_BANK_GATE_RELATIVE if gated and relative else 0) |
+                 (N.EF_MEM_DEVICE if dev else 0))
+        g, gp = _gate_arg(gate, device, M) if gated else (None, None)
+        dets = _empty((G, 8), np.int32, device) if dev else np.empty(G, dtype=N.SCAN_DET_DTYPE)
+        out = _frame_outputs(G, M, fh * fw, gated, device)
+        args = [_ptr(a) for a in [dets] + out] + [flags]
+        with self._torch_order(f, g, dets, *out) if dev else contextlib.nullcontext():
+            if gated:
+                self._chk(self._lib.ef_scan_frame_gated(self._h, fp, ld, ch, mt, gp, *args))
+            else:
+                self._chk(self._lib.ef_scan_frame(self._h, fp, ld, ch, mt, *args))
+        return (dets, *out)
 
     def scan_frame_gated(self, frame, gate, metric="cosine", relative=True, rgb=False):
         """:meth:`scan_frame` whose recognition step is :meth:`bank_recognize_gated`
@@ -1420,42 +1448,7 @@ class Engine:
             self._chk(self._lib.ef_scan_frame_gated(self._h, None, 0, 1, mt, one.ctypes.data, None, None, None, None,
                                                     None, None, 0))
             raise RuntimeError("call scan_prepare first")
-        (G, fh, fw), H, W = self._scan, self._tm[1], self._tm[2]
-        f, fp, ld, h, w, ch, dev = self._frame_view(frame)
-        if (h, w) != (H, W):
-            raise ValueError(f"frame must be {(H, W)}, got {(h, w)}")
-        M = self.bank_info()[0]
-        flags = (N.EF_IMG_RGB if rgb else 0) | (N.EF_BANK_GATE_RELATIVE if relative else 0)
-        if dev:
-            import torch
-            g = gate if _is_dev(gate) else torch.as_tensor(np.asarray(gate, np.float32), device=f.device)
-            g, gp = _dev(g, torch.float32)
-            if tuple(g.shape) != (M,):
-                raise ValueError(f"gate must be ({M},), got {tuple(g.shape)}")
-            dets = torch.empty((G, 8), dtype=torch.int32, device=f.device)
-            keys = torch.empty((G, M), dtype=torch.int64, device=f.device)
-            best = torch.empty(G, dtype=torch.int32, device=f.device)
-            rows = torch.empty((G, fh * fw), dtype=torch.uint8, device=f.device)
-            eps = torch.empty((G, M), dtype=torch.float32, device=f.device)
-            en = torch.empty((G, M), dtype=torch.float32, device=f.device)
-            with self._torch_order(f, g, dets, keys, best, rows, eps, en):
-                self._chk(self._lib.ef_scan_frame_gated(self._h, fp, ld, ch, mt, gp, dets.data_ptr(), keys.data_ptr(),
-                                                        best.data_ptr(), rows.data_ptr(), eps.data_ptr(),
-                                                        en.data_ptr(), flags | N.EF_MEM_DEVICE))
-            return dets, keys, best, rows, eps, en
-        g, gp = _host(gate, np.float32)
-        if g.shape != (M,):
-            raise ValueError(f"gate must be ({M},), got {g.shape}")
-        dets = np.empty(G, dtype=N.SCAN_DET_DTYPE)
-        keys = np.empty((G, M), dtype=np.int64)
-        best = np.empty(G, dtype=np.int32)
-        rows = np.empty((G, fh * fw), dtype=np.uint8)
-        eps = np.empty((G, M), dtype=np.float32)
-        en = np.empty((G, M), dtype=np.float32)
-        self._chk(self._lib.ef_scan_frame_gated(self._h, fp, ld, ch, mt, gp, dets.ctypes.data, keys.ctypes.data,
-                                                best.ctypes.data, rows.ctypes.data, eps.ctypes.data, en.ctypes.data,
-                                                flags))
-        return dets, keys, best, rows, eps, en
+        return self._scan_frame(frame, mt, True, gate, relative, rgb)
 
     # ------------------------------------------------------ Haar route in one call
     def haar_group(self, rects, min_neighbors=3, max_rects=None):
@@ -1533,47 +1526,18 @@ class Engine:
         if (h, w) != (H, W):
             raise ValueError(f"frame must be {(H, W)}, got {(h, w)}")
         M = self.bank_info()[0]
+        device = f.device if dev else None
         gated = gate is not None
-        flags = (N.EF_IMG_RGB if rgb else 0) | (N.EF_BANK_GATE_RELATIVE if gated and relative else 0)
-        if dev:
-            import torch
-            t = {"device": f.device}
-            gp = None
-            if gated:
-                g = gate if _is_dev(gate) else torch.as_tensor(np.asarray(gate, np.float32), device=f.device)
-                g, gp = _dev(g, torch.float32)
-                if tuple(g.shape) != (M,):
-                    raise ValueError(f"gate must be ({M},), got {tuple(g.shape)}")
-            head = torch.empty(4, dtype=torch.int32, **t)
-            rects = torch.empty((F, 4), dtype=torch.int32, **t)
-            keys = torch.empty((F, M), dtype=torch.int64, **t)
-            best = torch.empty(F, dtype=torch.int32, **t)
-            rows = torch.empty((F, fh * fw), dtype=torch.uint8, **t)
-            eps = torch.empty((F, M), dtype=torch.float32, **t) if gated else None
-            en = torch.empty((F, M), dtype=torch.float32, **t) if gated else None
-            with self._torch_order(f, g if gated else None, head, rects, keys, best, rows, eps, en):
-                self._chk(self._lib.ef_haar_scan_frame(self._h, fp, ld, ch, mt, gp, head.data_ptr(), rects.data_ptr(),
-                                                       keys.data_ptr(), best.data_ptr(), rows.data_ptr(),
-                                                       eps.data_ptr() if gated else None,
-                                                       en.data_ptr() if gated else None, flags | N.EF_MEM_DEVICE))
-            return (head, rects, keys, best, rows) + ((eps, en) if gated else ())
-        gp = None
-        if gated:
-            g, gp = _host(gate, np.float32)
-            if g.shape != (M,):
-                raise ValueError(f"gate must be ({M},), got {g.shape}")
-        head = np.zeros(1, dtype=N.HAAR_SCAN_HEAD_DTYPE)
-        rects = np.empty((F, 4), dtype=np.int32)
-        keys = np.empty((F, M), dtype=np.int64)
-        best = np.empty(F, dtype=np.int32)
-        rows = np.empty((F, fh * fw), dtype=np.uint8)
-        eps = np.empty((F, M), dtype=np.float32) if gated else None
-        en = np.empty((F, M), dtype=np.float32) if gated else None
-        self._chk(self._lib.ef_haar_scan_frame(self._h, fp, ld, ch, mt, gp, head.ctypes.data, rects.ctypes.data,
-                                               keys.ctypes.data, best.ctypes.data, rows.ctypes.data,
-                                               eps.ctypes.data if gated else None, en.ctypes.data if gated else None,
-                                               flags))
-        return (head[0], rects, keys, best, rows) + ((eps, en) if gated else ())
+        flags = ((N.EF_IMG_RGB if rgb else 0) | (N.EF_BANK_GATE_RELATIVE if gated and relative else 0) |
+                 (N.EF_MEM_DEVICE if dev else 0))
+        g, gp = _gate_arg(gate, device, M) if gated else (None, None)
+        head = _empty(4, np.int32, device) if dev else np.zeros(1, dtype=N.HAAR_SCAN_HEAD_DTYPE)
+        rects = _empty((F, 4), np.int32, device)
+        out = _frame_outputs(F, M, fh * fw, gated, device)
+        args = [_ptr(a) for a in [head, rects] + out] + [None] * (5 - len(out)) + [flags]
+        with self._torch_order(f, g, head, rects, *out) if dev else contextlib.nullcontext():
+            self._chk(self._lib.ef_haar_scan_frame(self._h, fp, ld, ch, mt, gp, *args))
+        return (head if dev else head[0], rects, *out)
 
     # --------------------------------------------------------------------- timing
     def timing(self, on=True):

@@ -97,6 +97,12 @@ def _is_model(m):
     return isinstance(m, dict) and ("eigenfaces" in m or "pca" in m)
 
 
+def _bank_resident(bank):
+    """The shared engine holding ``bank``'s slots and, when the bank has a face gate, their
+    reconstruction state: (re-)uploaded when someone else filled the engine's bank in between."""
+    return bank._engine(reconstruction=bank.gate is not None)
+
+
 class HaarScanner:
     """The Haar live loop (useless/scan.py:168-290, detection-v4.py:47-60: ``cvtColor`` ->
     ``detectMultiScale`` -> crop -> resize -> recognise) with one GPU call per frame
@@ -158,11 +164,7 @@ class HaarScanner:
             eng.haar_scan_prepare(self.frame_shape, self.scale_factor, self.min_neighbors, self.min_size, self.max_size,
                                   self.face_size, self.max_faces, self.max_candidates)
             eng.haar_scan_owner = self
-        if getattr(eng, "bank_owner", None) is not self.bank:
-            self.bank.refresh()
-        if self.bank.gate is not None and not self.bank._recon_up:
-            self.bank._upload_reconstruction(eng)
-        return eng
+        return _bank_resident(self.bank)
 
     def _separate_calls(self, eng, frame, rgb):
         """The frame through the calls ef_haar_scan_frame fuses, in its result layout."""
@@ -269,9 +271,7 @@ class FrameScanner:
             self.localiser._prepare()
             eng.scan_prepare(self.prob_group, max(len(self.persons), 1), FACE_SIZE, self.threshold)
             eng.scan_owner = self
-        if getattr(eng, "bank_owner", None) is not self.bank:
-            self.bank.refresh()
-        return eng
+        return _bank_resident(self.bank)
 
     def scan_raw(self, frame, rgb=False):
         """``Engine.scan_frame`` on this scanner's plan: (dets, keys, best_slot, rows); with a
@@ -279,8 +279,6 @@ class FrameScanner:
         eng = self._prepare()
         if self.bank.gate is None:
             return eng.scan_frame(frame, "cosine", rgb=rgb)
-        if not self.bank._recon_up:
-            self.bank._upload_reconstruction(eng)
         return eng.scan_frame_gated(frame, self.bank.gate, "cosine", relative=True, rgb=rgb)
 
     def scan(self, frame, rgb=False):

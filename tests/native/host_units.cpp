@@ -4,6 +4,8 @@
 // defined here (they take precedence over the shared library's) and only count.
 //   * Carve / carve_search_ws / carve_prefix_ws against the workspace arithmetic of the
 //     search written out by hand;
+//   * carve_frame_out, the frame scans' result block behind either route's front, against its
+//     layout written out by hand, and frame_route over every form of a call's outputs;
 //   * search_schedule, the plan every search runs and ef_search_schedule reports: pieces,
 //     per-piece plans, their maxima and the carved totals against the same arithmetic;
 //   * DevBuf, PinnedBuf, Event, Stream: default-empty, move-construct and move-assign leave
@@ -99,6 +101,88 @@ static void check_carve(size_t parts, size_t bpad, int k1, int kp) {
   CHECK(reinterpret_cast<char*>(pw.keys2) == pb + off); off += nk2;
   CHECK(reinterpret_cast<char*>(pw.match2) == pb + off);
   pw.match2[bpad - 1].key = 1;
+}
+
+// ---- the frame scans' result block (carve_frame_out) and output routing (frame_route) ----
+// the block's size written out by hand: a front of dets[g] (32-byte records) or of head[1]
+// (16 bytes) and rects[g][4], then keys[g][M], best[g], rows[g][d] and, gated, dffs2 and energy
+static size_t frame_out_bytes(bool haar, size_t g, size_t M, size_t d, bool gated) {
+  const size_t front = haar ? al(16) + al(g * 16) : al(g * 32);
+  return front + al(g * M * 8) + al(g * 4) + al(g * d) + (gated ? 2 * al(g * M * 4) : 0);
+}
+
+static void check_frame_out(bool haar, size_t g, size_t M, size_t d) {
+  static_assert(sizeof(ef_scan_det) == 32 && sizeof(ef_haar_scan_head) == 16, "front records");
+  const FrameFront fr = haar ? FrameFront{2, {sizeof(ef_haar_scan_head), g * 4 * sizeof(int)}}
+                             : FrameFront{1, {g * sizeof(ef_scan_det)}};
+  std::vector<char> mem(frame_out_bytes(haar, g, M, d, true) + 256);
+  char* base = reinterpret_cast<char*>(al(reinterpret_cast<size_t>(mem.data())));
+  FrameOut both[2];
+  for (int gated = 0; gated <= 1; ++gated) {
+    Carve size;
+    const FrameOut none = carve_frame_out(size, fr, g, M, d, gated != 0);
+    CHECK(size.total == frame_out_bytes(haar, g, M, d, gated != 0));
+    CHECK(!none.front[0] && !none.front[1] && !none.keys && !none.best && !none.rows && !none.dffs2 && !none.energy);
+    Carve cv{base};
+    const FrameOut o = both[gated] = carve_frame_out(cv, fr, g, M, d, gated != 0);
+    CHECK(cv.total == size.total);  // the size pass and the pointer pass agree
+    // the pieces in order, each 256-byte aligned
+    size_t off = 0;
+    CHECK(static_cast<char*>(o.front[0]) == base + off); off += al(haar ? 16 : g * 32);
+    if (haar) { CHECK(static_cast<char*>(o.front[1]) == base + off); off += al(g * 16); }
+    else CHECK(o.front[1] == nullptr);
+    CHECK(reinterpret_cast<char*>(o.keys) == base + off); off += al(g * M * 8);
+    CHECK(reinterpret_cast<char*>(o.best) == base + off); off += al(g * 4);
+    CHECK(reinterpret_cast<char*>(o.rows) == base + off); off += al(g * d);
+    if (gated) {
+      CHECK(reinterpret_cast<char*>(o.dffs2) == base + off); off += al(g * M * 4);
+      CHECK(reinterpret_cast<char*>(o.energy) == base + off); off += al(g * M * 4);
+      o.energy[g * M - 1] = 1.f;  // the last piece lies inside the allocation
+    } else {
+      CHECK(!o.dffs2 && !o.energy);
+      o.rows[g * d - 1] = 1;
+    }
+    CHECK(off == size.total && off % 256 == 0);
+  }
+  // the ungated block is a byte prefix of the gated one
+  CHECK(both[0].front[0] == both[1].front[0] && both[0].front[1] == both[1].front[1] && both[0].keys == both[1].keys &&
+        both[0].best == both[1].best && both[0].rows == both[1].rows);
+  CHECK(frame_out_bytes(haar, g, M, d, false) + 2 * al(g * M * 4) == frame_out_bytes(haar, g, M, d, true));
+}
+
+static void check_frame_route() {
+  // distinct fake addresses: nothing is dereferenced
+  auto at = [](size_t v) { return reinterpret_cast<char*>(v); };
+  const FrameOut blk{{at(0x1000), at(0x1100)}, reinterpret_cast<long long*>(at(0x1200)),
+                     reinterpret_cast<int*>(at(0x1300)), reinterpret_cast<uint8_t*>(at(0x1400)),
+                     reinterpret_cast<float*>(at(0x1500)), reinterpret_cast<float*>(at(0x1600))};
+  for (int dev = 0; dev <= 1; ++dev)
+    for (int has_rows = 0; has_rows <= 1; ++has_rows)
+      for (int has_energy = 0; has_energy <= 1; ++has_energy)
+        for (int gated = 0; gated <= 1; ++gated) {
+          const FrameOut caller{{at(0x2000), at(0x2100)}, reinterpret_cast<long long*>(at(0x2200)),
+                                reinterpret_cast<int*>(at(0x2300)),
+                                has_rows ? reinterpret_cast<uint8_t*>(at(0x2400)) : nullptr,
+                                reinterpret_cast<float*>(at(0x2500)),
+                                has_energy ? reinterpret_cast<float*>(at(0x2600)) : nullptr};
+          const FrameRoute r = frame_route(caller, dev != 0, gated != 0, blk);
+          const FrameOut& o = r.o;
+          if (!dev) {  // the host form writes everything into the block
+            CHECK(r.need);
+            CHECK(o.front[0] == blk.front[0] && o.front[1] == blk.front[1] && o.keys == blk.keys && o.best == blk.best &&
+                  o.rows == blk.rows && o.dffs2 == blk.dffs2 && o.energy == blk.energy);
+            continue;
+          }
+          // the device form writes to the caller's arrays ...
+          CHECK(o.front[0] == caller.front[0] && o.front[1] == caller.front[1] && o.keys == caller.keys &&
+                o.best == caller.best && o.dffs2 == caller.dffs2);
+          // ... except the rows and (gated) the energy, which fall back to the block exactly when null
+          CHECK(o.rows == (has_rows ? caller.rows : blk.rows));
+          CHECK(o.energy == (has_energy ? caller.energy : gated ? blk.energy : nullptr));
+          // and the block is asked for exactly when something falls back to it
+          CHECK(r.need == (o.rows == blk.rows || o.energy == blk.energy));
+          CHECK(r.need == (!has_rows || (gated && !has_energy)));
+        }
 }
 
 static bool same_plan(const SearchPlan& a, const SearchPlan& b) {
@@ -427,6 +511,15 @@ int main() {
   check_carve(1024 * 5, 1024, 64, 128);
   check_carve(4096 * 13, 4096, 16, 64);
   check_carve(33 * 1280, 1280, 32, 128);
+
+  // (template or Haar front, g, M, d)
+  for (int haar = 0; haar <= 1; ++haar) {
+    check_frame_out(haar != 0, 1, 1, 1);
+    check_frame_out(haar != 0, 3, 3, 4096);
+    check_frame_out(haar != 0, 8, 3, 1024);
+    check_frame_out(haar != 0, 64, 64, 4096);
+  }
+  check_frame_route();
 
   // (b, n, kp, pieces): planning only, nothing is allocated
   check_schedule(1, 1, 16, 1);

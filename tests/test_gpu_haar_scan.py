@@ -113,6 +113,90 @@ def test_gated_scan_equals_the_gated_bank_call(case):
     assert len(sc.scan(case["bgr"])) == 4
 
 
+def _same(host, dev):
+    """Host-form results against device-form ones, bit for bit."""
+    assert len(dev) == len(host)
+    assert tuple(int(v) for v in dev[0].cpu()) == tuple(int(v) for v in host[0])
+    for a, b in zip(host[1:], dev[1:]):
+        np.testing.assert_array_equal(a.view(np.uint8), b.cpu().numpy().view(np.uint8))
+
+
+def test_gated_device_form_equals_the_host_form(case):
+    """A device frame with the gate as a device tensor, and as a NumPy array (uploaded by the
+    wrapper), against the gated host form."""
+    import torch
+    sc = _scanner(case, face_gate=0.5)
+    host = sc.scan_raw(case["bgr"])
+    assert len(host) == 7
+    eng = sc._prepare()
+    frame = torch.as_tensor(case["bgr"], device="cuda")
+    for gate in (torch.as_tensor(sc.bank.gate, device="cuda"), sc.bank.gate):
+        dev = eng.haar_scan_frame(frame, "cosine", gate=gate, relative=True)
+        torch.cuda.synchronize()
+        _same(host, dev)
+
+
+def test_device_form_without_the_optional_outputs(case):
+    """ef_haar_scan_frame on device pointers, gated, with best_slot, rows and energy left out (the
+    rows and the energy then live in the plan's result block): head, rects, keys and dffs2 are byte
+    for byte those of the call that is given every output, and those of the host form."""
+    import torch
+    from eigenface import _native as N
+    sc = _scanner(case, face_gate=0.5)
+    host = sc.scan_raw(case["bgr"])
+    eng = sc._prepare()
+    F, M, d = sc.max_faces, 3, u.FACE * u.FACE
+    frame = torch.as_tensor(case["bgr"], device="cuda")
+    gate = torch.as_tensor(sc.bank.gate, device="cuda")
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def call(optional):
+        t = {"device": "cuda"}
+        head = torch.zeros(4, dtype=torch.int32, **t)
+        rects = torch.zeros((F, 4), dtype=torch.int32, **t)
+        keys = torch.zeros((F, M), dtype=torch.int64, **t)
+        eps = torch.zeros((F, M), dtype=torch.float32, **t)
+        best = torch.zeros(F, dtype=torch.int32, **t) if optional else None
+        rows = torch.zeros((F, d), dtype=torch.uint8, **t) if optional else None
+        en = torch.zeros((F, M), dtype=torch.float32, **t) if optional else None
+        with eng._torch_order(frame, gate, head, rects, keys, eps, best, rows, en):
+            eng._chk(eng._lib.ef_haar_scan_frame(eng._h, frame.data_ptr(), u.SHAPE[1] * 3, 3, N.EF_METRIC_COSINE,
+                                                 ptr(gate), ptr(head), ptr(rects), ptr(keys), ptr(best), ptr(rows),
+                                                 ptr(eps), ptr(en), N.EF_BANK_GATE_RELATIVE | N.EF_MEM_DEVICE))
+        torch.cuda.synchronize()
+        return [head, rects, keys, best, rows, eps, en]
+
+    bare, full = call(False), call(True)
+    for i in (0, 1, 2, 5):
+        np.testing.assert_array_equal(bare[i].cpu().numpy().view(np.uint8), full[i].cpu().numpy().view(np.uint8))
+    _same(host, full)
+
+
+def test_host_gate_is_uploaded_again_when_its_values_change(case):
+    """Three host frames with gate A, gate B, then A again: the gate stays resident between calls,
+    and each frame's best slots, dffs2 and energy are the bank's own gated call on the returned
+    rows with that frame's gate.  B rejects the two slots A accepts the known faces in, so a gate
+    left over from the frame before would change the best slots."""
+    sc = _scanner(case, face_gate=0.5)
+    eng = sc._prepare()
+    gate_a = sc.bank.gate
+    gate_b = np.array([-1.0, np.inf, -1.0], np.float32)
+    outs = []
+    for gate in (gate_a, gate_b, gate_a):
+        out = eng.haar_scan_frame(case["bgr"], "cosine", gate=gate, relative=True)
+        _, _, best2, _, eps2, en2 = eng.bank_recognize_gated_raw(out[4], gate, "cosine", relative=True)
+        np.testing.assert_array_equal(out[3], best2)
+        np.testing.assert_array_equal(out[5].view(np.int32), eps2.view(np.int32))
+        np.testing.assert_array_equal(out[6].view(np.int32), en2.view(np.int32))
+        outs.append(out)
+    assert not np.array_equal(outs[0][3], outs[1][3])
+    assert tuple(outs[2][0]) == tuple(outs[0][0])
+    for a, b in zip(outs[0][1:], outs[2][1:]):
+        np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
 def test_frame_without_a_detection(case, scanner):
     flat = np.full(u.SHAPE + (3,), 117, np.uint8)
     head, rects, keys, best, rows = scanner.scan_raw(flat)

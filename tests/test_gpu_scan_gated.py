@@ -76,6 +76,45 @@ def test_gated_scan_equals_the_plain_scan_and_the_bank_s_gated_call(case):
         np.testing.assert_array_equal(got.cpu().numpy(), want)
 
 
+def test_device_form_without_the_optional_outputs(case):
+    """ef_scan_frame_gated on device pointers with best_slot, rows and energy left out (the rows and
+    the energy then live in the plan's result block): dets, keys and dffs2 are byte for byte those of
+    the call that is given every output, and those of the host form."""
+    import torch
+    from eigenface import FrameScanner, _native as N
+    sc = FrameScanner(case["models"], (180, 240), face_gate=0.1)
+    host = sc.scan_raw(case["frame"])
+    eng = sc._prepare()
+    G, M, d = 3, 3, 64 * 64
+    frame = torch.as_tensor(case["frame"], device="cuda")
+    gate = torch.as_tensor(sc.bank.gate, device="cuda")
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def call(optional):
+        t = {"device": "cuda"}
+        dets = torch.zeros((G, 8), dtype=torch.int32, **t)
+        keys = torch.zeros((G, M), dtype=torch.int64, **t)
+        eps = torch.zeros((G, M), dtype=torch.float32, **t)
+        best = torch.zeros(G, dtype=torch.int32, **t) if optional else None
+        rows = torch.zeros((G, d), dtype=torch.uint8, **t) if optional else None
+        en = torch.zeros((G, M), dtype=torch.float32, **t) if optional else None
+        with eng._torch_order(frame, gate, dets, keys, eps, best, rows, en):
+            eng._chk(eng._lib.ef_scan_frame_gated(eng._h, frame.data_ptr(), 240 * 3, 3, N.EF_METRIC_COSINE, ptr(gate),
+                                                  ptr(dets), ptr(keys), ptr(best), ptr(rows), ptr(eps), ptr(en),
+                                                  N.EF_BANK_GATE_RELATIVE | N.EF_MEM_DEVICE))
+        torch.cuda.synchronize()
+        return [None if a is None else a.cpu().numpy() for a in (dets, keys, best, rows, eps, en)]
+
+    bare, full = call(False), call(True)
+    for i in (0, 1, 4):
+        np.testing.assert_array_equal(bare[i].view(np.uint8), full[i].view(np.uint8))
+    np.testing.assert_array_equal(full[0].reshape(-1), host[0].view(np.int32).reshape(-1))
+    for got, want in zip(full[1:], host[1:]):
+        np.testing.assert_array_equal(got.view(np.uint8), want.view(np.uint8))
+
+
 def test_a_matched_patch_that_is_no_face_is_unknown(case):
     from eigenface import FrameScanner
     frame = case["frame"]
