@@ -892,10 +892,120 @@ int ef_gallery_set(ef_ctx* c, const float* G, int64_t n, int32_t k, int64_t offs
   if (kp < 0) return set_err(c, EF_E_INVALID, "ef_gallery_set: k > 65536 is not supported");
   (void)hipSetDevice(c->device);
   c->der.reset();  // the copies and the guard's history belong to the gallery they were made from
+  c->has_labels = false;  // and so do the row labels (ef_gallery_labels)
+  release(c->glabels);
   DevBuf staging;
   EF_TRY(gallery_load(c, c->gal, G, n, k, flags, staging, &c->gmax2_host));
   c->g_offset = offset;
   return EF_OK;
+}
+
+int ef_gallery_labels(ef_ctx* c, const int32_t* labels, int64_t n, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (c->gal.k == 0) return set_err(c, EF_E_STATE, "ef_gallery_labels: no gallery (call ef_gallery_set)");
+  (void)hipSetDevice(c->device);
+  if (!labels) {  // drop them, once no queued search reads them any more
+    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+    c->has_labels = false;
+    release(c->glabels);
+    return EF_OK;
+  }
+  if (n != c->gal.n)
+    return set_err(c, EF_E_INVALID, "ef_gallery_labels: n differs from the resident gallery's row count");
+  // the new state is built completely, then published: a failure leaves the previous labels
+  DevBuf nb;
+  EF_TRY(ensure(c, nb, (size_t)n * sizeof(int32_t)));
+  if (n > 0)
+    EF_HIP(c,
+           hipMemcpyAsync(nb.p, labels, (size_t)n * sizeof(int32_t),
+                          (flags & EF_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
+           "copy labels");
+  EF_HIP(c, hipStreamSynchronize(c->stream), "copy labels");  // also: nothing queued reads the old ones
+  c->glabels = std::move(nb);
+  c->has_labels = true;
+  return EF_OK;
+}
+
+// The labelled top-1 search of the probes in ctx->q_pad (search_run's contract): always the fp32
+// scan (no split copy, no prefix scan), piece by piece; the probes' labels and exclusions
+// (plab, pexcl: launch_label_prep's output for all round_up(b, 256) rows) and the outputs advance
+// with the piece's offset.
+static int search_labelled_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, int relation, const int* plab,
+                               const int* pexcl, long long* keys_dev, ef_match* match_dev) {
+  const Gallery& g = c->gal;
+  if (g.n == 0) {
+    EF_HIP(c, launch_keys_none(c->stream, keys_dev, b, match_dev), "keys");
+    return EF_OK;
+  }
+  if (bpad < round_up(b, kSearchProbeTile))
+    return set_err(c, EF_E_INVALID, "labelled search: probe buffer shorter than the batch");
+  const SearchSchedule sc = search_schedule(b, g.n, g.kp, 0, 0, false, 0, 0);
+  EF_TRY(ensure(c, c->search_ws, sc.ws_bytes));
+  Carve cv{c->search_ws.p};
+  SearchWs ws = carve_search_ws(cv, sc.parts, (size_t)sc.bpad_max);
+  ws.lbl = relation + 1;
+  ws.glab = relation == EF_LABEL_ANY ? nullptr : static_cast<const int*>(c->glabels.p);
+  const float* G = static_cast<const float*>(g.G.p);
+  const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? g.gnorm2.p : g.ginv.p);
+  for (size_t i = 0; i < sc.pieces.size(); ++i) {
+    const SearchPiece& p = sc.pieces[i];
+    ws.match = match_dev ? match_dev + p.off : nullptr;
+    ws.plab = plab + p.off;
+    ws.pexcl = pexcl + p.off;
+    EF_HIP(c,
+           launch_search(c->stream, g.kp, metric, SplitScan{}, sc.plans[i],
+                         static_cast<const float*>(c->q_pad.p) + p.off * g.kp, p.bpad, p.b, G, aux, g.n, c->g_offset,
+                         c->gmax2_host, ws, keys_dev + p.off, c),
+           "labelled search");
+  }
+  return EF_OK;
+}
+
+int ef_search_labelled(ef_ctx* c, const float* Q, int64_t b, int32_t metric, int32_t relation,
+                       const int32_t* probe_labels, const int64_t* exclude_rows, int64_t* keys, ef_match* matches,
+                       uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (c->gal.k == 0) return set_err(c, EF_E_STATE, "ef_search_labelled: no gallery (call ef_gallery_set)");
+  const bool any = relation == EF_LABEL_ANY;
+  if ((!keys && !matches) || b < 0 || (b > 0 && !Q) || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE) ||
+      (relation != EF_LABEL_SAME && relation != EF_LABEL_OTHER && !any) || (!any && b > 0 && !probe_labels))
+    return set_err(c, EF_E_INVALID, "ef_search_labelled: bad arguments");
+  if (!any && !c->has_labels)
+    return set_err(c, EF_E_STATE, "ef_search_labelled: the gallery has no labels (call ef_gallery_labels)");
+  if (c->comm && c->comm_size > 1)
+    return set_err(c, EF_E_STATE, "ef_search_labelled: no labelled search over a communicator; search each shard "
+                                  "for its records on a context without one and merge them with ef_matches_merge");
+  if (b == 0) return EF_OK;
+  (void)hipSetDevice(c->device);
+  Results r{(flags & EF_MEM_DEVICE) != 0, b, 1, c->k, keys, matches, nullptr};
+  const int64_t bpad = round_up(b, kSearchProbeTile);
+  EF_TRY(stage_queries(c, Q, b, r.dev, bpad));
+  EF_TRY(r.stage_keys(c, bpad));
+  // scratch: plab[bpad], pexcl[bpad], then a host call's labels and exclusions
+  const size_t lab_off = align256((size_t)2 * bpad * sizeof(int));
+  const size_t exc_off = lab_off + align256((size_t)b * sizeof(int32_t));
+  EF_TRY(ensure(c, c->label_ws, exc_off + (size_t)b * sizeof(int64_t)));
+  char* base = static_cast<char*>(c->label_ws.p);
+  int* plab = reinterpret_cast<int*>(base);
+  int* pexcl = plab + bpad;
+  if (!r.dev) {
+    if (probe_labels) {
+      EF_HIP(c, hipMemcpyAsync(base + lab_off, probe_labels, (size_t)b * sizeof(int32_t), hipMemcpyHostToDevice, c->stream),
+             "H2D probe labels");
+      probe_labels = reinterpret_cast<const int32_t*>(base + lab_off);
+    }
+    if (exclude_rows) {
+      EF_HIP(c, hipMemcpyAsync(base + exc_off, exclude_rows, (size_t)b * sizeof(int64_t), hipMemcpyHostToDevice, c->stream),
+             "H2D excluded rows");
+      exclude_rows = reinterpret_cast<const int64_t*>(base + exc_off);
+    }
+  }
+  EF_HIP(c,
+         launch_label_prep(c->stream, any ? nullptr : probe_labels, exclude_rows, b, bpad, c->g_offset, c->gal.n, plab,
+                           pexcl),
+         "label prep");
+  EF_TRY(search_labelled_run(c, bpad, b, metric, relation, plab, pexcl, r.kdev, r.mdev));
+  return r.fetch(c);
 }
 
 // Top-m search of the probes in ctx->q_pad (search_run's contract): keys_dev[b][m] and,

@@ -55,6 +55,13 @@ struct SearchWs {
   int* cand_cnt;        // [bpad]
   ef_match* match;      // [b] exact merge records (fp64 winner score), may be null
   int cand_cap;         // rows kept per slot in cand (kCandMax; the top-m search sets its own), read on a hit
+  // labelled search (ef_search_labelled): read by the labelled instantiations of
+  // the scan kernels and of resolve_kernel alone, which launch_search_scan / top1_t pick when
+  // lbl != 0.  lbl = 0: a plain search; else EF_LABEL_* + 1.
+  const int* glab;      // [n] label of each gallery row; null for EF_LABEL_ANY
+  const int* plab;      // [bpad] label of each probe of the piece
+  const int* pexcl;     // [bpad] the probe's excluded local row, -1 for none (label_prep_kernel)
+  int lbl;
 };
 
 struct SearchPlan {
@@ -457,6 +464,10 @@ struct ef_ctx {
   ef::Gallery gal;       // gal.k == 0: none set yet
   int64_t g_offset = 0;  // global index of row 0
   float gmax2_host = 0.f;
+  // one label per gallery row (ef_gallery_labels); ef_gallery_set drops them
+  bool has_labels = false;
+  ef::DevBuf glabels;   // int32[gal.n]
+  ef::DevBuf label_ws;  // per-call scratch of ef_search_labelled: int[2][bpad], then the host call's staging
   ef::GalleryDerived der;  // the split and prefix copies and the prefix guard (search_copies)
   int64_t opt_search_prefix = 1;
   int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32
@@ -582,9 +593,15 @@ hipError_t launch_split_rows(hipStream_t s, const float* G, int64_t n, int kp, v
 // single-bf16 copy for the bf16 screen (EF_OPT_SEARCH_SPLIT_BF16 = 3), kp % 64 == 0
 hipError_t launch_hi_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);
 hipError_t launch_keys_none(hipStream_t s, long long* keys, int64_t b, ef_match* match);
-// One scan launch, the only map from (kp, metric, variant, main or COLLECT, cnt) to a scan
+// Labelled search (ef_search_labelled): plab[rows] / pexcl[rows] <- the probes' labels (0 when
+// plabels is null) and their excluded rows as local row indices, -1 for "none" (excl null, a
+// negative entry, one outside [g_offset, g_offset + n), and the rows past b)
+hipError_t launch_label_prep(hipStream_t s, const int32_t* plabels, const int64_t* excl, int64_t b, int64_t rows,
+                             int64_t g_offset, int64_t n, int* plab, int* pexcl);
+// One scan launch, the only map from (kp, metric, variant, main or COLLECT, cnt, labelled) to a scan
 // kernel: search_kernel, search16_kernel (kp == 128 under variant 1) and, kp > 128, the wide
-// kernels; variant 3 counts as 1 at kp <= 128.  The main pass writes per-chunk top-2 records
+// kernels; variant 3 counts as 1 at kp <= 128.  ws.lbl != 0 picks the labelled instantiations
+// (fp32 scan only: variant 0, no cnt).  The main pass writes per-chunk top-2 records
 // into ws, the COLLECT pass sweeps ws's queue.  q / G: what the variant reads (the fp32 probes
 // and gallery for 0, else the copies; at kp <= 128 the kernels split the fp32 probes themselves).
 // cnt: the main pass over a device-side probe count (the prefix path's second run: fp32, L2,

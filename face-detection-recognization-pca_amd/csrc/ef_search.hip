@@ -89,7 +89,10 @@ __device__ __forceinline__ void split8(const float* x, bf16x8& hi, bf16x8& lo) {
 // per-tile costs (barrier, DMA issue and wait, first LDS reads) show; 128 rows halve them.
 // The split-bf16 prefix scan (S3) has a quarter of the fp32 scan's MFMA cycles per tile and
 // takes 256 rows, two groups of four chains (64 KiB of LDS, still two workgroups per CU).
-template <int KP, int METRIC, bool COLLECT, bool S3 = false, bool CNT = false, int TGT = TG>
+// LBL (ef_search_labelled): the tile's row labels are staged beside its aux
+// values (wave 1 issues that DMA), and every finished block's scores pass label_mask before
+// consume — the fp32 scan at TGT = 64 only.
+template <int KP, int METRIC, bool COLLECT, bool S3 = false, bool CNT = false, int TGT = TG, bool LBL = false>
 __global__ __launch_bounds__(512, 4) void search_kernel(
     const float* __restrict__ qpad, const float* __restrict__ G, const float* __restrict__ aux, int64_t n,
     int n_ptiles, int tiles_per_chunk, int64_t bpad, SearchWs ws) {
@@ -104,6 +107,7 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   static_assert((NI % NW == 0 || NI < NW) && RP * CPR == 64 && TG == 64, "tile must be whole 1-KiB pieces");
   static_assert(TGT == 64 || (KP <= 32 && !COLLECT && TGT == (S3 ? kPrefixSplitTile : kPrefixTile)),
                 "larger tiles: the prefix scans at KP <= 32");
+  static_assert(!LBL || (!S3 && !CNT && TGT == TG), "labelled: the fp32 scan in 64-row tiles");
   constexpr int NBG = 4;  // S3 at TGT > 64: blocks run at once (4 x 16 accumulators fit 128 VGPRs)
   // KP = 128 (the k = 128 headline shape): no swizzle.  LDS piece p (1 KiB + 16 B pad)
   // holds row p of the tile's first 32-row block and row 32 + p of the second, so the
@@ -119,9 +123,13 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   // chunk order inside each row is XOR-swizzled by (row & (SW-1)) on the SOURCE address so
   // the A-fragment ds_read_b128s (16 lanes = 16 rows, same logical chunk) hit distinct
   // banks.  All LDS lives in one array (a second __shared__ object can de-pipeline).
-  __shared__ __attribute__((aligned(16))) float smem[2 * TGS + 2 * TGT];
+  __shared__ __attribute__((aligned(16))) float smem[2 * TGS + 2 * TGT + (LBL ? 2 * TGT + 2 * 512 : 0)];
   float* const sG0 = smem;
   float* const sAux0 = smem + 2 * TGS;
+  constexpr int LAB0 = 2 * TGS + 2 * TGT;  // LBL: the two tiles' row labels (int bits)
+  // LBL: each lane's (probe label, excluded row - 4 h), parked in LDS and re-read per tile: held
+  // in registers for the sweep, the pair costs search_kernel<128> (126 VGPRs without it) spills
+  constexpr int STASH0 = LAB0 + 2 * TGT;
 
   // one (gallery chunk gc, probe tile pt) work item
   auto body = [&](const int gc, const int pt, const int n_amb) {
@@ -161,6 +169,9 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
       if (nrem == TGT) {
         const unsigned long long gb = uniform_ptr(G + t * TGT * KP);
         if (wave == 0) glds4s(lid * 4u, uniform_ptr(aux + t * TG), lds_base + (unsigned)((2 * TGS + buf * TG) * 4));
+        if constexpr (LBL) {
+          if (wave == 1 && ws.glab) glds4s(lid * 4u, uniform_ptr(ws.glab + t * TG), lds_base + (unsigned)((LAB0 + buf * TG) * 4));
+        }
         const unsigned voff = ((lid >> 5) * 32 * KP + (lid & 31) * 4) * 4;
 #pragma unroll
         for (int jj = 0; jj < PPW; ++jj) {
@@ -179,6 +190,12 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
         if (wave == 0) {
           const int row = (int)lid < nrem ? (int)lid : nrem - 1;
           glds4(aux + t * TG + row, lds_base + (unsigned)((2 * TGS + buf * TG) * 4));
+        }
+        if constexpr (LBL) {
+          if (wave == 1 && ws.glab) {
+            const int row = (int)lid < nrem ? (int)lid : nrem - 1;
+            glds4(ws.glab + t * TG + row, lds_base + (unsigned)((LAB0 + buf * TG) * 4));
+          }
         }
       }
       return;
@@ -199,6 +216,9 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
       }
       if constexpr (TGT == 64) {
         if (wave == 0) glds4s((unsigned)lane * 4u, uniform_ptr(aux + t * TG), lds_base + (unsigned)((2 * TGS + buf * TG) * 4));
+        if constexpr (LBL) {
+          if (wave == 1 && ws.glab) glds4s((unsigned)lane * 4u, uniform_ptr(ws.glab + t * TG), lds_base + (unsigned)((LAB0 + buf * TG) * 4));
+        }
       } else {  // one 64-row half of the norms per wave
         if (wave < TGT / 64)
           glds4s((unsigned)lane * 4u, uniform_ptr(aux + t * TGT + wave * 64),
@@ -220,6 +240,12 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
         if (wave == 0) {
           const int row = lane < nrem ? lane : nrem - 1;
           glds4(aux + t * TG + row, lds_base + (unsigned)((2 * TGS + buf * TG) * 4));  // one 4-B piece per lane
+        }
+        if constexpr (LBL) {
+          if (wave == 1 && ws.glab) {
+            const int row = lane < nrem ? lane : nrem - 1;
+            glds4(ws.glab + t * TG + row, lds_base + (unsigned)((LAB0 + buf * TG) * 4));
+          }
         }
       } else {
         if (wave < TGT / 64) {
@@ -246,6 +272,10 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
     if constexpr (COLLECT) {
       v0 = s0 < n_amb;
       r0 = v0 ? ws.amb_list[s0] : 0;
+    }
+    if constexpr (LBL) {  // read back by this lane alone: no barrier
+      const LabelLane l = label_lane(ws, r0, h);
+      *reinterpret_cast<int2*>(smem + STASH0 + 2 * tid) = make_int2(l.plab, l.excl_h);
     }
     const float4* q0 = reinterpret_cast<const float4*>(qpad + r0 * KP + h * KH);
     if constexpr (S3) {
@@ -495,8 +525,21 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
         if (row + 32 >= n) acc1[r] = INF;
       }
     }
-    consume(acc0, tbase);  // rows of block 0 precede block 1 (row-order tie rule)
-    consume(acc1, tbase + 32);
+    if constexpr (LBL) {  // rows that do not qualify for this lane's probe: +inf as well
+      const float* tileL = smem + LAB0 + buf * TGT;
+      unsigned lid;  // re-derived in place, as in issue_tile
+      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
+      const int2 pe = *reinterpret_cast<const int2*>(smem + STASH0 + 2 * (wave * 64 + (int)lid));
+      const LabelLane lab{pe.x, pe.y, ws.lbl == EF_LABEL_OTHER + 1, ws.lbl == EF_LABEL_ANY + 1};
+      // block 1 is masked after block 0 is consumed: its label registers take block 0's place
+      label_mask(acc0, tileL, tbase, h, lab);
+      consume(acc0, tbase);
+      label_mask(acc1, tileL + 32, tbase + 32, h, lab);
+      consume(acc1, tbase + 32);
+    } else {
+      consume(acc0, tbase);  // rows of block 0 precede block 1 (row-order tie rule)
+      consume(acc1, tbase + 32);
+    }
     dma_wait_all();
     __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
   }
@@ -832,7 +875,9 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ q
 
 // fp64 resolution of queued probes: lowest index among candidates whose fp64 score is
 // within 1e-12 (relative) of the best — exact ties resolve like np.argmin/argmax.
-template <int KP, int METRIC>
+// LBL (ef_search_labelled): rows that do not qualify for the probe are passed over.  The
+// COLLECT pass queued qualifying rows only; the overflow sweep over all rows needs the rule.
+template <int KP, int METRIC, bool LBL = false>
 __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ qpad, const float* __restrict__ G,
                                                       int64_t n, int64_t g_offset, float gmax2, SearchWs ws,
                                                       long long* __restrict__ keys, int kp_rt) {
@@ -848,6 +893,9 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
   auto row_of = [&](int64_t j) -> int64_t { return overflow ? j : (int64_t)ws.cand[slot * kCandMax + j]; };
   double vmin = INFINITY;
   for (int64_t j = 0; j < m; ++j) {
+    if constexpr (LBL) {
+      if (!label_row_ok(ws, p, row_of(j))) continue;  // wave-uniform
+    }
     const double v = score64<KP, METRIC>(q, G + row_of(j) * kpv, lane, kpv);
     vmin = v < vmin ? v : vmin;
   }
@@ -861,6 +909,9 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
   double best_v = vmin;
   for (int64_t j = 0; j < m; ++j) {
     const int64_t r = row_of(j);
+    if constexpr (LBL) {
+      if (!label_row_ok(ws, p, r)) continue;
+    }
     const double v = score64<KP, METRIC>(q, G + r * kpv, lane, kpv);
     if (v <= vmin + tol && r < best_row) { best_row = r; best_v = v; }
   }
@@ -1154,7 +1205,13 @@ static hipError_t scan_t(hipStream_t s, bool collect, int variant, bool cnt, con
                          const float* G, const float* aux, int64_t n, int64_t bpad, const SearchWs& ws) {
   const dim3 grid(collect ? (unsigned)pl.c_grid : (unsigned)(pl.nchunks * pl.n_ptiles)), block(512);
   const int a = collect ? pl.c_chunks : pl.n_ptiles, t = collect ? pl.c_tpc : pl.tiles_per_chunk;
-  if (cnt) {
+  if (ws.lbl) {  // labelled search: the fp32 scan's labelled instantiations
+    if (cnt || variant) return hipErrorInvalidValue;
+    if (collect)
+      hipLaunchKernelGGL((search_kernel<KP, M, true, false, false, TG, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+    else
+      hipLaunchKernelGGL((search_kernel<KP, M, false, false, false, TG, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
+  } else if (cnt) {
     if constexpr (M == EF_METRIC_L2 && KP >= 32) {
       if (collect || variant) return hipErrorInvalidValue;
       hipLaunchKernelGGL((search_kernel<KP, M, false, false, true>), grid, block, 0, s, q, G, aux, n, a, t, bpad, ws);
@@ -1242,7 +1299,10 @@ static hipError_t top1_t(hipStream_t s, int variant, bool cnt, const SearchPlan&
   }
 #undef EF_REDUCE
   if ((e = launch_search_scan(s, kp, M, true, variant, false, pl, qs, Gs, aux, n, bpad, ws)) != hipSuccess) return e;
-  hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, pblock, 0, s, q, G, n, g_offset, gmax2, ws, keys, kp);
+  if (ws.lbl)
+    hipLaunchKernelGGL((resolve_kernel<KP, M, true>), pgrid, pblock, 0, s, q, G, n, g_offset, gmax2, ws, keys, kp);
+  else
+    hipLaunchKernelGGL((resolve_kernel<KP, M>), pgrid, pblock, 0, s, q, G, n, g_offset, gmax2, ws, keys, kp);
   return hipGetLastError();
 }
 
@@ -1362,6 +1422,25 @@ __global__ void keys_fill_kernel(long long* keys, int64_t b, ef_match* match) {
 
 hipError_t launch_keys_none(hipStream_t s, long long* keys, int64_t b, ef_match* match) {
   hipLaunchKernelGGL(keys_fill_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, s, keys, b, match);
+  return hipGetLastError();
+}
+
+// Labelled search: the probes' labels and excluded rows as the scan kernels read them
+__global__ void label_prep_kernel(const int32_t* __restrict__ plabels, const int64_t* __restrict__ excl, int64_t b,
+                                  int64_t rows, int64_t g_offset, int64_t n, int* __restrict__ plab,
+                                  int* __restrict__ pexcl) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  plab[i] = (i < b && plabels) ? plabels[i] : 0;
+  int64_t e = -1;
+  if (i < b && excl && excl[i] >= g_offset) e = excl[i] - g_offset;
+  pexcl[i] = (e >= 0 && e < n) ? (int)e : -1;
+}
+
+hipError_t launch_label_prep(hipStream_t s, const int32_t* plabels, const int64_t* excl, int64_t b, int64_t rows,
+                             int64_t g_offset, int64_t n, int* plab, int* pexcl) {
+  hipLaunchKernelGGL(label_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, plabels, excl, b, rows,
+                     g_offset, n, plab, pexcl);
   return hipGetLastError();
 }
 

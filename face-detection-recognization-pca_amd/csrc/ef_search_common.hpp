@@ -97,6 +97,49 @@ __device__ __forceinline__ float collect_threshold(const SearchWs& ws, int64_t s
   return thr;
 }
 
+// ---- labelled scan (ef_search_labelled) ----------------------------------
+// What a lane keeps of its probe for the whole sweep: the probe's label and its excluded
+// local row, less the lane half's row offset 4 h (so a block's row base plus a constant is
+// compared against it).  other / any are wave-uniform: the relation.
+struct LabelLane {
+  int plab, excl_h;
+  bool other, any;
+};
+__device__ __forceinline__ LabelLane label_lane(const SearchWs& ws, int64_t probe, int h) {
+  return LabelLane{ws.plab[probe], ws.pexcl[probe] - 4 * h, ws.lbl == EF_LABEL_OTHER + 1, ws.lbl == EF_LABEL_ANY + 1};
+}
+// Scores of one finished 32-row block (register r <-> row rowbase + (r & 3) + 8 (r >> 2) + 4 h)
+// whose row does not qualify become +inf, as the rows past the gallery's end do: the arg-best
+// epilogue and COLLECT then see the sub-gallery of qualifying rows.  labs: the block's 32 row
+// labels staged in LDS (not read for EF_LABEL_ANY, which has none).
+__device__ __forceinline__ void label_mask(f32x16& v, const float* labs, int rowbase, int h, const LabelLane& L) {
+  // the label reads stay behind the block's MFMAs: hoisted above them by the scheduler, their 16
+  // registers per block would be live across the chain (search_kernel then spills at every KP)
+  __builtin_amdgcn_sched_barrier(0);
+  // the excluded row relative to the block, compared against the 16 constants 8 q + j.  Opaque:
+  // left to itself the compiler hoists 32 loop-invariant 64-bit values excl_h - (8 q + j) out of
+  // the sweep (64 VGPRs; search_kernel<16> went from 76 VGPRs to 128 and spilled)
+  int d = L.excl_h - rowbase;
+  asm volatile("" : "+v"(d));
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (q == 2) __builtin_amdgcn_sched_barrier(0);  // two reads in flight at a time: 8 registers, not 16
+    const float4 x = *reinterpret_cast<const float4*>(labs + 8 * q + 4 * h);
+    const int l[4] = {__float_as_int(x.x), __float_as_int(x.y), __float_as_int(x.z), __float_as_int(x.w)};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool keep = (((l[j] == L.plab) != L.other) || L.any) && (d != 8 * q + j);
+      v[4 * q + j] = keep ? v[4 * q + j] : __builtin_inff();
+    }
+  }
+}
+// the same rule for one row, all lanes of a wave alike (resolve_kernel's sweep)
+__device__ __forceinline__ bool label_row_ok(const SearchWs& ws, int64_t probe, int64_t row) {
+  if (row == ws.pexcl[probe]) return false;
+  if (ws.lbl == EF_LABEL_ANY + 1) return true;
+  return (ws.glab[row] == ws.plab[probe]) != (ws.lbl == EF_LABEL_OTHER + 1);
+}
+
 // Rigorous bound on |scan score - exact score| (fp32 FMA chain of kpv terms, fp32 ||g||^2 /
 // 1/||g||, final rounding), doubled for two compared scores and doubled again as a safety
 // factor: delta = 4 e.  S3 is the scan's arithmetic (0 fp32, 1 split bf16, 2 single bf16),

@@ -52,7 +52,10 @@ struct WideGeom {
   }
 };
 
-template <int KP, int METRIC, bool COLLECT>
+// LBL (ef_search_labelled): the tile's row labels are staged behind its aux
+// values (wave 1 issues that DMA) and every finished block's scores pass label_mask before
+// consume, as in search_kernel.
+template <int KP, int METRIC, bool COLLECT, bool LBL = false>
 __global__ __launch_bounds__(256, 2) void search_wide_kernel(
     const float* __restrict__ qpad, const float* __restrict__ G, const float* __restrict__ aux, int64_t n,
     int n_ptiles, int tiles_per_chunk, int pblk, int cblk, int64_t bpad, SearchWs ws, int kp_rt) {
@@ -61,7 +64,9 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
   // [stage 0: gallery | probes][stage 1: gallery | probes][aux of even | odd tiles]
   // (aux is double-buffered by tile: the cosine epilogue reads it in the tile's last
   // slice, when the DMA of the next tile's first slice is already in flight)
-  __shared__ __attribute__((aligned(16))) float smem[4 * WSL + 2 * WR];
+  // LBL: [row labels of even | odd tiles] behind them, int bits
+  __shared__ __attribute__((aligned(16))) float smem[4 * WSL + 2 * WR + (LBL ? 2 * WR : 0)];
+  constexpr int LAB0 = 4 * WSL + 2 * WR;
 
   // one (gallery chunk gc, probe tile pt) work item
   auto body = [&](const int gc, const int pt, const int n_amb) {
@@ -114,11 +119,30 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
         glds4s(ao, ab, lds_base + (unsigned)((4 * WSL + ((t - t0) & 1) * WR + 64 * q) * 4));
       }
     }
+    if constexpr (LBL) {
+      if (jj == 3 && sl == 0 && wave == 1 && ws.glab) {  // the tile's row labels, clamped like aux
+        const unsigned long long lb = (unsigned long long)(size_t)(ws.glab + t * WR);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int rr = 64 * q + lane;
+          const unsigned ao = rr < nrem ? aoff + 256u * q : (unsigned)(nrem - 1) * 4;
+          glds4s(ao, lb, lds_base + (unsigned)((LAB0 + ((t - t0) & 1) * WR + 64 * q) * 4));
+        }
+      }
+    }
   };
   auto issue = [&](int64_t it, int buf) {
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) issue_piece(it, buf, jj);
   };
+
+  LabelLane lab{};  // LBL: the probe's label and excluded row, two registers for the sweep
+  if constexpr (LBL) {
+    int64_t r0 = s0;
+    if constexpr (COLLECT) r0 = s0 < n_amb ? ws.amb_list[s0] : 0;
+    lab = label_lane(ws, r0, h);
+    asm volatile("" ::"v"(lab.plab), "v"(lab.excl_h));  // settled before the loop, like thr
+  }
 
   const float INF = __builtin_inff();
   float b1 = INF, b2 = INF;
@@ -220,6 +244,8 @@ __global__ __launch_bounds__(256, 2) void search_wide_kernel(
           for (int r = 0; r < 16; ++r)
             if (tbase + rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= n) acc[rb][r] = INF;
         }
+        if constexpr (LBL)  // rows that do not qualify for this lane's probe: +inf as well
+          label_mask(acc[rb], smem + LAB0 + (int)(geo.tile(it) & 1) * WR + rb * 32, tbase + rb * 32, h, lab);
         consume(acc[rb], tbase + rb * 32);  // blocks in row order (tie rule)
       }
     }
@@ -821,7 +847,17 @@ static hipError_t wide_t(hipStream_t s, bool collect, int s3, const SearchPlan& 
       (int64_t)std::max(pl.tiles_per_chunk, pl.c_tpc) * ns >= ((int64_t)1 << 31))
     return hipErrorInvalidValue;
   // plan from search_plan(.., true); s3 = 1: the 16x16x32 kernel, 2: the 32x32x16 one
+  if (ws.lbl && s3) return hipErrorInvalidValue;  // labelled search: the fp32 scan only
   if (s3) return wide3_t<KP, M>(s, collect, s3 != 2, pl, qpad, G, aux, n, bpad, ws, kp);
+  if (ws.lbl) {
+    if (collect)
+      hipLaunchKernelGGL((search_wide_kernel<KP, M, true, true>), dim3((unsigned)pl.c_grid), block, 0, s, qpad, G, aux,
+                         n, pl.c_chunks, pl.c_tpc, pl.pblk, pl.cblk, bpad, ws, kp);
+    else
+      hipLaunchKernelGGL((search_wide_kernel<KP, M, false, true>), grid, block, 0, s, qpad, G, aux, n, pl.n_ptiles,
+                         pl.tiles_per_chunk, pl.pblk, pl.cblk, bpad, ws, kp);
+    return hipGetLastError();
+  }
   if (collect)
     hipLaunchKernelGGL((search_wide_kernel<KP, M, true>), dim3((unsigned)pl.c_grid), block, 0, s, qpad, G, aux, n,
                        pl.c_chunks, pl.c_tpc, pl.pblk, pl.cblk, bpad, ws, kp);

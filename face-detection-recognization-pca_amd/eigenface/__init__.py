@@ -11,6 +11,8 @@ from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_
 from .bank import ModelBank, best_over_models, face_gate_mask  # noqa: F401
 from .scanner import FrameScanner, HaarScanner, decide, label_bank, label_one, label_pair  # noqa: F401
 from .compat import face_space_distance, reconstruct_faces  # noqa: F401
+from .evaluate import (OpenSetRates, equal_error_threshold, evaluate_model, leave_one_out,  # noqa: F401
+                       open_set_rates)
 from .pca import (  # noqa: F401
     EigenfacePCA,
     get_engine,
@@ -35,4 +37,5 @@ __all__ = [
     "NativeLibraryError", "LIB_PATH", "save_gallery_cache", "load_gallery_cache", "ManualPCA",
     "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity", "ModelBank", "best_over_models",
     "FrameScanner", "HaarScanner", "decide", "label_one", "label_pair", "label_bank", "reconstruct_faces", "face_space_distance", "face_gate_mask", "bank_recon_schedule",
+    "leave_one_out", "open_set_rates", "equal_error_threshold", "evaluate_model", "OpenSetRates",
 ]

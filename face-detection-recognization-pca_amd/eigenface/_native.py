@@ -45,8 +45,10 @@ EF_OPT_SEARCH_PREFIX = 11
 EF_OPT_SEARCH_TOPK_CAND = 12
 EF_OPT_SEARCH_PREFIX_SPLIT = 13
 EF_TOPK_MAX = 64  # most ranks of a top-m search
+EF_LABEL_SAME, EF_LABEL_OTHER, EF_LABEL_ANY = 0, 1, 2  # ef_search_labelled relations
 EF_BANK_MAX_MODELS = 4096
 EF_BANK_MAX_PROBES = 4096  # per ef_bank_recognize call
+EF_E_INVALID, EF_E_STATE = -1, -3
 EF_E_NUMERIC = -5
 
 
@@ -146,6 +148,9 @@ _SIGS = {
     "ef_search_topk_matches": ([vp, vp, i64, i32, i32, vp, u32], C.c_int),
     "ef_matches_merge_topk": ([vp, vp, i32, i64, i32, vp, vp, u32], C.c_int),
     "ef_search_topk_stats": ([vp, C.POINTER(i64)], C.c_int),
+    # labelled search: added by symbol, EF_API_VERSION stays 7
+    "ef_gallery_labels": ([vp, vp, i64, u32], C.c_int),
+    "ef_search_labelled": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, u32], C.c_int),
     # model bank: added after API v7 without a version bump, so bound (and checked) by symbol
     "ef_bank_clear": ([vp], C.c_int),
     "ef_bank_add": ([vp, vp, vp, i64, i32, vp, i64, u32, C.POINTER(i32)], C.c_int),

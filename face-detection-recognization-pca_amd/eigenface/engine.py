@@ -17,6 +17,7 @@ import numpy as np
 from . import _native as N
 
 METRICS = {"l2": N.EF_METRIC_L2, "cosine": N.EF_METRIC_COSINE}
+_RELATIONS = {"same": N.EF_LABEL_SAME, "other": N.EF_LABEL_OTHER, "any": N.EF_LABEL_ANY}
 
 
 def _is_dev(x):
@@ -819,6 +820,78 @@ class Engine:
                 self._chk(self._lib.ef_matches_merge(self._h, parts.data_ptr(), nparts, b, keys.data_ptr(), None,
                                                      N.EF_MEM_DEVICE))
         return keys
+
+    # ---------------------------------------------------------- labelled search
+    def set_gallery_labels(self, labels):
+        """ef_gallery_labels: one int32 label per resident gallery row (a host array or a
+        device tensor); ``None`` drops the labels.  set_gallery drops them too."""
+        if self.gallery_k is None:
+            raise RuntimeError("no gallery: call set_gallery first")
+        if labels is None:
+            self._chk(self._lib.ef_gallery_labels(self._h, None, 0, 0))
+            return
+        if _is_dev(labels):
+            import torch
+            lab, lp = _dev(labels, torch.int32)
+            flags = N.EF_MEM_DEVICE
+        else:
+            lab, lp = _host(labels, np.int32)
+            flags = 0
+        if lab.ndim != 1:
+            raise ValueError("labels must be 1-D (n,)")
+        with self._order(flags != 0, lab):
+            self._chk(self._lib.ef_gallery_labels(self._h, lp, lab.shape[0], flags))
+
+    def _labelled(self, Q, probe_labels, relation, exclude_rows, metric, out, records):
+        mt = _metric(metric)
+        rel = _RELATIONS[relation.lower()] if isinstance(relation, str) else int(relation)
+        if self.gallery_k is None:
+            raise RuntimeError("no gallery: call set_gallery first")
+        q, qp, _, b, dev = self._probes(Q, pixels=False)
+
+        def per_probe(x, np_dtype, name):
+            if x is None:
+                return None, None
+            if dev:
+                import torch
+                if not _is_dev(x):
+                    x = torch.as_tensor(np.ascontiguousarray(x, dtype=np_dtype), device=q.device)
+                x, xp = _dev(x, getattr(torch, np.dtype(np_dtype).name))
+            else:
+                x, xp = _host(x, np_dtype)
+            if tuple(x.shape) != (b,):
+                raise ValueError(f"{name} must be ({b},), got {tuple(x.shape)}")
+            return x, xp
+
+        pl, plp = per_probe(probe_labels, np.int32, "probe_labels")
+        ex, exp = per_probe(exclude_rows, np.int64, "exclude_rows")
+        if pl is None and rel != N.EF_LABEL_ANY:
+            raise ValueError("probe_labels are required for the relations 'same' and 'other'")
+        out, op = self._result(q, dev, out, (b,), records, "out" if records else "keys")
+        with self._order(dev, q, pl, ex, out):
+            self._chk(self._lib.ef_search_labelled(self._h, qp, b, mt, rel, plp, exp, None if records else op,
+                                                   op if records else None, N.EF_MEM_DEVICE if dev else 0))
+        return out
+
+    def search_labelled_keys(self, Q, probe_labels, relation="same", exclude_rows=None, metric="l2", keys=None):
+        """ef_search_labelled: per probe the packed key search_keys would return on the
+        sub-gallery of the rows whose label stands in ``relation`` ("same", "other", "any") to
+        the probe's and whose global index is not ``exclude_rows[p]`` (negative: nothing
+        excluded); EF_KEY_NONE when no row qualifies.  Host arrays in, a host array out; device
+        tensors in, a device tensor out (stream-ordered, as search_keys)."""
+        return self._labelled(Q, probe_labels, relation, exclude_rows, metric, keys, False)
+
+    def search_labelled(self, Q, probe_labels, relation="same", exclude_rows=None, metric="l2"):
+        """(idx int64, best float32) of search_labelled_keys; (-1, NaN) where no row qualifies."""
+        keys = self.search_labelled_keys(Q, probe_labels, relation, exclude_rows, metric)
+        if _is_dev(keys):
+            keys = keys.cpu().numpy()
+        return decode_keys(keys, metric)
+
+    def search_labelled_matches(self, Q, probe_labels, relation="same", exclude_rows=None, metric="l2", out=None):
+        """The match records of the labelled search (as search_matches returns them): shards
+        searched one by one merge with merge_matches / merge_matches_host unchanged."""
+        return self._labelled(Q, probe_labels, relation, exclude_rows, metric, out, True)
 
     # ------------------------------------------------------------- top-m search
     def _topk_m(self, m):

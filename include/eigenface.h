@@ -306,6 +306,49 @@ int ef_matches_merge_topk(ef_ctx* ctx, const ef_match* parts, int32_t nparts, in
  * candidate rows re-scored in fp64}.  Synchronises the context's stream. */
 int ef_search_topk_stats(ef_ctx* ctx, int64_t out[4]);
 
+/* ------------------------------------------------- labelled search (leave-one-out)
+ * Added by symbol (EF_API_VERSION stays 7).  The nearest row of the probe's own identity (the
+ * genuine match) and the nearest row of any other identity (the impostor), with the probe's own
+ * gallery row left out: what a leave-one-out recognition rate and a threshold derived from a
+ * labelled gallery need.  The rows are masked inside the scan, so the answers carry ef_search's
+ * guarantee whatever the number of same-label rows in front of the nearest other-label one.
+ *
+ * ef_gallery_labels: one int32 label per resident gallery row (any value is an ordinary label),
+ *   copied to the device from host memory, or from device memory with EF_MEM_DEVICE.  EF_E_STATE
+ *   without a gallery; EF_E_INVALID when n differs from the resident row count; labels == NULL
+ *   drops the labels (n is not read); ef_gallery_set drops them, because the rows changed.  A
+ *   failed call leaves the previous labels in place.
+ * ef_search_labelled: Q[b*k] probe features -> keys[b] and / or matches[b] (at least one).  The
+ *   result for probe p is exactly what ef_search / ef_search_matches would return on the
+ *   sub-gallery of qualifying rows, the rows keeping their indices.  A row qualifies when its
+ *   label stands in `relation` to probe_labels[p] and its global index (local row +
+ *   global_offset, the index a key carries) is not exclude_rows[p]; a negative exclude_rows
+ *   entry, or one outside this shard, excludes nothing, and so does exclude_rows == NULL.  The
+ *   answer is the lowest qualifying row among those whose fp64 score is within
+ *   1e-12 * (|min| + scale) of the qualifying minimum, with ef_search's own scale: |q|^2 +
+ *   max |g|^2 of the WHOLE resident gallery for L2, 1 for cosine (the scan's error bound keeps
+ *   using the whole gallery's maximum as well: it remains an upper bound).  So with
+ *   EF_LABEL_OTHER and a probe label no row carries, or EF_LABEL_ANY without exclusion, keys and
+ *   records equal ef_search's bit for bit.  A probe with no qualifying row gets EF_KEY_NONE and
+ *   the record {+inf, 0, EF_KEY_NONE}, as an empty gallery gives.  The records merge across
+ *   shards with ef_matches_merge unchanged (pass global exclude_rows to every shard).
+ *   The call always runs the fp32 scan: EF_OPT_SEARCH_SPLIT_BF16 and EF_OPT_SEARCH_PREFIX are
+ *   ignored here, as the prefix scan is by the top-m search.  Every k of ef_search is supported.
+ *   Memory: ef_search's workspace plus O(b); no score matrix is written.
+ *   With EF_MEM_DEVICE every pointer is a device pointer and the call does not wait.  b = 0 is
+ *   EF_OK.  EF_E_STATE: no gallery; SAME or OTHER without gallery labels; a communicator of more
+ *   than one rank attached (search each shard on its own context and merge the records).
+ *   EF_E_INVALID: SAME or OTHER with probe_labels == NULL; an unknown relation or metric; neither
+ *   keys nor matches. */
+#define EF_LABEL_SAME  0   /* rows whose label equals the probe's                */
+#define EF_LABEL_OTHER 1   /* rows whose label differs from the probe's           */
+#define EF_LABEL_ANY   2   /* every row (labels not consulted; only the exclusion) */
+int ef_gallery_labels(ef_ctx* ctx, const int32_t* labels /* [n] or NULL */, int64_t n, uint32_t flags);
+int ef_search_labelled(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric, int32_t relation,
+                       const int32_t* probe_labels /* [b]; may be NULL for ANY */,
+                       const int64_t* exclude_rows /* [b] or NULL */,
+                       int64_t* keys /* [b] or NULL */, ef_match* matches /* [b] or NULL */, uint32_t flags);
+
 /* ------------------------------------------------------------------ model bank
  * Added after API v7 without a version bump (purely additive): detect the entry points by
  * symbol (dlsym / hasattr), not by ef_api_version().
