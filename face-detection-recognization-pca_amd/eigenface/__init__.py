@@ -5,14 +5,15 @@ Drop-in for the PCA / recognition hot path of saladbkp/face-detection-recognizat
 hand-written gfx950 HIP kernels in ``_lib/libeigenface.so`` (no CPU fallback).
 """
 from ._native import EigenfaceError, NativeLibraryError, LIB_PATH  # noqa: F401
-from .engine import (Engine, FitResult, bank_recon_schedule, decode_keys, device_count,  # noqa: F401
+from .engine import (Engine, FitResult, LdaResult, bank_recon_schedule, decode_keys, device_count,  # noqa: F401
                      merge_matches_host, merge_topk_host)
 from .manual import ManualPCA, ManualStandardScaler, cosine_similarity, project_face_to_eigenspace  # noqa: F401
 from .bank import ModelBank, best_over_models, face_gate_mask  # noqa: F401
 from .scanner import FrameScanner, HaarScanner, decide, label_bank, label_one, label_pair  # noqa: F401
 from .compat import face_space_distance, reconstruct_faces  # noqa: F401
-from .evaluate import (OpenSetRates, equal_error_threshold, evaluate_model, leave_one_out,  # noqa: F401
-                       open_set_rates)
+from .evaluate import (OpenSetRates, compare_subspaces, equal_error_threshold, evaluate_model,  # noqa: F401
+                       leave_one_out, open_set_rates)
+from .fisher import Fisherfaces  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
     get_engine,
@@ -38,4 +39,5 @@ __all__ = [
     "ManualStandardScaler", "project_face_to_eigenspace", "cosine_similarity", "ModelBank", "best_over_models",
     "FrameScanner", "HaarScanner", "decide", "label_one", "label_pair", "label_bank", "reconstruct_faces", "face_space_distance", "face_gate_mask", "bank_recon_schedule",
     "leave_one_out", "open_set_rates", "equal_error_threshold", "evaluate_model", "OpenSetRates",
+    "Fisherfaces", "LdaResult", "compare_subspaces",
 ]

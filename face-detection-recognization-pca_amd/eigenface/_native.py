@@ -178,6 +178,10 @@ _SIGS = {
     "ef_haar_scan_prepare": ([vp, i32, i32, C.c_double, i32, i32, i32, i32, i32, i32, i32, i32, i32], C.c_int),
     "ef_haar_scan_info": ([vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)], C.c_int),
     "ef_haar_scan_frame": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, u32], C.c_int),
+    # Fisher discriminant: class scatter and the generalised eigenproblem, bound by symbol
+    "ef_lda_order": ([vp, i64, i32, vp, vp], C.c_int),
+    "ef_lda_scatter": ([vp, vp, i32, i64, i32, vp, i32, vp, vp, vp, vp, vp, u32], C.c_int),
+    "ef_lda_fit": ([vp, vp, i32, i64, i32, vp, i32, i32, C.c_double, vp, vp, vp, vp, u32], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

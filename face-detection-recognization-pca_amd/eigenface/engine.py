@@ -123,6 +123,19 @@ class FitResult:
     iters: int
 
 
+@dataclass
+class LdaResult:
+    """Outputs of the Fisher discriminant fit (float64; NumPy, or tensors for device input).
+    ``scalings`` (k, m) maps features to the discriminant space: (f - anything) @ scalings
+    differs between two rows by the within-class Mahalanobis distance."""
+
+    scalings: np.ndarray
+    eigenvalues: np.ndarray
+    mean: np.ndarray
+    class_means: np.ndarray
+    classes: np.ndarray
+
+
 _TORCH_READY = False
 
 
@@ -403,6 +416,81 @@ class Engine:
         mean, var = np.empty(d), np.empty(d)
         self._chk(self._lib.ef_colstats(self._h, xp, xdt, n, d, 0, mean.ctypes.data, var.ctypes.data))
         return mean, var
+
+    # ------------------------------------------------------- Fisher discriminant
+    def _lda_input(self, F, labels, n_classes):
+        """(features, pointer, EF dtype, int32 labels, pointer, classes, C, on device): float32 /
+        float64 features (n, k) with one label per row.  With ``n_classes`` None the labels may
+        be any integers and are mapped to 0..C-1 by value (np.unique; ``classes`` holds the
+        values); else they are taken as they are, so that empty classes keep their rows."""
+        f, fp, fdt, dev = self._fit_input(F)
+        if fdt == N.EF_U8:
+            raise TypeError("features must be float32 or float64")
+        if f.ndim != 2 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError("features must be 2-D (n >= 1, k >= 1)")
+        n = int(f.shape[0])
+        if dev:
+            import torch
+            lab = labels if _is_dev(labels) else torch.as_tensor(np.asarray(labels), device=f.device)
+            if lab.ndim != 1 or lab.shape[0] != n:
+                raise ValueError(f"labels must be ({n},), got {tuple(lab.shape)}")
+            if n_classes is None:
+                classes, lab = torch.unique(lab, return_inverse=True)
+                n_classes = int(classes.shape[0])
+            else:
+                classes = torch.arange(int(n_classes), device=f.device)
+            lab = lab.to(torch.int32).contiguous()
+            return f, fp, fdt, lab, lab.data_ptr(), classes, int(n_classes), True
+        lab = np.asarray(labels)
+        if lab.ndim != 1 or lab.shape[0] != n:
+            raise ValueError(f"labels must be ({n},), got {lab.shape}")
+        if n_classes is None:
+            classes, lab = np.unique(lab, return_inverse=True)
+            n_classes = len(classes)
+        else:
+            classes = np.arange(int(n_classes))
+            # a value int32 cannot hold is out of range whatever n_classes is
+            lab = np.clip(lab, -1, np.iinfo(np.int32).max)
+        lab, lp = _host(lab.reshape(-1), np.int32)
+        return f, fp, fdt, lab, lp, classes, int(n_classes), False
+
+    def lda_scatter(self, F, labels, n_classes=None):
+        """Class statistics of labelled features (ef_lda_scatter), float64: a dict with
+        ``counts`` (C,) int64, ``mean`` (k,), ``class_means`` (C, k), ``Sw`` and ``Sb`` (k, k) and
+        ``classes`` (the label value of each class).  Labels are mapped to 0..C-1 by value
+        unless ``n_classes`` is given (then they must lie in [0, n_classes), and a class
+        without rows is empty).  Host arrays in -> NumPy out, device tensors in -> tensors out."""
+        f, fp, fdt, lab, lp, classes, C_, dev = self._lda_input(F, labels, n_classes)
+        n, k = (int(v) for v in f.shape)
+        device = f.device if dev else None
+        cnt, mean, cm = _empty(C_, np.int64, device), _empty(k, np.float64, device), _empty((C_, k), np.float64, device)
+        sw, sb = _empty((k, k), np.float64, device), _empty((k, k), np.float64, device)
+        with self._order(dev, f, lab, cnt, mean, cm, sw, sb):
+            self._chk(self._lib.ef_lda_scatter(self._h, fp, fdt, n, k, lp, C_, _ptr(cnt), _ptr(mean), _ptr(cm), _ptr(sw),
+                                               _ptr(sb), N.EF_MEM_DEVICE if dev else 0))
+        return {"counts": cnt, "mean": mean, "class_means": cm, "Sw": sw, "Sb": sb, "classes": classes}
+
+    def lda_fit(self, F, labels, n_components=None, shrinkage=0.0, n_classes=None) -> "LdaResult":
+        """The Fisher discriminant of labelled features (ef_lda_fit; conventions in
+        include/eigenface.h): ``scalings`` (k, m) with A^T (Sw_g / (n - C)) A = I, the
+        generalised ``eigenvalues`` (m,) descending, ``mean`` (k,), ``class_means`` (C, k) and
+        ``classes``.  ``n_components`` defaults to min(k, C - 1) over the non-empty classes.
+        Host arrays in -> NumPy out, device tensors in -> tensors out."""
+        f, fp, fdt, lab, lp, classes, C_, dev = self._lda_input(F, labels, n_classes)
+        n, k = (int(v) for v in f.shape)
+        if n_components is None:
+            present = int(lab.unique().numel()) if dev else len(np.unique(lab))
+            n_components = max(1, min(k, present - 1))
+        m = int(n_components)
+        if m < 1:
+            raise ValueError("n_components must be >= 1")
+        device = f.device if dev else None
+        A, ev = _empty((k, m), np.float64, device), _empty(m, np.float64, device)
+        mean, cm = _empty(k, np.float64, device), _empty((C_, k), np.float64, device)
+        with self._order(dev, f, lab, A, ev, mean, cm):
+            self._chk(self._lib.ef_lda_fit(self._h, fp, fdt, n, k, lp, C_, m, float(shrinkage), _ptr(A), _ptr(ev),
+                                           _ptr(mean), _ptr(cm), N.EF_MEM_DEVICE if dev else 0))
+        return LdaResult(A, ev, mean, cm, classes)
 
     # --------------------------------------------------------- sample-sharded fit
     def fit_shard_stats(self, X):

@@ -144,6 +144,19 @@ def summarize(genuine_key, impostor_key, metric="cosine", thresholds=REFERENCE_T
     return out
 
 
+def compare_subspaces(pca_features, fisher_features, labels, metric="l2", device=0, engine=None):
+    """The same labelled rows in two feature spaces, side by side: ``{"pca": summarize(...),
+    "fisher": summarize(...)}``, each from ``leave_one_out`` on its features.  What a
+    discriminant fit (``Fisherfaces``) buys on the user's own gallery."""
+    metric = _metric_name(metric)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    out = {}
+    for name, feats in (("pca", pca_features), ("fisher", fisher_features)):
+        loo = leave_one_out(feats, lab, metric, device, engine=engine)
+        out[name] = summarize(loo["genuine_key"], loo["impostor_key"], metric)
+    return out
+
+
 def evaluate_model(model_data, metric="cosine", device=0, keys=None):
     """Leave-one-out evaluation of a model dict holding ``face_features`` (n, k) and
     ``face_labels`` (n,) — the face_model.pkl layout (train-v4.py:210-222).  Returns

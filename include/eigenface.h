@@ -349,6 +349,57 @@ int ef_search_labelled(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric, i
                        const int64_t* exclude_rows /* [b] or NULL */,
                        int64_t* keys /* [b] or NULL */, ef_match* matches /* [b] or NULL */, uint32_t flags);
 
+/* ------------------------------------------------- Fisher discriminant (Fisherfaces)
+ * Added by symbol (EF_API_VERSION stays 7).  A linear discriminant inside face space
+ * (Belhumeur, Hespanha, Kriegman 1997): from features F[n][k] (EF_F32 / EF_F64; a fit's
+ * projection or a gallery) and one label in [0, n_classes) per row, the k x m matrix A whose
+ * columns maximise between-identity over within-identity scatter.  A folds into a projection
+ * matrix (W' = W . A, same mean), so every call that takes a model runs a Fisher model as is.
+ *
+ * ef_lda_order: the stable grouping of rows by label on the host (no context, no device):
+ *   order[n] lists the rows class by class, each class in input order (np.argsort(labels,
+ *   kind="stable")); offsets[n_classes + 1] are the class borders (offsets[c + 1] - offsets[c] =
+ *   rows of class c).  n = 0 is EF_OK.  EF_E_INVALID for a label outside [0, n_classes), with
+ *   nothing written.  It is the grouping the scatter runs on.
+ * ef_lda_scatter: all outputs float64, each optional (NULL):
+ *   counts[C]; mean[k] the mean m of all rows; class_means[C][k] (a zero row for an empty class);
+ *   Sb[k][k] = sum_c n_c (M_c - m)(M_c - m)^T;  Sw[k][k] = sum_c sum_{i in c} (f_i - M_c)(f_i - M_c)^T.
+ *   Any number of classes up to n, empty and one-row classes and unsorted labels included.  Every
+ *   sum is taken on rows centred first, in an order fixed by (n, k, labels): the same input
+ *   gives the same bytes.  Sw is formed directly from the rows centred on their class means.
+ *   Sums and products are carried as unevaluated pairs of doubles (compensated arithmetic), so
+ *   each output is the rounding of a result far more accurate than fp64: the discriminant's
+ *   error is the scatters' error times cond(Sw).  Sw and Sb are exactly symmetric.
+ *   1 <= k <= 1024.
+ *   A label outside [0, n_classes) is found on the device before any label is used as an index:
+ *   EF_E_INVALID, and the context stays usable.
+ * ef_lda_fit: the scatter, then on the device
+ *     Sw_g = (1 - g) Sw + g tr(Sw)/k I  (g = shrinkage in [0, 1]),  Sw_g = L L^T,
+ *     T = L^-1 Sb L^-T = V diag(lambda) V^T,  A = sqrt(n - C+) L^-T V  (leading m columns),
+ *   with C+ the number of non-empty classes.  Conventions:
+ *     - evals[m] are the generalised eigenvalues of (Sb, Sw_g), descending;
+ *     - A^T (Sw_g / (n - C+)) A = I, so L2 distance in the new space is the within-class
+ *       Mahalanobis distance, and A^T Sb A / (n - C+) = diag(evals);
+ *     - in each column the entry of largest magnitude is positive (first index on ties), the
+ *       rule of the eigenfaces;
+ *     - A is row-major [k][m];  1 <= m <= min(k, C+ - 1), else EF_E_INVALID;
+ *     - k > 256 is EF_E_INVALID (the Cholesky-inverse kernel's limit, see ef_chol_inv).
+ *   EF_E_NUMERIC when Sw_g is singular: n - C+ < k without shrinkage (rank Sw <= n - C+; too few
+ *   rows per identity for k, the classic small-sample case), or a pivot of the factorisation not
+ *   above 1e-12 of the largest diagonal entry; ef_last_error names n - C+, k and the shrinkage.
+ *   mean and class_means may be NULL.
+ * With EF_MEM_DEVICE every pointer is a device pointer and the work is ordered on the context's
+ * stream; both calls return after it has completed (the labels are grouped on the host: 4 bytes
+ * per row come down and 8 go up, these are fit-time calls). */
+int ef_lda_order(const int32_t* labels, int64_t n, int32_t n_classes, int64_t* order /* [n] */,
+                 int64_t* offsets /* [n_classes + 1] */);
+int ef_lda_scatter(ef_ctx* ctx, const void* F, int32_t f_dtype, int64_t n, int32_t k, const int32_t* labels,
+                   int32_t n_classes, int64_t* counts, double* mean, double* class_means, double* Sw, double* Sb,
+                   uint32_t flags);
+int ef_lda_fit(ef_ctx* ctx, const void* F, int32_t f_dtype, int64_t n, int32_t k, const int32_t* labels,
+               int32_t n_classes, int32_t m, double shrinkage, double* A /* [k][m] */, double* evals /* [m] */,
+               double* mean /* [k] or NULL */, double* class_means /* [C][k] or NULL */, uint32_t flags);
+
 /* ------------------------------------------------------------------ model bank
  * Added after API v7 without a version bump (purely additive): detect the entry points by
  * symbol (dlsym / hasattr), not by ef_api_version().
