@@ -238,6 +238,14 @@ static int search_copies(ef_ctx* c, int variant, int k1, bool split1, int64_t bp
   return EF_OK;
 }
 
+// max ||g||^2 as the search kernels take it: negated when the gallery has a row outside the scans'
+// error model for this metric (ef_search_common.hpp scan_regular), which sends every probe to the
+// fp64 sweeps; the magnitude is the tie window's scale either way
+static float scan_gmax2(const ef_ctx* c, int metric) {
+  const unsigned bad = kRowNotFinite | (metric == EF_METRIC_L2 ? 0u : kRowTiny);
+  return (c->gal_rows_host & bad) ? -c->gmax2_host : c->gmax2_host;
+}
+
 // Search the probes already in ctx->q_pad (at least round_up(b, 256) rows, kp = the gallery's)
 // of this rank's gallery: keys_dev[b] and, when match_dev is non-null, the fp64 match
 // records, piece by piece as search_schedule plans them.
@@ -281,12 +289,12 @@ static int search_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long*
       EF_HIP(c,
              launch_search_prefix(c->stream, g.kp, k1, sc.plans[i], sc.plans1[i], q, p.bpad, p.b, G, aux,
                                   static_cast<const float*>(c->der.G1.p), static_cast<const float*>(c->der.gnorm1.p),
-                                  split1, g.n, c->g_offset, c->gmax2_host, ws, pw, keys_dev + p.off, c),
+                                  split1, g.n, c->g_offset, scan_gmax2(c, metric), ws, pw, keys_dev + p.off, c),
              "prefix search");
     else
       EF_HIP(c,
              launch_search(c->stream, g.kp, metric, sp, sc.plans[i], q, p.bpad, p.b, G, aux, g.n, c->g_offset,
-                           c->gmax2_host, ws, keys_dev + p.off, c),
+                           scan_gmax2(c, metric), ws, keys_dev + p.off, c),
              "search");
   }
   if (k1 > 0) {
@@ -542,8 +550,9 @@ int weights_load(ef_ctx* c, DevBuf& mean_dst, DevBuf& W_dst, const float* mean, 
 }
 
 int gallery_load(ef_ctx* c, Gallery& g, const float* G, int64_t n, int k, uint32_t flags, DevBuf& staging,
-                 float* gmax2_host) {
+                 float* gmax2_host, unsigned* rows_host) {
   const int kp = feature_pad(k);
+  if (rows_host) *rows_host = 0;
   g.n = 0;  // empty until the last step has succeeded
   if (n > 0) {
     EF_TRY(ensure(c, g.gnorm2, (size_t)n * sizeof(float)));
@@ -560,6 +569,11 @@ int gallery_load(ef_ctx* c, Gallery& g, const float* G, int64_t n, int k, uint32
            "gallery norms");
     if (gmax2_host) {
       EF_HIP(c, hipMemcpyAsync(gmax2_host, g.gmax2.p, sizeof(float), hipMemcpyDeviceToHost, c->stream), "D2H gmax2");
+      if (rows_host)
+        EF_HIP(c,
+               hipMemcpyAsync(rows_host, static_cast<const unsigned*>(g.gmax2.p) + 1, sizeof(unsigned),
+                              hipMemcpyDeviceToHost, c->stream),
+               "D2H gallery row bits");
       EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
     }
   }
@@ -895,7 +909,7 @@ int ef_gallery_set(ef_ctx* c, const float* G, int64_t n, int32_t k, int64_t offs
   c->has_labels = false;  // and so do the row labels (ef_gallery_labels)
   release(c->glabels);
   DevBuf staging;
-  EF_TRY(gallery_load(c, c->gal, G, n, k, flags, staging, &c->gmax2_host));
+  EF_TRY(gallery_load(c, c->gal, G, n, k, flags, staging, &c->gmax2_host, &c->gal_rows_host));
   c->g_offset = offset;
   return EF_OK;
 }
@@ -955,7 +969,7 @@ static int search_labelled_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, i
     EF_HIP(c,
            launch_search(c->stream, g.kp, metric, SplitScan{}, sc.plans[i],
                          static_cast<const float*>(c->q_pad.p) + p.off * g.kp, p.bpad, p.b, G, aux, g.n, c->g_offset,
-                         c->gmax2_host, ws, keys_dev + p.off, c),
+                         scan_gmax2(c, metric), ws, keys_dev + p.off, c),
            "labelled search");
   }
   return EF_OK;
@@ -1040,7 +1054,7 @@ static int search_topk_run(ef_ctx* c, int64_t bpad, int64_t b, int m, int metric
     EF_HIP(c,
            launch_search_topk(c->stream, g.kp, metric, sp, m, sc.plans[i],
                               static_cast<const float*>(c->q_pad.p) + p.off * g.kp, p.bpad, p.b,
-                              static_cast<const float*>(g.G.p), aux, g.n, c->g_offset, c->gmax2_host, ws, tw, cap,
+                              static_cast<const float*>(g.G.p), aux, g.n, c->g_offset, scan_gmax2(c, metric), ws, tw, cap,
                               counters, keys_dev + p.off * m, match_dev ? match_dev + p.off * m : nullptr),
            "top-m search");
   }

@@ -43,6 +43,9 @@ constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
 constexpr int kTimers = 12;             // EF_KERNEL_* ids (include/eigenface.h)
 constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
+// What gallery_aux_kernel reports of a gallery's rows (ef_search_common.hpp scan_regular)
+constexpr unsigned kRowNotFinite = 1;   // a row whose fp32 ||g||^2 is +inf or NaN
+constexpr unsigned kRowTiny = 2;        // a row, not all zeros, whose fp32 ||g||^2 is below 2^-80
 
 // Workspace of one search call (device pointers).
 struct SearchWs {
@@ -319,7 +322,7 @@ struct Gallery {
   DevBuf G;       // float[n][kp]
   DevBuf gnorm2;  // float[n]  ||g||^2
   DevBuf ginv;    // float[n]  1/||g|| (0 for a zero row)
-  DevBuf gmax2;   // uint (float bits) max ||g||^2
+  DevBuf gmax2;   // uint[2]: (float bits) max ||g||^2 over the rows whose norm is finite, the kRow* bits
 };
 // What the context derives from its gallery on the first search that needs it, and the prefix
 // guard's history, which belongs to the gallery and settings it was seen on.  reset() forgets
@@ -464,6 +467,7 @@ struct ef_ctx {
   ef::Gallery gal;       // gal.k == 0: none set yet
   int64_t g_offset = 0;  // global index of row 0
   float gmax2_host = 0.f;
+  unsigned gal_rows_host = 0;  // the gallery's kRow* bits (scan_gmax2, ef_api.hip)
   // one label per gallery row (ef_gallery_labels); ef_gallery_set drops them
   bool has_labels = false;
   ef::DevBuf glabels;   // int32[gal.n]
@@ -715,12 +719,12 @@ int stage_probes(ef_ctx* c, const void* P, int dtype, int64_t b, int64_t d, uint
 // weights_load: mean[d] and W[d][k] into mean_dst and W_dst[d][kpw]; queued, not synchronised.
 // gallery_load: G[n][k] into g's buffers, grown in place (never a second copy of the rows), with
 // the norms; g is empty (n == 0) until the last step has succeeded.  gmax2_host non-null (the
-// context): the load is synchronised and max ||g||^2 is on the host on return; null (a bank
-// slot): everything stays queued and max ||g||^2 stays on the device.
+// context): the load is synchronised and max ||g||^2 is on the host on return, with the kRow* bits
+// in *rows_host; null (a bank slot): everything stays queued and both stay on the device.
 int weights_load(ef_ctx* c, DevBuf& mean_dst, DevBuf& W_dst, const float* mean, const float* W, int64_t d, int k,
                  int kpw, uint32_t flags, DevBuf& staging);
 int gallery_load(ef_ctx* c, Gallery& g, const float* G, int64_t n, int k, uint32_t flags, DevBuf& staging,
-                 float* gmax2_host);
+                 float* gmax2_host, unsigned* rows_host = nullptr);
 hipError_t launch_pad_rows(hipStream_t s, const float* src, int64_t rows, int k, int64_t rows_pad,
                            float* dst, int kp);
 hipError_t launch_gallery_aux(hipStream_t s, const float* G, int64_t n, int kp, float* gnorm2,

@@ -24,7 +24,10 @@
 //   * each workgroup writes its per-probe (best key, runner-up score) for its chunk.
 // Pass 2 — reduce_kernel: per probe, min over chunks -> winner + global runner-up; the
 //   winner is re-scored in fp64 (difference form for L2).  A rigorous fp32 error bound
-//   decides whether the runner-up could beat the winner; if so the probe is queued.
+//   decides whether the runner-up could beat the winner; if so the probe is queued.  Outside
+//   the bound's domain (scan_regular, ef_search_common.hpp: fp32 squares near overflow or
+//   underflow, non-finite rows) the probe is queued for a sweep of every row instead, and a
+//   probe with a NaN or an infinite component gets no key.
 // Pass 3 (only for queued probes; a no-op launch otherwise) — the search kernel in
 //   COLLECT mode gathers every row whose fp32 score is within the bound, and
 //   resolve_kernel re-scores them in fp64 and keeps the lowest index among exact ties.
@@ -827,11 +830,45 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ q
     const long long o = __shfl_xor(kmin, off);
     kmin = o < kmin ? o : kmin;
   }
-  if (kmin == LLONG_MAX) {  // empty gallery
+  const float* q = qpad + p * kpv;
+  // fp32 ||q||^2 for the bound, fp64 for the tie window's scale (resolve_kernel sums it alike)
+  float qq = 0.f;
+  for (int c = lane; c < kpv; c += 64) qq = __builtin_fmaf(q[c], q[c], qq);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) qq += __shfl_xor(qq, off);
+  double qq64 = 0.0;
+  for (int c = lane; c < kpv; c += 64) qq64 = fma((double)q[c], (double)q[c], qq64);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) qq64 += __shfl_xor(qq64, off);
+  const bool regular = scan_regular<METRIC>(qq, gmax2);  // ef_search_common.hpp
+  auto no_key = [&] {  // lane 0
+    keys[p] = LLONG_MAX;
+    if (ws.match) ws.match[p] = ef_match{__builtin_inf(), 0.0, LLONG_MAX};
+  };
+  // lane 0: queue the probe for resolve_kernel's fp64 sweep of every row (a count past kCandMax);
+  // the NaN threshold keeps the COLLECT pass from counting anything for it
+  auto queue_sweep = [&] {
+    const int slot = atomicAdd(ws.amb_count, 1);
+    ws.amb_list[slot] = (int)p;
+    ws.thr[slot] = __builtin_nanf("");
+    ws.cand_cnt[slot] = kCandMax + 1;
+  };
+  // a probe with a NaN or an infinite component (the fp64 sum of finite fp32 squares is finite)
+  if (!(qq64 < __builtin_inf())) {
+    if (lane == 0) no_key();
+    return;
+  }
+  // outside the bound's domain the scan's scores may be NaN or +-inf: neither its winner nor "no
+  // row scored" is believed, and the sweep decides, starting from "no key"
+  if (!regular) {
     if (lane == 0) {
-      keys[p] = LLONG_MAX;
-      if (ws.match) ws.match[p] = ef_match{__builtin_inf(), 0.0, LLONG_MAX};
+      no_key();
+      queue_sweep();
     }
+    return;
+  }
+  if (kmin == LLONG_MAX) {  // no row scored: an empty gallery, no qualifying row
+    if (lane == 0) no_key();
     return;
   }
   float r2 = __builtin_inff();
@@ -845,30 +882,24 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ q
 
   const float b1 = key_value(kmin);
   const unsigned row = (unsigned)(kmin & 0xffffffffll);
-  const float* q = qpad + p * kpv;
   const double v = score64<KP, METRIC>(q, G + (int64_t)row * kpv, lane, kpv);
   // rigorous bound on |fp32 score - exact score|, doubled for the two compared scores
-  float qq = 0.f;
-  for (int c = lane; c < kpv; c += 64) qq = __builtin_fmaf(q[c], q[c], qq);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) qq += __shfl_xor(qq, off);
   const float delta = scan_delta<METRIC, S3>(kpv, sqrtf(qq), gmax2, b1);  // ef_search_common.hpp
-  double qq64 = 0.0;  // tie-tolerance scale of the fp64 resolution (resolve_kernel)
-  if (METRIC == EF_METRIC_L2 && ws.match) {
-    for (int c = lane; c < kpv; c += 64) qq64 = fma((double)q[c], (double)q[c], qq64);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) qq64 += __shfl_xor(qq64, off);
-  }
   if (lane == 0) {
     keys[p] = pack_key((float)v, (unsigned)(row + g_offset));
     if (ws.match)
       ws.match[p] = ef_match{v, METRIC == EF_METRIC_L2 ? qq64 + (double)gmax2 : 1.0,
                              pack_key((float)v, (unsigned)(row + g_offset))};
-    if (r2 - b1 <= delta) {
-      const int slot = atomicAdd(ws.amb_count, 1);
-      ws.amb_list[slot] = (int)p;
-      ws.thr[slot] = b1 + delta;
-      ws.cand_cnt[slot] = 0;
+    // queued unless proven: a NaN on either side of the comparison leaves the probe unproven
+    if (!(r2 - b1 > delta)) {
+      if (fabsf(b1) + delta < __builtin_inff()) {
+        const int slot = atomicAdd(ws.amb_count, 1);
+        ws.amb_list[slot] = (int)p;
+        ws.thr[slot] = b1 + delta;
+        ws.cand_cnt[slot] = 0;
+      } else {  // a threshold that is not finite cannot select candidates
+        queue_sweep();
+      }
     }
   }
 }
@@ -903,11 +934,13 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
   for (int c = lane; c < kpv; c += 64) qq = fma((double)q[c], (double)q[c], qq);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) qq += __shfl_xor(qq, off);
-  const double scale = METRIC == EF_METRIC_L2 ? qq + (double)gmax2 : 1.0;
+  const double scale = METRIC == EF_METRIC_L2 ? qq + (double)fabsf(gmax2) : 1.0;  // negated: scan_regular
   const double tol = 1e-12 * (fabs(vmin) + scale);
   int64_t best_row = LLONG_MAX;
   double best_v = vmin;
-  for (int64_t j = 0; j < m; ++j) {
+  // a row with a NaN or an infinite component scores NaN or +inf against a finite probe; it is
+  // never below vmin, and vmin < inf keeps it out when every row is such a row
+  for (int64_t j = 0; j < m && vmin < INFINITY; ++j) {
     const int64_t r = row_of(j);
     if constexpr (LBL) {
       if (!label_row_ok(ws, p, r)) continue;
@@ -918,10 +951,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const float* __restrict__ 
   if (lane == 0 && best_row != LLONG_MAX) {
     const long long key = pack_key((float)best_v, (unsigned)(best_row + g_offset));
     keys[p] = key;
-    if (ws.match) {
-      ws.match[p].score = best_v;
-      ws.match[p].key = key;
-    }
+    if (ws.match) ws.match[p] = ef_match{best_v, scale, key};  // the scale as reduce_kernel forms it
   }
 }
 
@@ -1009,8 +1039,10 @@ __global__ __launch_bounds__(256) void reduce_prefix_kernel(const float* __restr
   const float delta1 = (S3 ? 2.f : 1.f) * scan_delta<EF_METRIC_L2, S3>(K1, sqrtf((float)qq64), gmax2, b1);
   const double scale = qq64 + (double)gmax2;
   const double tol = 1e-12 * (fabs(dw) + scale);
+  // outside the bound's domain (scan_regular: a negated gmax2 among them) nothing is proven here
+  const bool regular = scan_regular<EF_METRIC_L2>((float)qq64, gmax2);
   if (lane == 0) {
-    if (q1 + (double)r2 - (double)delta1 > dw + tol) {
+    if (regular && q1 + (double)r2 - (double)delta1 > dw + tol) {
       const long long key = pack_key((float)dw, (unsigned)(row + g_offset));
       keys[p] = key;
       if (ws.match) ws.match[p] = ef_match{dw, scale, key};
@@ -1068,21 +1100,32 @@ __global__ void pad_rows_kernel(const float* __restrict__ src, int64_t rows, int
 
 // ||g||^2 and 1/||g|| per gallery row (K7: computed once at enrolment, not per probe as
 // sklearn's cosine_similarity does, pairwise.py:1734), and max ||g||^2 for the bound.
+// irregular (null: not wanted): bits set when a row is outside the scans' error model
+// (scan_regular, ef_search_common.hpp): kRowNotFinite for a row whose fp32 ||g||^2 is +inf or
+// NaN (a non-finite component, or finite components whose squares overflow), kRowTiny for a row
+// that is not all zeros with ||g||^2 below kScanNormFloor, whose 1/||g|| is inexact or 0.
 __global__ void gallery_aux_kernel(const float* __restrict__ G, int64_t n, int kp, float* __restrict__ gnorm2,
-                                   float* __restrict__ ginv) {
+                                   float* __restrict__ ginv, unsigned* __restrict__ irregular) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= n) return;
   float s = 0.f;
+  bool nz = false;
   for (int c = lane; c < kp; c += 64) {
     const float v = G[row * kp + c];
     s = __builtin_fmaf(v, v, s);
+    nz = nz || v != 0.f;  // true for a NaN too
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  nz = __any(nz);
   if (lane == 0) {
     gnorm2[row] = s;
     ginv[row] = s > 0.f ? 1.0f / sqrtf(s) : 0.f;
+    if (irregular) {
+      if (!(s < __builtin_inff())) atomicOr(irregular, kRowNotFinite);
+      else if (nz && s < kScanNormFloor) atomicOr(irregular, kRowTiny);
+    }
   }
 }
 
@@ -1126,7 +1169,12 @@ __global__ void hi_rows_kernel(const float* __restrict__ G, int64_t blocks, uint
 __global__ __launch_bounds__(256) void max_kernel(const float* __restrict__ x, int64_t n, unsigned* __restrict__ out) {
   __shared__ float red[4];
   float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, x[i]);
+  // the finite values only: a row whose fp32 ||g||^2 is +inf or NaN is flagged by
+  // gallery_aux_kernel, and the tie window's scale is taken over the other rows
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float v = x[i];
+    m = fmaxf(m, v < __builtin_inff() ? v : 0.f);
+  }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
@@ -1406,7 +1454,7 @@ hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int k
   hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((n * (k1 / 4) + 255) / 256)), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(G), n, kp / 4, k1 / 4, reinterpret_cast<float4*>(G1));
   // the norms as gallery_aux_kernel computes gnorm2 (its 1/||g|| output goes to the spare half)
-  hipLaunchKernelGGL(gallery_aux_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, G1, n, k1, gnorm1, gnorm1 + n);
+  hipLaunchKernelGGL(gallery_aux_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, G1, n, k1, gnorm1, gnorm1 + n, nullptr);
   // the split scan reads (hi, lo) rows: split the copy in place, after its fp32 norms are taken
   if (split) return launch_split_rows(s, G1, n, k1, G1);
   return hipGetLastError();
@@ -1469,9 +1517,11 @@ hipError_t launch_hi_rows(hipStream_t s, const float* G, int64_t n, int kp, void
 
 hipError_t launch_gallery_aux(hipStream_t s, const float* G, int64_t n, int kp, float* gnorm2, float* ginv,
                               unsigned* gmax2_bits) {
-  hipError_t e = hipMemsetAsync(gmax2_bits, 0, sizeof(unsigned), s);
+  // gmax2_bits[0] max ||g||^2 over the rows whose norm is finite, [1] the kRow* bits
+  hipError_t e = hipMemsetAsync(gmax2_bits, 0, 2 * sizeof(unsigned), s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(gallery_aux_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, G, n, kp, gnorm2, ginv);
+  hipLaunchKernelGGL(gallery_aux_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, G, n, kp, gnorm2, ginv,
+                     gmax2_bits + 1);
   hipLaunchKernelGGL(max_kernel, dim3(256), dim3(256), 0, s, gnorm2, n, gmax2_bits);
   return hipGetLastError();
 }

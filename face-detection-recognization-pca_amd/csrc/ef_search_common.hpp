@@ -182,6 +182,32 @@ __device__ __forceinline__ float scan_delta(int kpv, float qn, float gmax2, floa
   return delta * 2.f;  // safety factor
 }
 
+// Where scan_delta's error model holds.  The bound counts roundings relative to the values
+// (u per operation), so it needs every partial sum of a chain below fp32's overflow and the
+// absolute error of underflow (at most 2^-126 per operand or operation, whether the unit
+// flushes subnormals or rounds them gradually) far below delta.
+//   above: every element product, norm and partial sum of a chain is at most
+//     mag = gmax2 + 2.02 ||q|| gm in magnitude (1 % more for the split chains' hi parts);
+//     mag <= 2^126 keeps them finite.  An overflowed fp32 ||q||^2 makes mag +inf.
+//   below: L2's delta is at least 4 (k + 4) u gmax2 and (4 k + 8) underflows cost at most
+//     (4 k + 8) 2^-126, which is below 2^-20 of it for gmax2 >= 2^-80; a flushed operand
+//     costs 2^-126 times the other one, covered alike since gm >= 2^-40.  Cosine's delta is
+//     proportional to ||q|| and its score carries 1/||g|| <= 2^40, so ||q||^2 >= 2^-80 as well.
+// gmax2 arrives NEGATED (scan_gmax2, ef_api.hip) when a gallery row is outside the model:
+// a row whose fp32 ||g||^2 is not finite, or for cosine a non-zero row whose ||g||^2 is below
+// 2^-80 (its 1/||g|| is inexact or 0).  |gmax2| is then the maximum over the other rows.  A
+// NaN anywhere makes the answer false.  A probe that is not regular is never decided from scan
+// scores: every row is re-scored in fp64 (resolve_kernel's sweep, topk_sweep_kernel).
+constexpr float kScanNormFloor = 8.2718061e-25f;  // 2^-80
+constexpr float kScanMagMax = 8.5070592e+37f;     // 2^126
+template <int METRIC>
+__device__ __forceinline__ bool scan_regular(float qq, float gmax2) {
+  const float mag = gmax2 + 2.02f * sqrtf(qq) * sqrtf(gmax2);  // NaN for a negated gmax2
+  bool ok = gmax2 >= kScanNormFloor && mag <= kScanMagMax;
+  if constexpr (METRIC != EF_METRIC_L2) ok = ok && qq >= kScanNormFloor;
+  return ok;
+}
+
 // ---- work items -----------------------------------------------------------------------
 // Tiles [t0, t1) of gallery chunk gc (ROWS rows per tile); t0 >= t1 for an empty chunk.
 template <int ROWS>
@@ -256,7 +282,8 @@ __device__ __forceinline__ unsigned wide_tail_clamp(unsigned go, int nrem, int r
 
 
 // fp64 score of gallery row `row` for probe q (L2: squared distance in difference form;
-// cosine: -q.g/(|q||g|), 0 for a zero vector — sklearn normalize semantics).
+// cosine: -q.g/(|q||g|), 0 for a zero vector — sklearn normalize semantics; NaN when a norm is
+// NaN or infinite, +inf or NaN for L2 with such a component: the sweeps pass such rows over).
 // KP = 0: the row length is kp_rt (k > 512, any multiple of 128).
 template <int KP, int METRIC>
 __device__ __forceinline__ double score64(const float* __restrict__ q, const float* __restrict__ g, int lane,
@@ -290,7 +317,10 @@ __device__ __forceinline__ double score64(const float* __restrict__ q, const flo
   if constexpr (METRIC == EF_METRIC_L2) {
     return s0;
   } else {
-    return (s1 > 0.0 && s2 > 0.0) ? -(s0 / (sqrt(s1) * sqrt(s2))) : 0.0;
+    if (s1 > 0.0 && s2 > 0.0) return -(s0 / (sqrt(s1) * sqrt(s2)));  // NaN for an infinite norm
+    // 0 is for a true zero vector alone: a NaN norm (a NaN component) scores NaN, so that the
+    // sweeps pass the row over instead of ranking it at cosine 0
+    return (s1 != s1 || s2 != s2) ? __builtin_nan("") : 0.0;
   }
 }
 

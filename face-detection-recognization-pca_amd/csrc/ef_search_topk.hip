@@ -105,12 +105,19 @@ __global__ __launch_bounds__(256) void topk_threshold_kernel(const float* __rest
     pv = bv;
     pi = bi;
   }
-  const float qn = sqrtf(probe_norm2_f32(qpad + p * kpv, kpv, lane));
-  const float cut = topk_cut<METRIC>(tau, s3, kpv, qn, gmax2);
+  const float qq = probe_norm2_f32(qpad + p * kpv, kpv, lane);
+  const double qq64 = probe_norm2_f64(qpad + p * kpv, kpv, lane);
+  const float cut = topk_cut<METRIC>(tau, s3, kpv, sqrtf(qq), gmax2);
+  // A probe outside the bound's domain (scan_regular, ef_search_common.hpp) takes nothing from
+  // the scan: its list starts past the cap and the NaN cut collects nothing, so both rounds pass
+  // it on and topk_sweep_kernel re-scores every row.  A probe with a NaN or an infinite component
+  // (fp64 ||q||^2 not finite) collects nothing into an empty list: m empty slots.
+  const bool finite = qq64 < __builtin_inf();
+  const bool regular = scan_regular<METRIC>(qq, gmax2);
   if (lane == 0) {
-    ws.thr[p] = cut;
+    ws.thr[p] = finite && regular ? cut : __builtin_nanf("");
     ws.amb_list[p] = (int)p;
-    ws.cand_cnt[p] = 0;
+    ws.cand_cnt[p] = finite && !regular ? ws.cand_cap + 1 : 0;
     if (p == 0) *ws.amb_count = (int)b;
   }
 }
@@ -185,7 +192,9 @@ __global__ __launch_bounds__(256) void topk_resolve_kernel(
   const float* q = qpad + p * kpv;
   const int cnt = cnt_of[slot];
   const bool overflow = cnt > cap;
-  const int nc = overflow ? cap : cnt;
+  const float qq32 = probe_norm2_f32(q, kpv, lane);
+  const bool regular = scan_regular<METRIC>(qq32, gmax2);
+  const int nc = overflow ? (regular ? cap : 0) : cnt;  // not regular: nothing was collected
   int P = 64;
   while (P < nc) P <<= 1;
   for (int j = wave; j < P; j += 4) {
@@ -203,21 +212,22 @@ __global__ __launch_bounds__(256) void topk_resolve_kernel(
   __syncthreads();
   bitonic_sort_pairs(sv, sr, P);
   if (overflow) {
-    const float qn = sqrtf(probe_norm2_f32(q, kpv, lane));
+    const float qn = sqrtf(qq32);
     if (threadIdx.x == 0) {
       const double t2 = sv[m - 1];  // cap >= m rows were scored
       const float tau = __double2float_ru(METRIC == EF_METRIC_L2 ? t2 - qq64 : t2 * sqrt(qq64));
       const int at = atomicAdd(nx.count, 1);
       nx.list[at] = (int)p;
-      if (nx.thr) nx.thr[at] = topk_cut<METRIC>(tau, s3, kpv, qn, gmax2);
-      if (nx.cnt) nx.cnt[at] = 0;
+      // not regular: past the cap again with a NaN cut, on to the sweep (topk_threshold_kernel)
+      if (nx.thr) nx.thr[at] = regular ? topk_cut<METRIC>(tau, s3, kpv, qn, gmax2) : __builtin_nanf("");
+      if (nx.cnt) nx.cnt[at] = regular ? 0 : cap + 1;
       if (first_round) atomicAdd(&counters[1], 1ull);
       atomicAdd(&counters[3], (unsigned long long)nc);
     }
     return;
   }
   const double vmin = sv[0];
-  const double scale = METRIC == EF_METRIC_L2 ? qq64 + (double)gmax2 : 1.0;
+  const double scale = METRIC == EF_METRIC_L2 ? qq64 + (double)fabsf(gmax2) : 1.0;  // negated: scan_regular
   const double tol = 1e-12 * (fabs(vmin) + scale);
   for (int i = threadIdx.x; i < nc; i += blockDim.x)
     if (sv[i] <= vmin + tol) atomicMin(&s_r0, sr[i]);
@@ -246,23 +256,24 @@ __global__ __launch_bounds__(256) void topk_sweep_kernel(const float* __restrict
   __shared__ int sr[256];
   __shared__ double w_v[4];
   __shared__ int w_r[4];
-  __shared__ int s_z;
+  __shared__ int s_z, s_nv;
   const int slot = blockIdx.x;
   if (slot >= *count) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t p = list[slot];
   const float* q = qpad + p * kpv;
+  // a row with a NaN or an infinite component scores NaN or +inf: it is passed over
   double vm = INFINITY;
   for (int64_t row = wave; row < n; row += 4) {
     const double v = score64<0, METRIC>(q, G + row * kpv, lane, kpv);
     vm = v < vm ? v : vm;
   }
   if (lane == 0) w_v[wave] = vm;
-  if (threadIdx.x == 0) s_z = INT_MAX;
+  if (threadIdx.x == 0) { s_z = INT_MAX; s_nv = 0; }
   const double qq64 = probe_norm2_f64(q, kpv, lane);
   __syncthreads();
   const double vmin = fmin(fmin(w_v[0], w_v[1]), fmin(w_v[2], w_v[3]));
-  const double scale = METRIC == EF_METRIC_L2 ? qq64 + (double)gmax2 : 1.0;
+  const double scale = METRIC == EF_METRIC_L2 ? qq64 + (double)fabsf(gmax2) : 1.0;  // negated: scan_regular
   const double tol = 1e-12 * (fabs(vmin) + scale);
   __syncthreads();  // w_v is rewritten below
   double ev = INFINITY, v0 = INFINITY;  // this lane's entry of the wave's sorted list
@@ -270,11 +281,12 @@ __global__ __launch_bounds__(256) void topk_sweep_kernel(const float* __restrict
   for (int64_t row = wave; row < n; row += 4) {
     const double v = __shfl(score64<0, METRIC>(q, G + row * kpv, lane, kpv), 0);
     const int r = (int)row;
-    if (v <= vmin + tol && r < r0) { r0 = r; v0 = v; }
+    const bool have = v < INFINITY;  // wave-uniform
+    if (have && v <= vmin + tol && r < r0) { r0 = r; v0 = v; }
     // insert (v, r): entries below it stay, the first one not below takes it, the rest shift
     const double uv = __shfl_up(ev, 1);
     const int ur = __shfl_up(er, 1);
-    if (!pair_less(ev, er, v, r)) {
+    if (have && !pair_less(ev, er, v, r)) {
       const bool first = lane == 0 || pair_less(uv, ur, v, r);
       ev = first ? v : uv;
       er = first ? r : ur;
@@ -290,8 +302,9 @@ __global__ __launch_bounds__(256) void topk_sweep_kernel(const float* __restrict
   for (int w = 0; w < 4; ++w)
     if (w_r[w] < r0) { r0 = w_r[w]; v0 = w_v[w]; }
   if (sr[threadIdx.x] == r0) s_z = threadIdx.x;
+  if (sr[threadIdx.x] != INT_MAX) atomicAdd(&s_nv, 1);  // the list's entries, sorted ahead of the empty ones
   __syncthreads();
-  const int nvalid = (int)(n < 256 ? n : 256);
+  const int nvalid = s_nv;
   topk_emit(sv, sr, r0 == INT_MAX ? 0 : nvalid, v0, r0, s_z, m, scale, g_offset, keys, match, p);
   if (threadIdx.x == 0) {
     atomicAdd(&counters[2], 1ull);

@@ -223,7 +223,24 @@ int ef_gallery_set(ef_ctx* ctx, const float* G, int64_t n, int32_t k, int64_t gl
 /* Q[b*k] float32 probe features -> keys[b].  A key packs the exact fp32 score
  * of the winning row in its high 32 bits (order-preserving) and the global
  * row index in its low 32 bits, so min over keys == argbest with lowest-index
- * tie-break; an all-reduce(MIN) over ranks combines sharded galleries. */
+ * tie-break; an all-reduce(MIN) over ranks combines sharded galleries.
+ *
+ * Input domain of the arg-best guarantee (ef_search, ef_search_matches, ef_search_topk*,
+ * ef_search_labelled*, ef_recognize* on the context's gallery; not the model bank, whose slots
+ * keep the domain "fp32 squares neither overflow nor underflow"): ANY finite fp32 values.  The
+ * returned row is the lowest index among the rows whose fp64 score is within
+ * 1e-12 * (|min| + scale) of the fp64 minimum, whatever the features' scale, offset or spread
+ * of norms.  The fp32 / bf16 scan decides a probe only where its error bound holds: fp32
+ * max |g|^2 in [2^-80, 2^126] together with 2.02 |q| max|g|, for cosine also |q|^2 >= 2^-80
+ * and no non-zero row with |g|^2 < 2^-80.  Outside it the probe is re-scored against every
+ * row in fp64: exact, at the cost of b * n fp64 row products.  scale takes max |g|^2 over the
+ * rows whose fp32 |g|^2 is finite, so where squares overflow the window is narrower than
+ * stated, never wider.
+ * NaN and +-inf: a gallery row with such a component is never returned (unless the probe has
+ * none to prefer: then EF_KEY_NONE), does not enter scale, and sends every probe of that
+ * gallery to the fp64 re-scoring; the other rows rank as if it were absent.  A probe with such
+ * a component gets EF_KEY_NONE (all m slots of a top-m search; the record {+inf, 0,
+ * EF_KEY_NONE}) on every call and route, and does not affect the other probes of its batch. */
 int ef_search(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric, int64_t* keys, uint32_t flags);
 /* Fused pipeline: project P then search; feats (b*k float32) optional. */
 int ef_recognize(ef_ctx* ctx, const void* P, int32_t p_dtype, int64_t b, int32_t metric,
