@@ -82,7 +82,7 @@ struct SearchPlan {
 // full-k scan (the device count of the second run), amb_count[2] = their total over the
 // search's pieces.
 struct PrefixWs {
-  float* q1;         // [bpad][K1] the probes' first K1 components
+  float* q1;         // [bpad][K1] the probes' first K1 components (the search_kernel forms; prefix64_kernel reads qpad)
   float* qpad2;      // [bpad][KP] the unproven probes' rows, in list order
   int* list;         // [bpad] probe of each unproven slot
   long long* keys2;  // [bpad] keys of the second run, by slot
@@ -564,7 +564,9 @@ void timer_arm(ef_ctx* c, int kernel, TimerEvt* t);
 void timer_commit(ef_ctx* c, TimerEvt* t);
 
 // ---- launchers (defined in the .hip files) -------------------------------------------
-// tile_rows: gallery rows per tile when not the kernel family's own (the prefix scan)
+// tile_rows: gallery rows per tile when not the kernel family's own (the prefix scan); the
+// 256-row plans are the split-bf16 prefix scan's at k1 <= 32, whose workgroups take 512 probes:
+// n_ptiles counts those, rounding up (bpad is a multiple of 256)
 // min_chunks (the top-m search): at least round_up(min_chunks, 8) gallery chunks
 SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows = 0, int min_chunks = 0);
 // rows per tile of the prefix scan at prefix length k1 (split: the split-bf16 scan)

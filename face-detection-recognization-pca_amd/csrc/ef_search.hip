@@ -45,9 +45,10 @@
 // records equal the fp32 path's bit for bit whenever both resolve
 // (tests/test_gpu_search_split.py; at the full C3 size, tests/test_gpu_c3_full.py).
 //
-// Prefix scan (EF_OPT_SEARCH_PREFIX; L2, EF_OPT_SEARCH_SPLIT_BF16 = 0): search_kernel<K1> over
-// a compact copy of the rows' first K1 components, in split-bf16 arithmetic by default
-// (EF_OPT_SEARCH_PREFIX_SPLIT) or in fp32, gives a lower bound of every distance;
+// Prefix scan (EF_OPT_SEARCH_PREFIX; L2, EF_OPT_SEARCH_SPLIT_BF16 = 0): a scan over a compact
+// copy of the rows' first K1 components, in split-bf16 arithmetic by default
+// (EF_OPT_SEARCH_PREFIX_SPLIT; prefix64_kernel at K1 <= 32, search_kernel<K1, .., S3> at 64) or
+// in fp32 (search_kernel<K1>), gives a lower bound of every distance;
 // reduce_prefix_kernel proves the winner from it where it can, and only the unproven probes
 // go through passes 1-3 at full k (launch_search_prefix).
 //
@@ -64,6 +65,9 @@ constexpr int TG = 64;  // gallery rows per LDS tile (two 32-row MFMA blocks)
 // rows per tile of the prefix scans at K1 <= 32: fp32, and split bf16 (profiles/r11: 256 rows
 // measured 0.847 ms per C3 step against 0.872 at 128 and 0.909 at 64)
 constexpr int kPrefixTile = 128, kPrefixSplitTile = 256;
+// probes per workgroup of the split-bf16 prefix scan at K1 <= 32 (prefix64_kernel: 8 waves x 64
+// probes); search_plan takes it for the plans of kPrefixSplitTile rows
+constexpr int kPrefixSplitProbes = 512;
 
 // round-to-nearest-even fp32 -> bf16 bits (finite inputs) and back
 __device__ __forceinline__ unsigned bf16_bits(float x) {
@@ -88,10 +92,9 @@ __device__ __forceinline__ void split8(const float* x, bf16x8& hi, bf16x8& lo) {
 // CNT (main pass of the prefix path's second run, launch_search_prefix): the probe count is
 // on the device (ws.amb_count[1]); workgroups whose probe tile starts at or past it return.
 // TGT: gallery rows per LDS tile, TGT / 32 independent accumulator chains per wave.  64
-// everywhere but the prefix scan at K1 <= 32, whose tiles hold so few MFMAs that the
+// everywhere but the fp32 prefix scan at K1 <= 32, whose tiles hold so few MFMAs that the
 // per-tile costs (barrier, DMA issue and wait, first LDS reads) show; 128 rows halve them.
-// The split-bf16 prefix scan (S3) has a quarter of the fp32 scan's MFMA cycles per tile and
-// takes 256 rows, two groups of four chains (64 KiB of LDS, still two workgroups per CU).
+// The split-bf16 prefix scan at K1 <= 32 is a kernel of its own (prefix64_kernel below).
 // LBL (ef_search_labelled): the tile's row labels are staged beside its aux
 // values (wave 1 issues that DMA), and every finished block's scores pass label_mask before
 // consume — the fp32 scan at TGT = 64 only.
@@ -108,10 +111,9 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
   constexpr int PPW = (NI + NW - 1) / NW;                              // pieces per wave
   constexpr int RP = 64 / CPR;                                         // rows per piece
   static_assert((NI % NW == 0 || NI < NW) && RP * CPR == 64 && TG == 64, "tile must be whole 1-KiB pieces");
-  static_assert(TGT == 64 || (KP <= 32 && !COLLECT && TGT == (S3 ? kPrefixSplitTile : kPrefixTile)),
-                "larger tiles: the prefix scans at KP <= 32");
+  static_assert(TGT == 64 || (KP <= 32 && !COLLECT && !S3 && TGT == kPrefixTile),
+                "larger tiles: the fp32 prefix scan at KP <= 32");
   static_assert(!LBL || (!S3 && !CNT && TGT == TG), "labelled: the fp32 scan in 64-row tiles");
-  constexpr int NBG = 4;  // S3 at TGT > 64: blocks run at once (4 x 16 accumulators fit 128 VGPRs)
   // KP = 128 (the k = 128 headline shape): no swizzle.  LDS piece p (1 KiB + 16 B pad)
   // holds row p of the tile's first 32-row block and row 32 + p of the second, so the
   // lane reading row c32 of either block uses one base (c32 * 1040 B) plus immediate
@@ -417,57 +419,6 @@ __global__ __launch_bounds__(512, 4) void search_kernel(
       }
 #pragma unroll
       for (int bi = 0; bi < NB; ++bi) consume(acc[bi], tbase + 32 * bi);  // in row order (tie rule)
-      dma_wait_all();
-      __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
-      continue;
-    }
-    if constexpr (TGT != 64 && S3) {
-      // Split-bf16 chains, NBG blocks at once (their accumulators share the probe fragments;
-      // block bi = rows 32 bi + c32, the same swizzle: 32 is a multiple of SW), the tile's
-      // groups of NBG blocks one after the other, in row order
-      const float* arow = tileG + c32 * KP;
-#pragma unroll
-      for (int g0 = 0; g0 < NB; g0 += NBG) {
-        f32x16 acc[NBG];
-#pragma unroll
-        for (int bi = 0; bi < NBG; ++bi) acc[bi] = acc_init(tileA + 32 * (g0 + bi));
-        // fragment i: chunks 2i (hi) and 2i + 1 (lo) of this lane half's k range
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-          const int c0 = h * (CPR / 2) + 2 * i;
-          const int ch = c0 ^ swz, cl = (c0 + 1) ^ swz;
-          bf16x8 ah[NBG], al[NBG];
-#pragma unroll
-          for (int bi = 0; bi < NBG; ++bi) {
-            ah[bi] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + bi) * 32 * KP + ch * 4));
-            al[bi] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + bi) * 32 * KP + cl * 4));
-          }
-#pragma unroll
-          for (int bi = 0; bi < NBG; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[bi], qh[i], acc[bi], 0, 0, 0);
-#pragma unroll
-          for (int bi = 0; bi < NBG; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[bi], ql[i], acc[bi], 0, 0, 0);
-#pragma unroll
-          for (int bi = 0; bi < NBG; ++bi) acc[bi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[bi], qh[i], acc[bi], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);  // bound the A prefetch depth
-        }
-#pragma unroll
-        for (int bi = 0; bi < NBG; ++bi) {
-          if constexpr (METRIC != EF_METRIC_L2) {  // cosine: -(q.g) * (1/||g||)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const float4 x = *reinterpret_cast<const float4*>(tileA + 32 * (g0 + bi) + 8 * q + 4 * h);
-              acc[bi][4 * q] *= x.x; acc[bi][4 * q + 1] *= x.y; acc[bi][4 * q + 2] *= x.z; acc[bi][4 * q + 3] *= x.w;
-            }
-          }
-          if (tail) {  // uniform: only the last tile has rows past n
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if (tbase + 32 * (g0 + bi) + (r & 3) + 8 * (r >> 2) + 4 * h >= n) acc[bi][r] = INF;
-          }
-        }
-#pragma unroll
-        for (int bi = 0; bi < NBG; ++bi) consume(acc[bi], tbase + 32 * (g0 + bi));  // in row order (tie rule)
-      }
       dma_wait_all();
       __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
       continue;
@@ -800,6 +751,259 @@ __global__ __launch_bounds__(512, 4) void search16_kernel(
     const int lin = xcd_lin();
     const int gc = lin / n_ptiles;
     body(gc, lin - gc * n_ptiles, 0);
+  }
+}
+
+// Split-bf16 prefix scan at K1 <= 32 (L2, main pass only; launch_search_prefix).
+// At these shapes the matrix work per row is so short that the LDS reads and the arg-best
+// epilogue weigh as much as the MFMAs (profiles/r11, r14), so this kernel spends less on both:
+//   * workgroup = 8 waves x 32 PB probes, PB = 2 (kPrefixSplitProbes = 512): each wave keeps PB
+//     32-probe B blocks (pb; K1 VGPRs of hi / lo fragments for the two) and runs every A
+//     fragment it reads against each, so the tile's 32-row blocks go RB = 4 / PB at a time (rb)
+//     as RB x PB = 4 accumulator chains — half the LDS reads, tile DMAs, barriers and gallery
+//     sweeps per MFMA.  PB = 1 (search_kernel's shape) compiles too and measured slower;
+//   * the epilogue merges only the accumulator registers that can change a record (consume);
+//   * the staged norms of a row block are read once and start both probe blocks' chains;
+//   * rows of K1 floats lie in LDS with chunk c of row r at chunk c ^ ((r >> SS) & (CPR - 1)),
+//     SS = 1 at K1 = 32 (128-byte rows: two rows span the 64 banks), 2 at K1 = 16 (four rows).
+//     ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (and
+//     + 32; MI355X LDS): in either group the rows that share a bank range (equal row & 1, or
+//     row & 3) have distinct (r >> SS) & (CPR - 1), so a group covers 64 distinct banks.  Rows
+//     c32 and 32 bi + c32 share a swizzle;
+//   * the probes are read from qpad itself (row stride KP), once per workgroup: no prefix copy.
+// The arithmetic of every (probe, row) score is search_kernel<K1, L2, false, true>'s: the same
+// MFMA, the chain started from the row's fp32 norm, fragments in ascending k, per fragment
+// hi.hi', hi.lo', lo.hi', the same k split over the lane halves — part_key / part_b2 hold the
+// same values, and each probe block consumes its row blocks in row order (the tie rule).
+// 123 VGPRs, no scratch, 66 KiB of LDS at K1 = 32: two workgroups per CU, as search_kernel.
+// bpad is a multiple of 256 only: the upper four waves of the last workgroup may own no probe
+// (live = false).  They read no probe, run the sweep on zeros (they issue tile DMAs and take
+// part in the barriers like the others) and store nothing.
+template <int KP, int K1, int PB>
+__global__ __launch_bounds__(512, 4) void prefix64_kernel(
+    const float* __restrict__ qpad, const float* __restrict__ G1, const float* __restrict__ gnorm1, int64_t n,
+    int n_ptiles, int tiles_per_chunk, int64_t bpad, SearchWs ws) {
+  static_assert((K1 == 16 || K1 == 32) && K1 < KP, "the prefix lengths that take 256-row tiles");
+  constexpr int NW = 8, TGT = kPrefixSplitTile;
+  constexpr int RB = 4 / PB;  // row blocks run at once: RB x PB = 4 accumulator chains
+  constexpr int KH = K1 / 2, NF = KH / 8;  // k per lane half, 8-element fragments of it
+  constexpr int CPR = K1 / 4;              // 16-B chunks per row
+  constexpr int SS = K1 == 32 ? 1 : 2;     // swizzle: chunk ^ ((row >> SS) & (CPR - 1))
+  constexpr int RP = 64 / CPR;             // rows per 1-KiB DMA piece
+  constexpr int NI = TGT / RP, PPW = NI / NW;
+  constexpr int TGS = TGT * K1;            // floats per tile buffer
+  static_assert(PPW * NW == NI && RP % (1 << SS) == 0, "whole pieces per wave, swizzle splits per piece");
+  __shared__ __attribute__((aligned(16))) float smem[2 * TGS + 2 * TGT];
+  float* const sAux0 = smem + 2 * TGS;
+
+  const int lin = xcd_lin();  // the probe tiles of one chunk co-resident on an XCD
+  const int gc = lin / n_ptiles, pt = lin - gc * n_ptiles;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // The lane id is re-derived where it is needed (two VALU instructions) instead of living in
+  // VGPRs through the sweep with what is computed from it: 64 accumulators, 32 probe registers
+  // and 16 of A fragments leave 16 for everything else
+  auto lane_id = [] {
+    unsigned l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return (int)l;
+  };
+
+  int64_t t0, t1;
+  chunk_range<TGT>(n, gc, tiles_per_chunk, t0, t1);
+  // this lane's probe slots: block 0 at s0, block 1 at s0 + 32; a wave's 64 slots lie on one
+  // side of bpad (a multiple of 256)
+  const int64_t w0 = (int64_t)pt * (NW * 32 * PB) + wave * (32 * PB);
+  const bool live = w0 < bpad;  // wave-uniform
+
+  if (t0 >= t1) {  // empty chunk: publish "no candidate" so the reducer can skip it
+    const int lane = lane_id();
+    const int64_t s0 = w0 + lane;
+    if (live && lane < 32) {
+#pragma unroll
+      for (int pb = 0; pb < PB; ++pb) top2_store_empty(ws, (int64_t)gc * bpad, s0 + 32 * pb);
+    }
+    return;
+  }
+
+  // LDS-DMA of tile t into buffer buf: wave w fills pieces [w PPW, (w + 1) PPW), a piece is RP
+  // whole rows, lane-linear.  The swizzle is applied on the source address and splits into a
+  // lane constant and a wave-uniform part: ((j RP + lrow) >> SS) = (j RP >> SS) + (lrow >> SS),
+  // a sum without carries.  Rows past n (tail tile) re-read the last row, masked below.
+  const unsigned lds_base = lds_addr(smem);
+  auto issue_tile = [&](int64_t t, int buf) {
+    const int nrem = (int)((n - t * TGT) < TGT ? (n - t * TGT) : TGT);
+    const int lane = lane_id();
+    const int lr = lane / CPR;                                // this lane's (row, chunk) inside a piece
+    const int lx = (lane % CPR) ^ ((lr >> SS) & (CPR - 1));  // chunk, with the lane's swizzle part
+    if (nrem == TGT) {
+      const unsigned long long gb = uniform_ptr(G1 + t * TGT * K1);
+      const unsigned lro = (unsigned)(lr * K1 * 4);
+#pragma unroll
+      for (int jj = 0; jj < PPW; ++jj) {
+        const int j = wave * PPW + jj;
+        const int sj = ((j * RP) >> SS) & (CPR - 1);
+        glds16s(lro + ((unsigned)(lx ^ sj) << 4), gb + (unsigned long long)(j * RP * K1 * 4),
+                lds_base + (unsigned)((buf * TGS + j * 256) * 4));
+      }
+      if (wave < TGT / 64)  // one 64-row piece of the norms per wave
+        glds4s((unsigned)lane * 4u, uniform_ptr(gnorm1 + t * TGT + wave * 64),
+               lds_base + (unsigned)((2 * TGS + buf * TGT + wave * 64) * 4));
+    } else {
+      const float* gbase = G1 + t * TGT * K1;  // wave-uniform
+#pragma unroll
+      for (int jj = 0; jj < PPW; ++jj) {
+        const int j = wave * PPW + jj;
+        const int sj = ((j * RP) >> SS) & (CPR - 1);
+        int row = j * RP + lr;
+        row = row < nrem ? row : nrem - 1;
+        glds16(gbase + row * K1 + ((lx ^ sj) << 2), lds_base + (unsigned)((buf * TGS + j * 256) * 4));
+      }
+      if (wave < TGT / 64) {
+        const int row = wave * 64 + lane < nrem ? wave * 64 + lane : nrem - 1;
+        glds4(gnorm1 + t * TGT + row, lds_base + (unsigned)((2 * TGS + buf * TGT + wave * 64) * 4));
+      }
+    }
+  };
+
+  issue_tile(t0, 0);
+
+  // Probe fragments (B operands): lane holds probes c32 and 32 + c32 of the wave, k in
+  // [h KH, h KH + KH) of the row's first K1 columns, scaled by -2 (exact) and split, so that a
+  // chain started from ||g||^2 ends at the L2 prefix score
+  bf16x8 qh[PB][NF], ql[PB][NF];
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb) {
+    const int lane = lane_id();
+    const float4* q0 =
+        reinterpret_cast<const float4*>(qpad + (live ? w0 + (lane & 31) + 32 * pb : 0) * KP + (lane >> 5) * KH);
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      const float4 a = live ? q0[2 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 b = live ? q0[2 * i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float t[8] = {-2.f * a.x, -2.f * a.y, -2.f * a.z, -2.f * a.w, -2.f * b.x, -2.f * b.y, -2.f * b.z, -2.f * b.w};
+      split8(t, qh[pb][i], ql[pb][i]);
+    }
+  }
+  // consumed here so that the waits for these loads stand before the loop (search_kernel)
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+    for (int i = 0; i < NF; ++i) asm volatile("" ::"v"(qh[pb][i]), "v"(ql[pb][i]));
+
+  const float INF = __builtin_inff();
+  float b1[PB], b2[PB];
+  int i1[PB];
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb) b1[pb] = b2[pb] = INF, i1[pb] = INT_MAX;
+
+  // Arg-best epilogue of one finished block of scores v (register r <-> row rowbase + (r & 3) +
+  // 8 (r >> 2) + 4 h, increasing with r), merged into probe block pb's running record.  The
+  // screen is search_kernel's: a block whose minimum is not below the lane's runner-up changes
+  // nothing, and when that holds for every lane the block is skipped on a uniform branch.  A
+  // block that passes is walked in row order, and only the registers in which some lane has a
+  // score below its runner-up are merged (a uniform branch each; a score that is not below b2
+  // leaves b1, b2 and i1 as they are): with b1 <= b2 the new runner-up is the median of (b1,
+  // score, b2), and strict '<' keeps the lowest row on ties.  The chunk sweeps are short enough
+  // that about half the blocks pass the screen for one or two lanes, and search_kernel's
+  // branch-free top-2 of all 16 registers (64 VALU instructions) was most of this scan's
+  // non-MFMA work.  The record is the same: minimum, its first row, second smallest of the
+  // multiset.
+  auto consume = [&](const f32x16& v, int rowbase, int pb, int h) {
+    float mn = v[0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mn = fminf(mn, v[r]);
+    if (!__any(mn < b2[pb])) return;  // exact skip: the block changes nothing
+    const int row0 = rowbase + 4 * h;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      // expected not taken: the merges then lie out of line and a walk falls through 16 compares
+      if (__builtin_expect(!__any(v[r] < b2[pb]), 1)) continue;
+      const bool lt = v[r] < b1[pb];
+      b2[pb] = __builtin_amdgcn_fmed3f(b1[pb], v[r], b2[pb]);
+      i1[pb] = lt ? row0 + (r & 3) + 8 * (r >> 2) : i1[pb];
+      b1[pb] = lt ? v[r] : b1[pb];
+    }
+  };
+
+  dma_wait_all();
+  __syncthreads();  // tile t0 landed
+
+  for (int64_t t = t0; t < t1; ++t) {
+    const int buf = (int)((t - t0) & 1);
+    if (t + 1 < t1) issue_tile(t + 1, buf ^ 1);  // lands under this tile's MFMAs
+    const float* tileA = sAux0 + buf * TGT;
+    const bool tail = (t + 1) * TGT > n;
+    const int tbase = (int)(t * TGT);
+    const int lane = lane_id();
+    const int h = lane >> 5, c32 = lane & 31;
+    const int swz = (c32 >> SS) & (CPR - 1);  // rows c32 and 32 bi + c32 share it
+    const float* arow = smem + buf * TGS + c32 * K1;
+#pragma unroll
+    for (int g0 = 0; g0 < TGT / 32; g0 += RB) {  // row blocks g0 .. g0 + RB - 1 against every probe block
+      f32x16 acc[RB][PB];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        f32x16 a;  // ||g||^2 of the block's rows, in the register <-> row map
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 x = *reinterpret_cast<const float4*>(tileA + 32 * (g0 + rb) + 8 * q + 4 * h);
+          a[4 * q] = x.x;
+          a[4 * q + 1] = x.y;
+          a[4 * q + 2] = x.z;
+          a[4 * q + 3] = x.w;
+        }
+#pragma unroll
+        for (int pb = 0; pb < PB; ++pb) acc[rb][pb] = a;
+      }
+      // fragment i: chunks 2i (hi) and 2i + 1 (lo) of this lane half's k range
+#pragma unroll
+      for (int i = 0; i < NF; ++i) {
+        const int c0 = h * (CPR / 2) + 2 * i;
+        const int ch = c0 ^ swz, cl = (c0 + 1) ^ swz;
+        bf16x8 ah[RB], al[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+          ah[rb] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + rb) * 32 * K1 + ch * 4));
+          al[rb] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + rb) * 32 * K1 + cl * 4));
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[c / PB][c % PB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c / PB], qh[c % PB][i], acc[c / PB][c % PB], 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[c / PB][c % PB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c / PB], ql[c % PB][i], acc[c / PB][c % PB], 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[c / PB][c % PB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[c / PB], qh[c % PB][i], acc[c / PB][c % PB], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);  // bound the A prefetch depth
+      }
+      if (tail) {  // uniform: only the last tile has rows past n
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (tbase + 32 * (g0 + rb) + (r & 3) + 8 * (r >> 2) + 4 * h >= n) {
+#pragma unroll
+              for (int pb = 0; pb < PB; ++pb) acc[rb][pb][r] = INF;
+            }
+      }
+#pragma unroll
+      for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) consume(acc[rb][pb], tbase + 32 * (g0 + rb), pb, h);  // in row order (tie rule)
+    }
+    dma_wait_all();
+    __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
+  }
+
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb) {  // merge the two lane halves (same probe, disjoint rows)
+    const float ob1 = __shfl_xor(b1[pb], 32);
+    const int oi1 = __shfl_xor(i1[pb], 32);
+    const float ob2 = __shfl_xor(b2[pb], 32);
+    top2_merge(b1[pb], b2[pb], i1[pb], ob1, ob2, oi1);
+    const int lane = lane_id();
+    if (live && lane < 32) top2_store(ws, (int64_t)gc * bpad, w0 + lane + 32 * pb, b1[pb], b2[pb], i1[pb]);
   }
 }
 
@@ -1192,7 +1396,12 @@ SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows, 
   SearchPlan pl;
   const bool wide = kp > 128;
   const bool w3 = wide && s3;  // split-bf16 wide kernel: 256 x 256 tiles, one workgroup per CU
-  pl.n_ptiles = (int)(bpad / (w3 ? kWide3ProbeTile : wide ? kWideProbeTile : kSearchProbeTile));
+  // probes per workgroup.  The plans of kPrefixSplitTile rows are prefix64_kernel's (512 probes);
+  // bpad is a multiple of 256 only, so its probe tiles are counted rounding up and the last one
+  // may be half empty (the other tile sizes divide bpad)
+  const int64_t ptile = w3 ? kWide3ProbeTile : wide ? kWideProbeTile
+                        : tile_rows == kPrefixSplitTile ? kPrefixSplitProbes : kSearchProbeTile;
+  pl.n_ptiles = (int)((bpad + ptile - 1) / ptile);
   const int64_t rows_per_tile = tile_rows ? tile_rows : w3 ? kWide3RowTile : wide ? kWideRowTile : TG;
   const int64_t tiles = (n + rows_per_tile - 1) / rows_per_tile;
   // ~512 workgroups = one resident wave of them (2 per CU): every chunk is swept by a
@@ -1389,8 +1598,10 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SplitScan& sp,
 //   1. Q1 <- the probes' first K1 columns; search_kernel<K1> over (Q1, G1, gnorm1): the
 //      timed main launch, a K1 / KP share of the full scan's MFMAs, in 128-row tiles at
 //      K1 <= 32 (prefix_tile_rows; profiles/r08).  S3 (EF_OPT_SEARCH_PREFIX_SPLIT): G1 holds
-//      split-bf16 rows, the kernel splits Q1 in registers and runs the split chain, 3 bf16
-//      MFMAs of 32 cycles per 16 k against 8 fp32 ones of 64, in 256-row tiles (profiles/r11).
+//      split-bf16 rows, the kernel splits the probes in registers and runs the split chain, 3
+//      bf16 MFMAs of 32 cycles per 16 k against 8 fp32 ones of 64.  At K1 <= 32 that is
+//      prefix64_kernel: 512 probes per workgroup (pl1 counts those tiles), 256-row tiles, the
+//      probes read from qpad in place — no Q1 copy and no launch for it (profiles/r14).
 //   2. reduce_prefix_kernel: proven probes get their key / match record, the others are listed.
 //   3. The listed probes' rows are gathered into qpad2 and go through top1_t's sequence
 //      in its cnt form (untimed, the device count in place of b, no memset of its own); the grids
@@ -1402,14 +1613,19 @@ static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const Sea
                                   int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
                                   long long* keys, ef_ctx* c) {
   constexpr int M = EF_METRIC_L2;
-  const dim3 block(512), pgrid((unsigned)((b + 3) / 4));
-  hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((bpad * (K1 / 4) + 255) / 256)), dim3(256), 0, s,
-                     reinterpret_cast<const float4*>(qpad), bpad, KP / 4, K1 / 4, reinterpret_cast<float4*>(pw.q1));
+  const dim3 block(512), pgrid((unsigned)((b + 3) / 4)), sgrid((unsigned)(pl1.nchunks * pl1.n_ptiles));
+  constexpr bool W64 = S3 && K1 <= 32;  // prefix64_kernel reads the probes' rows in place
+  if constexpr (!W64)
+    hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((bpad * (K1 / 4) + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const float4*>(qpad), bpad, KP / 4, K1 / 4, reinterpret_cast<float4*>(pw.q1));
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_SEARCH, &tev);
-  hipLaunchKernelGGL((search_kernel<K1, M, false, S3, false, (K1 <= 32 ? (S3 ? kPrefixSplitTile : kPrefixTile) : TG)>),
-                     dim3((unsigned)(pl1.nchunks * pl1.n_ptiles)), block, 0, s, pw.q1, G1, gnorm1, n, pl1.n_ptiles,
-                     pl1.tiles_per_chunk, bpad, ws);
+  if constexpr (W64)
+    hipLaunchKernelGGL((prefix64_kernel<KP, K1, kPrefixSplitProbes / 256>), sgrid, block, 0, s, qpad, G1, gnorm1, n, pl1.n_ptiles,
+                       pl1.tiles_per_chunk, bpad, ws);
+  else
+    hipLaunchKernelGGL((search_kernel<K1, M, false, S3, false, (K1 <= 32 ? kPrefixTile : TG)>), sgrid, block, 0, s,
+                       pw.q1, G1, gnorm1, n, pl1.n_ptiles, pl1.tiles_per_chunk, bpad, ws);
   timer_end(c, &tev);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
