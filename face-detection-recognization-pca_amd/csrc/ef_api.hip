@@ -1022,6 +1022,71 @@ int ef_search_labelled(ef_ctx* c, const float* Q, int64_t b, int32_t metric, int
   return r.fetch(c);
 }
 
+int ef_score_census(ef_ctx* c, const float* Q, int64_t b, int32_t metric, const int32_t* probe_labels,
+                    const int64_t* exclude_rows, float lo, float hi, int32_t nbins, int64_t* counts, uint32_t flags) {
+  if (!c) return EF_E_INVALID;
+  if (c->gal.k == 0) return set_err(c, EF_E_STATE, "ef_score_census: no gallery (call ef_gallery_set)");
+  // NaN bounds fail lo < hi; infinite ones the differences
+  if (!counts || !probe_labels || b < 0 || (b > 0 && !Q) || (metric != EF_METRIC_L2 && metric != EF_METRIC_COSINE) ||
+      nbins < 1 || nbins > kCensusMaxBins || !(lo < hi) || !(hi - lo < __builtin_inff()) || !(lo - lo == 0.f))
+    return set_err(c, EF_E_INVALID, "ef_score_census: bad arguments (1 <= nbins <= 2048, finite lo < hi, "
+                                    "probe_labels and counts required)");
+  if (!c->has_labels)
+    return set_err(c, EF_E_STATE, "ef_score_census: the gallery has no labels (call ef_gallery_labels)");
+  if (c->comm && c->comm_size > 1)
+    return set_err(c, EF_E_STATE, "ef_score_census: no census over a communicator; run each shard on a context "
+                                  "without one and add the counts");
+  (void)hipSetDevice(c->device);
+  const bool dev = (flags & EF_MEM_DEVICE) != 0;
+  const Gallery& g = c->gal;
+  const size_t cnt_bytes = (size_t)2 * (nbins + 3) * sizeof(int64_t);
+  if (b == 0 || g.n == 0) {
+    if (dev) EF_HIP(c, hipMemsetAsync(counts, 0, cnt_bytes, c->stream), "zero counts");
+    else std::memset(counts, 0, cnt_bytes);
+    return EF_OK;
+  }
+  const int64_t bpad = round_up(b, kSearchProbeTile);
+  EF_TRY(stage_queries(c, Q, b, dev, bpad));
+  // scratch: plab[bpad], pexcl[bpad], qaux[bpad], then a host call's labels, exclusions and counts
+  const size_t lab_off = align256((size_t)3 * bpad * sizeof(int));
+  const size_t exc_off = lab_off + align256((size_t)b * sizeof(int32_t));
+  const size_t cnt_off = exc_off + align256((size_t)b * sizeof(int64_t));
+  EF_TRY(ensure(c, c->label_ws, cnt_off + cnt_bytes));
+  char* base = static_cast<char*>(c->label_ws.p);
+  int* plab = reinterpret_cast<int*>(base);
+  int* pexcl = plab + bpad;
+  float* qaux = reinterpret_cast<float*>(pexcl + bpad);
+  unsigned long long* cdev = reinterpret_cast<unsigned long long*>(counts);
+  if (!dev) {
+    EF_HIP(c, hipMemcpyAsync(base + lab_off, probe_labels, (size_t)b * sizeof(int32_t), hipMemcpyHostToDevice, c->stream),
+           "H2D probe labels");
+    probe_labels = reinterpret_cast<const int32_t*>(base + lab_off);
+    if (exclude_rows) {
+      EF_HIP(c, hipMemcpyAsync(base + exc_off, exclude_rows, (size_t)b * sizeof(int64_t), hipMemcpyHostToDevice, c->stream),
+             "H2D excluded rows");
+      exclude_rows = reinterpret_cast<const int64_t*>(base + exc_off);
+    }
+    cdev = reinterpret_cast<unsigned long long*>(base + cnt_off);
+  }
+  EF_HIP(c, hipMemsetAsync(cdev, 0, cnt_bytes, c->stream), "zero counts");
+  EF_HIP(c, launch_label_prep(c->stream, probe_labels, exclude_rows, b, bpad, c->g_offset, g.n, plab, pexcl),
+         "label prep");
+  const float* qpad = static_cast<const float*>(c->q_pad.p);
+  EF_HIP(c, launch_census_probe_aux(c->stream, qpad, bpad, g.kp, metric, qaux), "census probe norms");
+  const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? g.gnorm2.p : g.ginv.p);
+  for (const SearchPiece& p : search_pieces(b, g.kp))  // a padded probe block stays below 2 GiB
+    EF_HIP(c,
+           launch_census(c->stream, g.kp, metric, qpad + p.off * g.kp, p.bpad, p.b, static_cast<const float*>(g.G.p),
+                         aux, static_cast<const int*>(c->glabels.p), g.n, qaux + p.off, plab + p.off, pexcl + p.off, lo,
+                         hi, nbins, cdev),
+           "score census");
+  if (!dev) {
+    EF_HIP(c, hipMemcpyAsync(counts, cdev, cnt_bytes, hipMemcpyDeviceToHost, c->stream), "D2H counts");
+    EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
+  }
+  return EF_OK;
+}
+
 // Top-m search of the probes in ctx->q_pad (search_run's contract): keys_dev[b][m] and,
 // when match_dev is non-null, match_dev[b][m].  The split scans of EF_OPT_SEARCH_SPLIT_BF16
 // apply (3, the single-bf16 screen, counts as 1); the prefix scan never does.

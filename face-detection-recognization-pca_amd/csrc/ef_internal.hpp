@@ -472,6 +472,7 @@ struct ef_ctx {
   bool has_labels = false;
   ef::DevBuf glabels;   // int32[gal.n]
   ef::DevBuf label_ws;  // per-call scratch of ef_search_labelled: int[2][bpad], then the host call's staging
+                        // (ef_score_census: int[2][bpad], float[bpad] probe norms, the staging, the counts)
   ef::GalleryDerived der;  // the split and prefix copies and the prefix guard (search_copies)
   int64_t opt_search_prefix = 1;
   int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32
@@ -604,6 +605,18 @@ hipError_t launch_keys_none(hipStream_t s, long long* keys, int64_t b, ef_match*
 // negative entry, one outside [g_offset, g_offset + n), and the rows past b)
 hipError_t launch_label_prep(hipStream_t s, const int32_t* plabels, const int64_t* excl, int64_t b, int64_t rows,
                              int64_t g_offset, int64_t n, int* plab, int* pexcl);
+// Score census (ef_score_census; ef_census.hip).  launch_census_probe_aux:
+// qaux[rows] <- what the census epilogue needs of each probe row of qpad[rows][kp], from the fp64
+// sum of squares rounded once: ||q||^2 (L2), or 1/||q|| (cosine; 0 for a zero probe, NaN for one
+// with a NaN or infinite component).  launch_census: the pairs of probes [0, b) of qpad (bpad
+// rows, a multiple of 128) with the n gallery rows are added to counts[2][nbins + 3], which the
+// caller has zeroed; aux as the scans take it (||g||^2 for L2, 1/||g|| for cosine), plab / pexcl
+// launch_label_prep's output.
+constexpr int kCensusMaxBins = EF_CENSUS_MAX_BINS;
+hipError_t launch_census_probe_aux(hipStream_t s, const float* qpad, int64_t rows, int kp, int metric, float* qaux);
+hipError_t launch_census(hipStream_t s, int kp, int metric, const float* qpad, int64_t bpad, int64_t b, const float* G,
+                         const float* aux, const int* glab, int64_t n, const float* qaux, const int* plab,
+                         const int* pexcl, float lo, float hi, int nbins, unsigned long long* counts);
 // One scan launch, the only map from (kp, metric, variant, main or COLLECT, cnt, labelled) to a scan
 // kernel: search_kernel, search16_kernel (kp == 128 under variant 1) and, kp > 128, the wide
 // kernels; variant 3 counts as 1 at kp <= 128.  ws.lbl != 0 picks the labelled instantiations

@@ -13,6 +13,8 @@ from .scanner import FrameScanner, HaarScanner, decide, label_bank, label_one, l
 from .compat import face_space_distance, reconstruct_faces  # noqa: F401
 from .evaluate import (OpenSetRates, compare_subspaces, equal_error_threshold, evaluate_model,  # noqa: F401
                        leave_one_out, open_set_rates)
+from .evaluate import (VerificationRates, auc, compare_verification, d_prime, pair_equal_error,  # noqa: F401
+                       score_census, tar_at_fmr, verification_rates)
 from .fisher import Fisherfaces  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
@@ -40,4 +42,6 @@ __all__ = [
     "FrameScanner", "HaarScanner", "decide", "label_one", "label_pair", "label_bank", "reconstruct_faces", "face_space_distance", "face_gate_mask", "bank_recon_schedule",
     "leave_one_out", "open_set_rates", "equal_error_threshold", "evaluate_model", "OpenSetRates",
     "Fisherfaces", "LdaResult", "compare_subspaces",
+    "score_census", "VerificationRates", "verification_rates", "pair_equal_error", "tar_at_fmr", "auc", "d_prime",
+    "compare_verification",
 ]

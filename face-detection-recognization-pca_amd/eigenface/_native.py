@@ -46,6 +46,7 @@ EF_OPT_SEARCH_TOPK_CAND = 12
 EF_OPT_SEARCH_PREFIX_SPLIT = 13
 EF_TOPK_MAX = 64  # most ranks of a top-m search
 EF_LABEL_SAME, EF_LABEL_OTHER, EF_LABEL_ANY = 0, 1, 2  # ef_search_labelled relations
+EF_CENSUS_MAX_BINS = 2048  # most bins of ef_score_census
 EF_BANK_MAX_MODELS = 4096
 EF_BANK_MAX_PROBES = 4096  # per ef_bank_recognize call
 EF_E_INVALID, EF_E_STATE = -1, -3
@@ -151,6 +152,8 @@ _SIGS = {
     # labelled search: added by symbol, EF_API_VERSION stays 7
     "ef_gallery_labels": ([vp, vp, i64, u32], C.c_int),
     "ef_search_labelled": ([vp, vp, i64, i32, i32, vp, vp, vp, vp, u32], C.c_int),
+    # score census: added the same way
+    "ef_score_census": ([vp, vp, i64, i32, vp, vp, C.c_float, C.c_float, i32, vp, u32], C.c_int),
     # model bank: added after API v7 without a version bump, so bound (and checked) by symbol
     "ef_bank_clear": ([vp], C.c_int),
     "ef_bank_add": ([vp, vp, vp, i64, i32, vp, i64, u32, C.POINTER(i32)], C.c_int),

@@ -49,6 +49,23 @@ def _empty(shape, dtype, device):
     return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=device)
 
 
+def _per_probe(x, np_dtype, name, q, dev):
+    """(array or tensor, pointer) of one value per probe of q, or (None, None): a host array for
+    host probes; for device probes a tensor on their device (an array is uploaded)."""
+    if x is None:
+        return None, None
+    if dev:
+        import torch
+        if not _is_dev(x):
+            x = torch.as_tensor(np.ascontiguousarray(x, dtype=np_dtype), device=q.device)
+        x, xp = _dev(x, getattr(torch, np.dtype(np_dtype).name))
+    else:
+        x, xp = _host(x, np_dtype)
+    if tuple(x.shape) != (q.shape[0],):
+        raise ValueError(f"{name} must be ({q.shape[0]},), got {tuple(x.shape)}")
+    return x, xp
+
+
 def _gate_arg(gate, device, M):
     """(array or tensor, pointer) of a face gate (M,) float32: NumPy for ``device`` None, else a
     tensor on ``device`` (an array is uploaded)."""
@@ -936,23 +953,8 @@ class Engine:
         if self.gallery_k is None:
             raise RuntimeError("no gallery: call set_gallery first")
         q, qp, _, b, dev = self._probes(Q, pixels=False)
-
-        def per_probe(x, np_dtype, name):
-            if x is None:
-                return None, None
-            if dev:
-                import torch
-                if not _is_dev(x):
-                    x = torch.as_tensor(np.ascontiguousarray(x, dtype=np_dtype), device=q.device)
-                x, xp = _dev(x, getattr(torch, np.dtype(np_dtype).name))
-            else:
-                x, xp = _host(x, np_dtype)
-            if tuple(x.shape) != (b,):
-                raise ValueError(f"{name} must be ({b},), got {tuple(x.shape)}")
-            return x, xp
-
-        pl, plp = per_probe(probe_labels, np.int32, "probe_labels")
-        ex, exp = per_probe(exclude_rows, np.int64, "exclude_rows")
+        pl, plp = _per_probe(probe_labels, np.int32, "probe_labels", q, dev)
+        ex, exp = _per_probe(exclude_rows, np.int64, "exclude_rows", q, dev)
         if pl is None and rel != N.EF_LABEL_ANY:
             raise ValueError("probe_labels are required for the relations 'same' and 'other'")
         out, op = self._result(q, dev, out, (b,), records, "out" if records else "keys")
@@ -980,6 +982,47 @@ class Engine:
         """The match records of the labelled search (as search_matches returns them): shards
         searched one by one merge with merge_matches / merge_matches_host unchanged."""
         return self._labelled(Q, probe_labels, relation, exclude_rows, metric, out, True)
+
+    # ------------------------------------------------------------- score census
+    def score_census(self, Q, probe_labels, exclude_rows=None, metric="cosine", nbins=256, range=(-1.0, 1.0),
+                     counts=None):
+        """ef_score_census: histograms of all genuine (row 0) and all impostor (row 1) pair scores
+        of the probes against the labelled resident gallery, an int64 array (2, nbins + 3): slot 0
+        the scores below ``range[0]``, slots 1 .. nbins the bins, slot nbins + 1 the scores at or
+        above ``range[1]``, slot nbins + 2 the pairs whose score is not finite.  The pair of probe
+        p with the row of global index ``exclude_rows[p]`` is left out (negative: nothing).  Host
+        arrays in, a host array out; device tensors in, a device tensor out (stream-ordered, as
+        search_labelled_keys; ``counts``: the caller's tensor)."""
+        mt = _metric(metric)
+        nbins = int(nbins)
+        if not 1 <= nbins <= N.EF_CENSUS_MAX_BINS:
+            raise ValueError(f"nbins must be 1 .. {N.EF_CENSUS_MAX_BINS}, got {nbins}")
+        lo, hi = (float(np.float32(v)) for v in range)
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError(f"range must be finite (lo, hi) with lo < hi in float32, got {tuple(range)}")
+        if self.gallery_k is None:
+            raise RuntimeError("no gallery: call set_gallery first")
+        if probe_labels is None:
+            raise ValueError("probe_labels are required")
+        q, qp, _, b, dev = self._probes(Q, pixels=False)
+        pl, plp = _per_probe(probe_labels, np.int32, "probe_labels", q, dev)
+        ex, exp = _per_probe(exclude_rows, np.int64, "exclude_rows", q, dev)
+        shape = (2, nbins + 3)
+        if dev:
+            import torch
+            if counts is None:
+                counts = torch.empty(shape, dtype=torch.int64, device=q.device)
+            self._dev_out(counts, shape, torch.int64, "counts")
+            cp = counts.data_ptr()
+        else:
+            if counts is not None:
+                raise ValueError("counts is for device input; host input returns a new array")
+            counts = np.empty(shape, np.int64)
+            cp = counts.ctypes.data
+        with self._order(dev, q, pl, ex, counts):
+            self._chk(self._lib.ef_score_census(self._h, qp, b, mt, plp, exp, lo, hi, nbins, cp,
+                                                N.EF_MEM_DEVICE if dev else 0))
+        return counts
 
     # ------------------------------------------------------------- top-m search
     def _topk_m(self, m):

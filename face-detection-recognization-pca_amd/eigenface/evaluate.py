@@ -157,6 +157,178 @@ def compare_subspaces(pca_features, fisher_features, labels, metric="l2", device
     return out
 
 
+# ------------------------------------------------------------------- pairwise verification
+# The score census (Engine.score_census, ef_score_census) counts ALL genuine and ALL impostor
+# pair scores of a labelled gallery into two histograms on the GPU; everything below it is host
+# arithmetic on those (2, nbins + 3) counts: slot 0 the scores below lo, slots 1 .. nbins the
+# bins of width (hi - lo) / nbins, slot nbins + 1 the scores at or above hi, slot nbins + 2 the
+# pairs whose score is not finite.
+
+@dataclass
+class VerificationRates:
+    thresholds: np.ndarray  # the nbins + 1 bin edges lo + j (hi - lo) / nbins, ascending
+    fmr: np.ndarray         # share of the impostor pairs accepted at each edge (NaN: no impostor pair)
+    fnmr: np.ndarray        # share of the genuine pairs rejected at each edge (NaN: no genuine pair)
+    metric: str
+    n_genuine: int          # pairs with a finite score: the denominators
+    n_impostor: int
+    nonfinite: tuple        # (genuine, impostor) pairs whose score is not finite: in no rate
+
+
+def _census_counts(counts):
+    c = np.asarray(counts)
+    if c.ndim != 2 or c.shape[0] != 2 or c.shape[1] < 4 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"counts must be an integer array (2, nbins + 3), got {c.dtype} {c.shape}")
+    if (c < 0).any():
+        raise ValueError("counts must not be negative")
+    return c.astype(np.int64), c.shape[1] - 3
+
+
+def _census_range(lo, hi):
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"the range must be finite with lo < hi, got ({lo}, {hi})")
+    return lo, hi
+
+
+def verification_rates(counts, lo, hi, metric) -> VerificationRates:
+    """FMR and FNMR at the nbins + 1 bin edges from the census counts (pure host).  A pair is
+    accepted at edge e when it is binned on the accepting side of e (``_accept``'s direction):
+    score >= e for cosine, score < e for L2 (<= but for the scores equal to an edge, which the
+    bins cannot tell).  The non-finite slot is in no numerator and no denominator; a side
+    without a finite pair gives NaN."""
+    metric = _metric_name(metric)
+    c, nbins = _census_counts(counts)
+    lo, hi = _census_range(lo, hi)
+    edges = lo + (hi - lo) * np.arange(nbins + 1, dtype=np.float64) / nbins
+    finite = c[:, :nbins + 2]
+    below = np.cumsum(finite, axis=1)[:, :nbins + 1]  # binned below edge j: slots 0 .. j
+    total = finite.sum(axis=1)
+    accepted = total[:, None] - below if metric == "cosine" else below
+    with np.errstate(invalid="ignore", divide="ignore"):
+        share = np.where(total[:, None] > 0, accepted / np.maximum(total[:, None], 1).astype(np.float64), np.nan)
+    return VerificationRates(edges, share[1], 1.0 - share[0], metric, int(total[0]), int(total[1]),
+                             (int(c[0, nbins + 2]), int(c[1, nbins + 2])))
+
+
+def pair_equal_error(rates: VerificationRates):
+    """(threshold, rate): the edge with the smallest max(FMR, FNMR) and that maximum; among equals
+    the strictest edge (the largest similarity, the smallest distance), equal_error_threshold's
+    rule.  A side without pairs (NaN) does not count; (NaN, NaN) when neither has any."""
+    worst = np.fmax(rates.fmr, rates.fnmr)
+    if worst.size == 0 or np.isnan(worst).all():
+        return float("nan"), float("nan")
+    best = np.nanmin(worst)
+    tied = rates.thresholds[worst == best]
+    return float(tied.max() if rates.metric == "cosine" else tied.min()), float(best)
+
+
+def tar_at_fmr(rates: VerificationRates, fmr) -> float:
+    """The largest true-accept rate 1 - FNMR over the edges whose FMR is at most ``fmr``; NaN when
+    no edge qualifies or a side has no pairs."""
+    ok = rates.fmr <= float(fmr)  # False for NaN
+    tar = (1.0 - rates.fnmr)[ok]
+    tar = tar[~np.isnan(tar)]
+    return float(tar.max()) if tar.size else float("nan")
+
+
+def auc(rates: VerificationRates) -> float:
+    """Area under the ROC (FMR, TAR) through the edges, closed at (0, 0) and (1, 1), by the
+    trapezoid rule; NaN when a side has no pairs."""
+    if np.isnan(rates.fmr).any() or np.isnan(rates.fnmr).any():
+        return float("nan")
+    x = np.concatenate([[0.0], rates.fmr, [1.0]])
+    y = np.concatenate([[0.0], 1.0 - rates.fnmr, [1.0]])
+    order = np.lexsort((y, x))
+    x, y = x[order], y[order]
+    return float(((x[1:] - x[:-1]) * (y[1:] + y[:-1])).sum() / 2.0)
+
+
+def d_prime(counts, lo, hi) -> float:
+    """|mean_g - mean_i| / sqrt((var_g + var_i) / 2) from the bin centres, weighted by the counts
+    of the nbins inner bins (the outer and the non-finite slots have no centre and are left
+    out).  NaN when a side has no pair inside the range or both variances vanish at one mean."""
+    c, nbins = _census_counts(counts)
+    lo, hi = _census_range(lo, hi)
+    centre = lo + (hi - lo) * (np.arange(nbins, dtype=np.float64) + 0.5) / nbins
+    w = c[:, 1:nbins + 1].astype(np.float64)
+    tot = w.sum(axis=1)
+    if (tot == 0).any():
+        return float("nan")
+    mean = (w * centre).sum(axis=1) / tot
+    var = (w * (centre[None, :] - mean[:, None]) ** 2).sum(axis=1) / tot
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(abs(mean[0] - mean[1]) / np.sqrt((var[0] + var[1]) / 2.0))
+
+
+def _default_census_range(g, metric):
+    if metric == "cosine":
+        return -1.0, 1.0  # a similarity that rounds to >= 1 falls in the top slot, an outer bin of the rates
+    top = 4.0 * float((np.asarray(g, np.float64) ** 2).sum(axis=1).max(initial=0.0))  # ||a - b||^2 <= 4 max ||g||^2
+    hi = np.float32(top)
+    if float(hi) < top:
+        hi = np.nextafter(hi, np.float32(np.inf))
+    return 0.0, float(hi) if hi > 0 and np.isfinite(hi) else 1.0
+
+
+def score_census(G, labels, metric="cosine", nbins=1024, range=None, device=0, batch=4096, engine=None):
+    """The census of a labelled gallery against itself, leave-one-out: every row of ``G`` (n, k)
+    is a probe, its own row is excluded, and the batches' counts are summed on the host.  Loads G
+    and its int32 ``labels`` into the engine (a new Engine(device) unless ``engine`` is given).
+    Returns ``(counts, (lo, hi))``: counts int64 (2, nbins + 3), genuine then impostor, and the
+    float32 range they were binned over — by default (-1, 1) for cosine and (0, 4 max ||g||^2)
+    for L2, the maximum taken from the data in fp64.  Every unordered pair {a, b} appears twice,
+    as (a, b) and as (b, a): the counts are of ordered pairs, which leaves every rate unchanged."""
+    from .engine import Engine
+    metric = _metric_name(metric)
+    g = np.ascontiguousarray(G, dtype=np.float32)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if g.ndim != 2 or lab.shape != (g.shape[0],):
+        raise ValueError(f"G must be (n, k) and labels (n,), got {g.shape} and {lab.shape}")
+    lo, hi = _default_census_range(g, metric) if range is None else range
+    lo, hi = _census_range(np.float32(lo), np.float32(hi))
+    nbins = int(nbins)
+    n = g.shape[0]
+    own = engine is None
+    e = Engine(device) if own else engine
+    try:
+        e.set_gallery(g)
+        e.set_gallery_labels(lab)
+        counts = np.zeros((2, nbins + 3), np.int64)
+        rows = np.arange(n, dtype=np.int64)
+        for a in np.arange(0, n, int(batch)):
+            s = slice(int(a), min(n, int(a) + int(batch)))
+            counts += e.score_census(g[s], lab[s], rows[s], metric, nbins, (lo, hi))
+    finally:
+        if own:
+            e.close()
+    return counts, (lo, hi)
+
+
+def summarize_verification(counts, lo, hi, metric, fmr=(1e-2, 1e-3)):
+    """The host half of compare_verification: pair counts, the pairwise equal-error threshold and
+    rate, AUC, d' and the true-accept rate at each target FMR."""
+    r = verification_rates(counts, lo, hi, metric)
+    t, eer = pair_equal_error(r)
+    return {"metric": r.metric, "range": (float(lo), float(hi)), "n_genuine": r.n_genuine, "n_impostor": r.n_impostor,
+            "nonfinite": r.nonfinite, "equal_error_threshold": t, "equal_error_rate": eer, "auc": auc(r),
+            "d_prime": d_prime(counts, lo, hi), "tar_at_fmr": {float(f): tar_at_fmr(r, f) for f in fmr}}
+
+
+def compare_verification(pca_features, fisher_features, labels, metric="l2", fmr=(1e-2, 1e-3), nbins=1024, device=0,
+                         batch=4096, engine=None):
+    """The pairwise counterpart of compare_subspaces: the same labelled rows in two feature
+    spaces, ``{"pca": summarize_verification(...), "fisher": ...}``, each from ``score_census`` on
+    its features over its own default range.  What a discriminant fit buys at a fixed FMR."""
+    metric = _metric_name(metric)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    out = {}
+    for name, feats in (("pca", pca_features), ("fisher", fisher_features)):
+        counts, (lo, hi) = score_census(feats, lab, metric, nbins, None, device, batch, engine)
+        out[name] = summarize_verification(counts, lo, hi, metric, fmr)
+    return out
+
+
 def evaluate_model(model_data, metric="cosine", device=0, keys=None):
     """Leave-one-out evaluation of a model dict holding ``face_features`` (n, k) and
     ``face_labels`` (n,) — the face_model.pkl layout (train-v4.py:210-222).  Returns

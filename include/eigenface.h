@@ -366,6 +366,59 @@ int ef_search_labelled(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric, i
                        const int64_t* exclude_rows /* [b] or NULL */,
                        int64_t* keys /* [b] or NULL */, ef_match* matches /* [b] or NULL */, uint32_t flags);
 
+/* ------------------------------------------------- score census (verification evaluation)
+ * Added by symbol (EF_API_VERSION stays 7).  Histograms of ALL genuine and ALL impostor pair
+ * scores of b probes against the resident labelled gallery: what FMR(t), FNMR(t), TAR at a fixed
+ * FMR, the pairwise equal-error rate, AUC and d' are computed from.  A distance GEMM whose
+ * epilogue bins each score instead of taking an arg-best: one gallery sweep per 128-probe tile,
+ * no b x n array of any kind.
+ *
+ * What is counted: each (probe p, resident row r) is one pair, unless r's global index (local row
+ *   + global_offset) equals exclude_rows[p]; a negative entry, one outside this shard, or
+ *   exclude_rows == NULL excludes nothing (ef_search_labelled's rule).  Side 0 (genuine) takes
+ *   the pairs with label[r] == probe_labels[p], side 1 (impostor) the rest.  The score is the one
+ *   ef_keys_decode shows: squared L2 distance, or cosine similarity, where a zero row or a zero
+ *   probe scores 0.
+ * counts[side][nbins + 3], overwritten by the call (nothing accumulates across calls), with
+ *   w = (hi - lo) / nbins:
+ *     [0]          scores below lo
+ *     [1 + j]      lo + j w <= score < lo + (j + 1) w,  j = 0 .. nbins - 1
+ *     [nbins + 1]  scores at or above hi
+ *     [nbins + 2]  pairs whose scan score is not finite (a NaN or +-inf component in the row or
+ *                  in the probe); such a pair is counted in no other slot.
+ * Guarantee: every qualifying pair is counted exactly once; all accumulation is in integers, so
+ *   the counts are the same on every run.  Inside the scan's domain (as for ef_search: fp32
+ *   max |g|^2 in [2^-80, 2^126] together with 2.02 |q| max|g|, for cosine also |q|^2 >= 2^-80 and
+ *   no non-zero row with |g|^2 < 2^-80) a pair lands in the bin of its fp64 score, or in a
+ *   neighbouring bin when that score lies within delta of an edge: for every edge
+ *   e_j = lo + j w, the number of pairs binned below e_j lies between the fp64 counts of
+ *   score < e_j - delta and of score < e_j + delta.  With u = 2^-24, kp the padded k
+ *   (16, 32, 64, 128, 256, 512, then multiples of 128), |q| and |g| Euclidean norms and the
+ *   maxima taken over the call's probes, the gallery's rows and the pairs' scores s:
+ *     L2      delta = 2 [(kp + 4) u 1.01 (2 max|q| max|g| + max|g|^2) + 4 u max|s|]
+ *                     + 8 u max(|lo|, |hi|)
+ *     cosine  delta = 2 (kp + 12) u 1.01 + 8 u max(|lo|, |hi|)
+ *   derived from the kernel's arithmetic: a chain of kp fp32 fused multiply-adds
+ *   from the row's fp32 -|g|^2 / 2 (L2), |q|^2 and 1/|q| rounded once from fp64, the row's fp32
+ *   1/|g|, one rounding for the score; the last term is the bin index, floor((s - lo) nbins /
+ *   (hi - lo)) in fp32.  lo, hi and the scores are fp32: scores that are integers below 2^23, with
+ *   lo = -0.5 and hi - lo = nbins, are binned exactly.
+ *   Outside the domain every pair is still counted once, in a bin that need not be its own; a row
+ *   with finite components whose squares overflow fp32 scores 0 under cosine.
+ * Arguments: 1 <= nbins <= 2048; lo < hi, both finite; probe_labels and counts non-NULL; b = 0
+ *   (or an empty gallery) is EF_OK with all zeros.  EF_E_STATE: no gallery; no gallery labels; a
+ *   communicator of more than one rank attached (run each shard on its own context and add the
+ *   counts: they are additive across shards given global exclude_rows).  EF_E_INVALID for every
+ *   other bad argument.  With EF_MEM_DEVICE every pointer is a device pointer and the call does
+ *   not wait.  Every k of ef_search is supported.  Memory: O(b) + O(nbins) beside the padded
+ *   probes. */
+#define EF_CENSUS_MAX_BINS 2048
+int ef_score_census(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric,
+                    const int32_t* probe_labels /* [b] */,
+                    const int64_t* exclude_rows /* [b] or NULL */,
+                    float lo, float hi, int32_t nbins,
+                    int64_t* counts /* [2][nbins + 3] */, uint32_t flags);
+
 /* ------------------------------------------------- Fisher discriminant (Fisherfaces)
  * Added by symbol (EF_API_VERSION stays 7).  A linear discriminant inside face space
  * (Belhumeur, Hespanha, Kriegman 1997): from features F[n][k] (EF_F32 / EF_F64; a fit's
