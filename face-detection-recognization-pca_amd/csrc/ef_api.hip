@@ -324,6 +324,35 @@ static int search_qpad(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long
   return EF_OK;
 }
 
+// The split form of the fp32 model (EF_OPT_PROJECT_SPLIT_BF16): the three bf16 pieces of W,
+// round(mean) as bytes and the correction row, built once per model by the first projection
+// that can use them (ef_model_set resets split3_state); the device-side guard decides whether
+// the form is exact for this model (split3_state 1) or the model keeps the fp32 kernel (-1).
+static int split3_prepare(ef_ctx* c) {
+  const int64_t d = c->d;
+  const int ldw = c->kpw;
+  EF_TRY(ensure(c, c->W3f, (size_t)3 * ldw * d * sizeof(unsigned short)));
+  EF_TRY(ensure(c, c->corr, (size_t)ldw * sizeof(float)));
+  const size_t off = align256((size_t)d);  // the two counters sit behind the bytes
+  EF_TRY(ensure(c, c->mean_u8, off + 16));
+  const int nchunk = 256;
+  DevBuf cp;  // the kernels that use it are synchronised below, before it goes out of scope
+  EF_TRY(ensure(c, cp, (size_t)nchunk * ldw * sizeof(double)));
+  int bad[2] = {1, 1};
+  int* bad_dev = reinterpret_cast<int*>(static_cast<char*>(c->mean_u8.p) + off);
+  EF_HIP(c, hipMemsetAsync(bad_dev, 0, sizeof(bad), c->stream), "split model");
+  EF_HIP(c,
+         launch_split3_model(c->stream, static_cast<const float*>(c->W.p), static_cast<const float*>(c->mean.p), d,
+                             ldw, c->W3f.p, static_cast<uint8_t*>(c->mean_u8.p), static_cast<float*>(c->corr.p),
+                             static_cast<double*>(cp.p), nchunk, bad_dev),
+         "split model");
+  EF_HIP(c, hipMemcpyAsync(bad, bad_dev, sizeof(bad), hipMemcpyDeviceToHost, c->stream), "split model");
+  EF_HIP(c, hipStreamSynchronize(c->stream), "split model");
+  c->split3_state = (bad[0] == 0 && bad[1] == 0) ? 1 : -1;
+  if (c->split3_state < 0) release(c->W3f);
+  return EF_OK;
+}
+
 // Project b probes (device pointer P) into ctx->q_pad; optional feature output (device).
 static int project_dev(ef_ctx* c, const void* P, int dtype, int64_t b, int64_t bpad, float* f_dev, DevBuf* dst) {
   EF_TRY(ensure(c, *dst, (size_t)bpad * c->kp * sizeof(float)));
@@ -332,14 +361,25 @@ static int project_dev(ef_ctx* c, const void* P, int dtype, int64_t b, int64_t b
     return EF_OK;
   }
   int64_t pps = 0;
+  // one selector for every caller: the split form wherever it is eligible, else the fp32 kernel
+  bool split3 = !c->bf16 && c->opt_project_split_bf16 == 1 && c->split3_state >= 0 &&
+                project_split3_ok(dtype, P, c->d, c->kpw);
+  if (split3 && c->split3_state == 0) EF_TRY(split3_prepare(c));
+  split3 = split3 && c->split3_state == 1;
   const uint8_t* mu8 = c->mean_u8_ok ? static_cast<const uint8_t*>(c->mean_u8.p) : nullptr;
   const void* wf = c->w16f_ok ? c->W16f.p : nullptr;
-  const int ns = c->bf16 ? project_bf16_nsplit(dtype, P, mu8, wf, bpad, c->d, c->kpw, &pps)
-                         : project_nsplit(bpad, c->d, c->kpw, &pps);
+  const int ns = c->bf16  ? project_bf16_nsplit(dtype, P, mu8, wf, bpad, c->d, c->kpw, &pps)
+                 : split3 ? project_split3_nsplit(bpad, c->d, c->kpw, &pps)
+                          : project_nsplit(bpad, c->d, c->kpw, &pps);
   EF_TRY(ensure(c, c->proj_part, (size_t)ns * bpad * c->kpw * sizeof(float)));
   TimerEvt t;
   timer_begin(c, EF_KERNEL_PROJECT, &t);
-  if (c->bf16) {
+  if (split3) {
+    EF_HIP(c,
+           launch_project_split3(c->stream, P, b, bpad, c->d, static_cast<const uint8_t*>(c->mean_u8.p), c->W3f.p,
+                                 c->kpw, static_cast<float*>(c->proj_part.p), ns, pps),
+           "project kernel (split bf16)");
+  } else if (c->bf16) {
     EF_HIP(c,
            launch_project_bf16(c->stream, dtype, P, b, bpad, c->d, static_cast<const float*>(c->mean_r.p),
                                mu8, static_cast<const unsigned short*>(c->W16.p), wf,
@@ -355,7 +395,7 @@ static int project_dev(ef_ctx* c, const void* P, int dtype, int64_t b, int64_t b
   timer_end(c, &t);
   EF_HIP(c,
          launch_project_reduce(c->stream, static_cast<const float*>(c->proj_part.p), ns, b, bpad, c->kpw,
-                               c->k, c->kp, c->bf16 ? static_cast<const float*>(c->corr.p) : nullptr,
+                               c->k, c->kp, c->bf16 || split3 ? static_cast<const float*>(c->corr.p) : nullptr,
                                static_cast<float*>(dst->p), f_dev),
          "project reduce");
   return EF_OK;
@@ -727,6 +767,7 @@ int ef_model_set(ef_ctx* c, const float* mean, const float* W, int64_t d, int32_
     EF_HIP(c, hipStreamSynchronize(c->stream), "pad W");
   }
   c->mean_u8_ok = c->w16f_ok = false;
+  c->split3_state = 0;  // the pieces belonged to the old W
   if (bf16) {
     const int ldw = kpw;
     EF_TRY(ensure(c, c->W16, (size_t)ldw * d * sizeof(unsigned short)));
@@ -1264,6 +1305,10 @@ int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
       c->opt_search_prefix_split = value;
       c->der.reset();  // a clean guard; the compact copy is rebuilt in the new arithmetic's layout
       return EF_OK;
+    case EF_OPT_PROJECT_SPLIT_BF16:
+      if (value != 0 && value != 1) return set_err(c, EF_E_INVALID, "EF_OPT_PROJECT_SPLIT_BF16 must be 0 or 1");
+      c->opt_project_split_bf16 = value;  // read by the next projection; the pieces stay with the model
+      return EF_OK;
     case EF_OPT_SEARCH_TOPK_CAND:
       if (value < 16 || value > 4096) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_TOPK_CAND must be 16 .. 4096");
       c->opt_search_topk_cand = value;
@@ -1293,6 +1338,7 @@ int ef_get_option(const ef_ctx* c, int32_t option, int64_t* value) {
     case EF_OPT_SEARCH_PREFIX: *value = c->opt_search_prefix; return EF_OK;
     case EF_OPT_SEARCH_TOPK_CAND: *value = c->opt_search_topk_cand; return EF_OK;
     case EF_OPT_SEARCH_PREFIX_SPLIT: *value = c->opt_search_prefix_split; return EF_OK;
+    case EF_OPT_PROJECT_SPLIT_BF16: *value = c->opt_project_split_bf16; return EF_OK;
     default: return EF_E_INVALID;
   }
 }

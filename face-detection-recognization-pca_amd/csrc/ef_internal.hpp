@@ -462,6 +462,12 @@ struct ef_ctx {
   ef::DevBuf mean_u8;  // uint8[d] round(mean) (wide bf16 kernel) + int counter
   bool mean_u8_ok = false;  // every round(mean) in 0..255
   ef::DevBuf corr;     // float[kpw] (mean - round(mean)).W
+  // split form of an fp32 model (EF_OPT_PROJECT_SPLIT_BF16): built by the first projection that
+  // can use it (split3_prepare, ef_api.hip), dropped by ef_model_set; mean_u8 and corr above
+  // are then this model's
+  int64_t opt_project_split_bf16 = 1;
+  int split3_state = 0;  // 0 not built yet, 1 usable, -1 the guard ruled this model out
+  ef::DevBuf W3f;        // the hi, mid, lo bf16 pieces of W in MFMA-fragment order
 
   // gallery
   ef::Gallery gal;       // gal.k == 0: none set yet
@@ -764,6 +770,17 @@ hipError_t launch_project_bf16(hipStream_t s, int p_dtype, const void* P, int64_
 bool bf16_frag_supported(int64_t d, int ldw);
 hipError_t launch_bf16_frag(hipStream_t s, const unsigned short* Wt16, int64_t d, int ldw, void* Wf);
 hipError_t launch_mean_u8(hipStream_t s, const float* mean_r, int64_t d, uint8_t* out, int* bad);
+// split form of an fp32 model (EF_OPT_PROJECT_SPLIT_BF16; d % 64 == 0, ldw % 128 == 0): the three
+// bf16 pieces of W in fragment order (3 x 2 bytes per element), round(mean) as bytes, the correction
+// row; bad[0] / bad[1] count the W elements / mean entries for which the form is not exact
+bool split3_supported(int64_t d, int ldw);
+hipError_t launch_split3_model(hipStream_t s, const float* W, const float* mean, int64_t d, int ldw, void* Wf3,
+                               uint8_t* mean_u8, float* corr, double* corr_part, int nchunk, int* bad);
+bool project_split3_ok(int p_dtype, const void* P, int64_t d, int ldw);
+int project_split3_nsplit(int64_t bpad, int64_t d, int ldw, int64_t* pix_per_split);
+hipError_t launch_project_split3(hipStream_t s, const void* P, int64_t b, int64_t bpad, int64_t d,
+                                 const uint8_t* mean_u8, const void* Wf3, int ldw, float* part, int nsplit,
+                                 int64_t pps);
 
 // ---- back-projection (ef_recon.hip) ---------------------------------------------------
 // R is kept as [kp][recon_dpad(d)] (zero past k and past d).  recon_nsplit: pixel-axis splits of

@@ -331,7 +331,15 @@ __device__ __forceinline__ void frag_lds_barrier() { asm volatile("s_waitcnt lgk
 constexpr int kFragMeanLds = 16384;
 // NW = 4: a 256-thread workgroup (one wave per SIMD, 128 probes x 256 components at
 // NT = 256), two per CU, so one workgroup's barrier is covered by the other's MFMAs.
-template <int NT, int WK, bool ML, int NW = 8>
+// NP = 3 (fp32 models, EF_OPT_PROJECT_SPLIT_BF16): Wf holds the three bf16 pieces hi, mid,
+// lo of every fp32 W element (split3_frag_kernel), a k-step's three fragments adjacent; each
+// A fragment read from LDS feeds three MFMAs per column block into the same accumulator, so
+// LDS bytes and conversion work per MFMA are a third of NP = 1's.  Every product is exact
+// (an integer of at most 8 bits times an 8-bit significand); the only roundings are the
+// fp32 accumulator's.  The ring stays four entries of two fragments (32 VGPRs), an entry now
+// being one piece of a k-step: 8 MFMAs per entry and four entries of cover, as at NP = 1.
+constexpr int kSplitMeanLds = 2048;  // NP = 3: two 256-probe workgroups and their mean bytes fit one CU's LDS
+template <int NT, int WK, bool ML, int NW = 8, int NP = 1>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void project_bf16_frag_kernel(const uint8_t* __restrict__ P, int64_t b, int64_t d,
                                                                    const uint8_t* __restrict__ mean_u8,
                                                                    const uint4* __restrict__ Wf, int ldw,
@@ -346,10 +354,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void project_bf16_frag_ke
   constexpr int PT = RM * WK / NTH;    // pixels per thread per stage
   constexpr int TPR = WK / PT;         // threads per probe row
   constexpr int NV = PT / 16;          // uint4 of raw pixels per thread per stage
-  constexpr int RD = 4;                // B ring depth (k-steps in flight)
-  static_assert(NG * MG == NW && PT % 16 == 0 && TPR >= 1 && SUB % RD == 0, "frag tile");
+  constexpr int RD = 4;                // B ring depth (entries in flight: a k-step is NP entries)
+  static_assert(NG * MG == NW && PT % 16 == 0 && TPR >= 1 && (SUB * NP) % RD == 0, "frag tile");
+  static_assert(NP == 1 || NP == 3, "one bf16 W, or the three pieces of an fp32 W");
   __shared__ __attribute__((aligned(16))) unsigned short sA[2][RM * WS];
-  __shared__ __attribute__((aligned(16))) uint8_t sMean[ML ? kFragMeanLds : 16];
+  __shared__ __attribute__((aligned(16))) uint8_t sMean[ML ? (NP == 3 ? kSplitMeanLds : kFragMeanLds) : 16];
 
   // XCD-aware deal (as the wide kernel): XCD x takes the contiguous run of (split, m-tile,
   // n-tile) items [x * per, (x + 1) * per), split-major, so one K split's Wf slice streams
@@ -418,11 +427,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void project_bf16_frag_ke
   };
 
   // B fragments: wave columns ct0, ct0 + 1 (32 each); k-step g of this split is fragment
-  // row kb0 + g
+  // row kb0 + g.  NP = 3: a k-step is NP ring entries, its pieces hi, mid, lo in turn, so
+  // entry g = NP * (k-step) + piece is fragment (kb0 * NP + g) of the column block.
   const int64_t KB = d / 16;
   const int64_t ct0 = (col0 + ng * 64) / 32;
-  const uint4* wb0 = Wf + (ct0 * KB + k_beg / 16) * 64 + lane;
-  const uint4* wb1 = wb0 + KB * 64;
+  const uint4* wb0 = Wf + (ct0 * KB + k_beg / 16) * (64 * NP) + lane;
+  const uint4* wb1 = wb0 + KB * (64 * NP);
+  const int nent = nsub * NP;
   uint4 ring[RD][2];
   auto load_b = [&](int g, uint4* dst) {
     dst[0] = wb0[(int64_t)g * 64];
@@ -444,7 +455,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void project_bf16_frag_ke
   }
   load_raw(0, r0);
 #pragma unroll
-  for (int g = 0; g < RD; ++g) load_b(g < nsub ? g : nsub - 1, ring[g]);
+  for (int g = 0; g < RD; ++g) load_b(g < nent ? g : nent - 1, ring[g]);
   load_raw(nsteps > 1 ? 1 : 0, r1);
   convert_store(r0, 0, 0);
   frag_lds_barrier();
@@ -467,12 +478,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void project_bf16_frag_ke
     read_a(buf, 0, acur);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int s = 0; s < SUB; ++s) {  // lane (r, h) holds A[r][16s + 8h + j], B[16s + 8h + j][r]
-      if (s + 1 < SUB) read_a(buf, s + 1, anxt);
+    for (int t = 0; t < SUB * NP; ++t) {  // lane (r, h) holds A[r][16s + 8h + j], B[16s + 8h + j][r]
+      const int s = t / NP, q = t % NP;    // k-step and piece of ring entry t
+      if (q == 0 && s + 1 < SUB) read_a(buf, s + 1, anxt);
       // the next k-step's A reads issue before this k-step's MFMAs (8 MFMAs = 256 cycles of
       // cover for the LDS latency; the scheduler otherwise sank them below 7 of the 8)
       __builtin_amdgcn_sched_barrier(0);
-      const int slot = s % RD;
+      const int slot = t % RD;
       bf16x8 w0, w1;
       __builtin_memcpy(&w0, &ring[slot][0], 16);
       __builtin_memcpy(&w1, &ring[slot][1], 16);
@@ -481,10 +493,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void project_bf16_frag_ke
         acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acur[i], w0, acc[i][0], 0, 0, 0);
         acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(acur[i], w1, acc[i][1], 0, 0, 0);
       }
-      const int g = st * SUB + s + RD;
-      load_b(g < nsub ? g : nsub - 1, ring[slot]);
+      const int g = st * (SUB * NP) + t + RD;
+      load_b(g < nent ? g : nent - 1, ring[slot]);
       __builtin_amdgcn_sched_barrier(0);
-      if (s + 1 < SUB) {
+      if (q == NP - 1 && s + 1 < SUB) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) acur[i] = anxt[i];
       }
@@ -596,13 +608,119 @@ __global__ void mean_u8_kernel(const float* __restrict__ mean_r, int64_t d, uint
                                int* __restrict__ bad) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= d) return;
-  const float v = mean_r[i];
+  const float v = rintf(mean_r[i]);  // (the fp32 model's split form passes mean itself)
   if (!(v >= 0.f && v <= 255.f)) atomicAdd(bad, 1);
   out[i] = (uint8_t)fminf(fmaxf(v, 0.f), 255.f);
 }
 
 hipError_t launch_mean_u8(hipStream_t s, const float* mean_r, int64_t d, uint8_t* out, int* bad) {
   hipLaunchKernelGGL(mean_u8_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, mean_r, d, out, bad);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// Split form of an fp32 model (EF_OPT_PROJECT_SPLIT_BF16): w = hi + mid + lo, three bf16
+// pieces by round-to-nearest-even of the running remainder.
+//   Wf3[((ct * KB + kb) * 3 + q) * 64 + lane] (16 B) = piece q of
+//   W[16 kb + 8 (lane >> 5) .. + 8][32 ct + (lane & 31)]
+// (bf16_frag_kernel's order with a k-step's three pieces adjacent).  *bad counts the
+// elements for which the form would not be exact: w not finite, hi + mid + lo != w, or a
+// piece that is neither zero nor a normal number (the matrix cores flush bf16 subnormals).
+__global__ void split3_frag_kernel(const float* __restrict__ W, int64_t d, int ldw, int64_t total,
+                                   uint4* __restrict__ Wf3, int* __restrict__ bad) {
+  const int64_t KB = d / 16;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (int64_t)gridDim.x * blockDim.x) {
+    const int ln = (int)(idx & 63);
+    const int64_t rest = idx >> 6;
+    const int64_t kb = rest % KB, ct = rest / KB;
+    const float* src = W + (kb * 16 + 8 * (ln >> 5)) * ldw + ct * 32 + (ln & 31);
+    unsigned pc[3][8];
+    int nbad = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float w = src[(int64_t)j * ldw];
+      bool ok = (__float_as_uint(w) & 0x7f800000u) != 0x7f800000u;
+      float rem = ok ? w : 0.f;
+      double sum = 0.0;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const unsigned bits = bf16_bits(rem);
+        const float pf = __uint_as_float(bits << 16);
+        pc[q][j] = bits;
+        ok = ok && ((bits & 0x7f80u) != 0x7f80u) && ((bits & 0x7f80u) != 0u || (bits & 0x7fffu) == 0u);
+        sum += (double)pf;
+        rem -= pf;
+      }
+      ok = ok && sum == (double)w;
+      nbad += ok ? 0 : 1;
+    }
+    if (nbad) atomicAdd(bad, nbad);
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      Wf3[(rest * 3 + q) * 64 + ln] = make_uint4(pc[q][0] | (pc[q][1] << 16), pc[q][2] | (pc[q][3] << 16),
+                                                 pc[q][4] | (pc[q][5] << 16), pc[q][6] | (pc[q][7] << 16));
+  }
+}
+
+bool split3_supported(int64_t d, int ldw) { return d % 64 == 0 && ldw % 128 == 0; }
+
+// The pieces, round(mean) as bytes and the fp64-derived correction row of an fp32 model;
+// bad[0] counts the W elements, bad[1] the mean entries, that rule the form out.
+hipError_t launch_split3_model(hipStream_t s, const float* W, const float* mean, int64_t d, int ldw, void* Wf3,
+                               uint8_t* mean_u8, float* corr, double* corr_part, int nchunk, int* bad) {
+  if (!split3_supported(d, ldw)) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)(ldw / 32) * (d / 16) * 64;
+  hipLaunchKernelGGL(split3_frag_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65536)), dim3(256), 0,
+                     s, W, d, ldw, total, static_cast<uint4*>(Wf3), bad);
+  hipLaunchKernelGGL(mean_u8_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, s, mean, d, mean_u8, bad + 1);
+  const int64_t chunk = (d + nchunk - 1) / nchunk;
+  hipLaunchKernelGGL(bf16_corr_kernel, dim3((unsigned)nchunk, (unsigned)((ldw + 127) / 128)), dim3(128), 0, s, W,
+                     mean, d, ldw, chunk, corr_part);
+  hipLaunchKernelGGL(bf16_corr_sum_kernel, dim3((unsigned)((ldw + 127) / 128)), dim3(128), 0, s, corr_part, nchunk,
+                     ldw, corr);
+  return hipGetLastError();
+}
+
+// uint8 probes on 16-byte aligned rows (d % 64 == 0 makes every row as aligned as the first)
+bool project_split3_ok(int p_dtype, const void* P, int64_t d, int ldw) {
+  return p_dtype == EF_U8 && split3_supported(d, ldw) && (reinterpret_cast<uintptr_t>(P) & 15) == 0;
+}
+
+// Split-form launch shape: 256 probes x 128 components per workgroup of four waves (each 128
+// x 64), 64-pixel stages, ldw / 128 column tiles; K splits for one workgroup per CU.  Two per
+// CU (the kernel's registers and LDS allow it) doubles the splits and the slab bytes (67 MB
+// against 33 MB at 4096 probes x 16384 pixels x 128) and measured 0.065 against 0.061 ms there.
+constexpr int kSplitRM = 256, kSplitWK = 64, kSplitPerCu = 1;
+
+// A pure function of (padded batch, d, ldw), as project_nsplit.
+int project_split3_nsplit(int64_t bpad, int64_t d, int ldw, int64_t* pix_per_split) {
+  const int64_t wsteps = d / kSplitWK;
+  const int64_t tiles = (bpad + kSplitRM - 1) / kSplitRM * (ldw / 128);
+  int64_t ns = (256 * kSplitPerCu + tiles - 1) / tiles;  // every CU busy
+  // a split's round(mean) bytes live in the kernel's LDS: at most kSplitMeanLds pixels per split
+  if (ns < (d + kSplitMeanLds - 1) / kSplitMeanLds) ns = (d + kSplitMeanLds - 1) / kSplitMeanLds;
+  if (ns > wsteps) ns = wsteps;
+  if (ns < 1) ns = 1;
+  while ((tiles * ns) % 8 != 0 && ns < wsteps) ++ns;  // an even deal over the XCDs
+  const int64_t steps_per = (wsteps + ns - 1) / ns;
+  *pix_per_split = steps_per * kSplitWK;
+  return (int)((d + *pix_per_split - 1) / *pix_per_split);
+}
+
+hipError_t launch_project_split3(hipStream_t s, const void* P, int64_t b, int64_t bpad, int64_t d,
+                                 const uint8_t* mean_u8, const void* Wf3, int ldw, float* part, int nsplit,
+                                 int64_t pps) {
+  if (!split3_supported(d, ldw) || pps % kSplitWK != 0 || pps > kSplitMeanLds ||
+      (reinterpret_cast<uintptr_t>(P) & 15) != 0)
+    return hipErrorInvalidValue;
+  const int nt = ldw / 128;
+  const int mt = (int)((bpad + kSplitRM - 1) / kSplitRM);
+  const int grid = (mt * nt * nsplit + 7) / 8 * 8;
+  const uint8_t* p8 = static_cast<const uint8_t*>(P);
+  const uint4* wf = static_cast<const uint4*>(Wf3);
+  hipLaunchKernelGGL((project_bf16_frag_kernel<128, kSplitWK, true, 4, 3>), dim3((unsigned)grid), dim3(256), 0, s, p8,
+                     b, d, mean_u8, wf, ldw, part, bpad, pps, mt, nt, nsplit);
   return hipGetLastError();
 }
 

@@ -44,6 +44,7 @@ EF_OPT_HOST_THREADS = 10
 EF_OPT_SEARCH_PREFIX = 11
 EF_OPT_SEARCH_TOPK_CAND = 12
 EF_OPT_SEARCH_PREFIX_SPLIT = 13
+EF_OPT_PROJECT_SPLIT_BF16 = 14
 EF_TOPK_MAX = 64  # most ranks of a top-m search
 EF_LABEL_SAME, EF_LABEL_OTHER, EF_LABEL_ANY = 0, 1, 2  # ef_search_labelled relations
 EF_CENSUS_MAX_BINS = 2048  # most bins of ef_score_census

@@ -95,7 +95,8 @@ _OPTIONS = {"fit_max_iters": N.EF_OPT_FIT_MAX_ITERS, "fit_fp32_coarse": N.EF_OPT
             "search_split_bf16": N.EF_OPT_SEARCH_SPLIT_BF16, "jpeg_part_files": N.EF_OPT_JPEG_PART_FILES,
             "fit_chebyshev": N.EF_OPT_FIT_CHEBYSHEV, "host_threads": N.EF_OPT_HOST_THREADS,
             "search_prefix": N.EF_OPT_SEARCH_PREFIX, "search_topk_cand": N.EF_OPT_SEARCH_TOPK_CAND,
-            "search_prefix_split": N.EF_OPT_SEARCH_PREFIX_SPLIT}
+            "search_prefix_split": N.EF_OPT_SEARCH_PREFIX_SPLIT,
+            "project_split_bf16": N.EF_OPT_PROJECT_SPLIT_BF16}
 
 
 def host_cpu_share():
@@ -308,7 +309,8 @@ class Engine:
         """Context tunable (include/eigenface.h EF_OPT_*): "fit_max_iters",
         "fit_fp32_coarse", "cov_slab_bytes", "tm_int64_sums", "haar_ordered", "jpeg_chunk_bits",
         "search_split_bf16", "jpeg_part_files", "fit_chebyshev", "host_threads" (process-wide),
-        "search_prefix", "search_topk_cand", "search_prefix_split" or the code."""
+        "search_prefix", "search_topk_cand", "search_prefix_split", "project_split_bf16" or the
+        code."""
         self._chk(self._lib.ef_set_option(self._h, _option(option), int(value)))
 
     def get_option(self, option):

@@ -651,6 +651,25 @@ int ef_comm_info(const ef_ctx* ctx, int32_t* nranks, int32_t* rank);
                                       chain's wider bound; 0: the fp32 scan.  Results are the same;
                                       the compact copy (n x K1 x 4 B + 8 n B either way) is rebuilt
                                       on the next search after a change */
+#define EF_OPT_PROJECT_SPLIT_BF16 14 /* projection of uint8 probes with an fp32 model (added by symbol,
+                                      EF_API_VERSION stays 7).  1 [default]: where eligible (uint8
+                                      probes on a 16-byte aligned pointer, d % 64 == 0, more than 64
+                                      padded components, a model without EF_MODEL_BF16 that passes
+                                      the guard) the projection runs on bf16 MFMA as
+                                      (p - round(mean)).(W_hi + W_mid + W_lo) - (mean - round(mean)).W:
+                                      the three bf16 pieces sum to the fp32 W exactly and
+                                      p - round(mean) is an integer of at most 8 bits, so no input
+                                      is rounded and only the fp32 accumulation rounds; the
+                                      correction row is computed in fp64 once per model.  The guard,
+                                      run once per model on the device: every W element finite and
+                                      equal to the sum of its pieces, every piece zero or a normal
+                                      bf16, every round(mean) in 0..255; a model that fails it, and
+                                      every ineligible call, takes the fp32 kernel.  The pieces
+                                      (6 B per padded W element) are built by the first eligible
+                                      projection after ef_model_set.  Features differ from option
+                                      0's in their last bits (as between two batch sizes) and
+                                      repeat bit for bit from call to call.  0: always the fp32
+                                      kernel */
 int ef_set_option(ef_ctx* ctx, int32_t option, int64_t value);
 int ef_get_option(const ef_ctx* ctx, int32_t option, int64_t* value);
 
