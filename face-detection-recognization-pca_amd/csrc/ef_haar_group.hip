@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "ef_haar.hpp"
+#include "ef_union_find.hpp"
 
 namespace ef {
 
@@ -83,27 +84,6 @@ __device__ __forceinline__ bool similar_rects(const int4 a, const int4 b) {
          (double)abs(a.x + a.z - b.x - b.z) <= delta && (double)abs(a.y + a.w - b.y - b.w) <= delta;
 }
 
-__device__ __forceinline__ int parent_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The root of x's chain, at most n links away, or -1 at the bound.  halve: shorten the chain
-// on the way (a non-root never becomes a root again and any ancestor is a valid parent, so the
-// store races with nothing that matters).
-template <bool HALVE>
-__device__ __forceinline__ int group_find(int* parent, int x, int n) {
-  for (int s = 0; s <= n; ++s) {
-    const int p = parent_load(parent + x);
-    if (p == x) return x;
-    if (HALVE) {
-      const int gp = parent_load(parent + p);
-      if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    x = p;
-  }
-  return -1;
-}
-
 __global__ __launch_bounds__(256) void haar_group_union_kernel(const int* __restrict__ ncount, int maxc, HaarGroupWs ws) {
   __shared__ int4 sr[256];
   const int n = group_count(ncount, maxc);
@@ -119,23 +99,9 @@ __global__ __launch_bounds__(256) void haar_group_union_kernel(const int* __rest
   for (int jj = 0; jj < m; ++jj) {
     const int j = j0 + jj;
     if (j <= i || !similar_rects(ri, sr[jj])) continue;
-    int a = i, b = j;
-    bool done = false;
-    for (int it = 0; it < 2 * n + 2 && !done; ++it) {
-      a = group_find<true>(ws.parent, a, n);
-      b = group_find<true>(ws.parent, b, n);
-      if (a < 0 || b < 0) break;
-      if (a == b) {
-        done = true;
-        break;
-      }
-      const bool a_low = ws.key[a] < ws.key[b];
-      const int lo = a_low ? a : b, hi = a_low ? b : a;
-      done = atomicCAS(ws.parent + hi, hi, lo) == hi;  // hi was still a root: linked below lo
-      a = lo;
-      b = hi;
-    }
-    if (!done) atomicOr(ws.count + 1, EF_HAAR_SCAN_UNCONVERGED);
+    const u64* const key = ws.key;
+    if (!group_union(ws.parent, i, j, n, [key](int a, int b) { return key[a] < key[b]; }))
+      atomicOr(ws.count + 1, EF_HAAR_SCAN_UNCONVERGED);
   }
 }
 

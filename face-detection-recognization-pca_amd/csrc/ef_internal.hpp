@@ -41,7 +41,7 @@ inline int proj_pad(int kp) { return kp <= 64 ? 64 : (kp + 127) / 128 * 128; }
 constexpr int kSearchProbeTile = 256;   // probes per search workgroup (4 waves x 64)
 constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
-constexpr int kTimers = 12;             // EF_KERNEL_* ids (include/eigenface.h)
+constexpr int kTimers = 13;             // EF_KERNEL_* ids (include/eigenface.h)
 constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
 // What gallery_aux_kernel reports of a gallery's rows (ef_search_common.hpp scan_regular)
 constexpr unsigned kRowNotFinite = 1;   // a row whose fp32 ||g||^2 is +inf or NaN
@@ -479,6 +479,7 @@ struct ef_ctx {
   ef::DevBuf glabels;   // int32[gal.n]
   ef::DevBuf label_ws;  // per-call scratch of ef_search_labelled: int[2][bpad], then the host call's staging
                         // (ef_score_census: int[2][bpad], float[bpad] probe norms, the staging, the counts)
+  ef::DevBuf cluster_ws;  // per-call scratch of ef_gallery_cluster (ef_cluster.hip): O(n)
   ef::GalleryDerived der;  // the split and prefix copies and the prefix guard (search_copies)
   int64_t opt_search_prefix = 1;
   int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32

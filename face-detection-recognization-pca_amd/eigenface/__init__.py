@@ -16,6 +16,8 @@ from .evaluate import (OpenSetRates, compare_subspaces, equal_error_threshold, e
 from .evaluate import (VerificationRates, auc, compare_verification, d_prime, pair_equal_error,  # noqa: F401
                        score_census, tar_at_fmr, verification_rates)
 from .fisher import Fisherfaces  # noqa: F401
+from .cluster import (ClusterResult, cluster_faces, cluster_gallery, cluster_schedule, pair_confusion,  # noqa: F401
+                      pairwise_scores)
 from .pca import (  # noqa: F401
     EigenfacePCA,
     get_engine,
@@ -44,4 +46,5 @@ __all__ = [
     "Fisherfaces", "LdaResult", "compare_subspaces",
     "score_census", "VerificationRates", "verification_rates", "pair_equal_error", "tar_at_fmr", "auc", "d_prime",
     "compare_verification",
+    "ClusterResult", "cluster_gallery", "cluster_faces", "cluster_schedule", "pair_confusion", "pairwise_scores",
 ]

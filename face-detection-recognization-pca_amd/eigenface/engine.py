@@ -1026,6 +1026,51 @@ class Engine:
                                                 N.EF_MEM_DEVICE if dev else 0))
         return counts
 
+    # ------------------------------------------------------- gallery clustering
+    def cluster_gallery(self, threshold, metric="l2", min_samples=1, degree=False, labels=None):
+        """ef_gallery_cluster: group the resident gallery's rows by identity without labels.  Rows
+        i != j are linked when their fp64 squared distance is <= ``threshold`` (l2) or their fp64
+        cosine similarity is >= ``threshold`` (cosine), every edge decided as in fp64; the result
+        is the connected components, numbered by their lowest member row.  ``min_samples`` > 1
+        adds DBSCAN's density floor (noise rows get -1).
+
+        Returns ``(labels int32 (n,), degree int32 (n,) or None, info int64 (4,))`` with info =
+        (clusters, noise rows, linked unordered pairs, pairs settled in fp64).  Host outputs are
+        numpy arrays.  With ``labels`` a caller's int32 device tensor of shape (n,) (and ``degree``
+        either a bool or such a tensor) the outputs are device tensors and the call is
+        stream-ordered without a host wait; bit EF_CLUSTER_UNCONVERGED of info[3] then reports
+        what a host call raises."""
+        mt = _metric(metric)
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("threshold must not be NaN")
+        if self.gallery_k is None:
+            raise RuntimeError("no gallery: call set_gallery first")
+        n = self.gallery_n
+        dev = labels is not None
+        if dev:
+            import torch
+            if not _is_dev(labels):
+                raise TypeError("labels must be a device tensor (host outputs are returned as new arrays)")
+            self._dev_out(labels, (n,), torch.int32, "labels")
+            if _is_dev(degree):
+                self._dev_out(degree, (n,), torch.int32, "degree")
+            elif degree is not None and not isinstance(degree, (bool, np.bool_)):
+                raise TypeError("degree must be a bool or an int32 device tensor")
+            else:
+                degree = torch.empty(n, dtype=torch.int32, device=labels.device) if degree else None
+            info = torch.empty(4, dtype=torch.int64, device=labels.device)
+        else:
+            if _is_dev(degree):
+                raise ValueError("a degree tensor needs a labels tensor too")
+            labels = np.empty(n, np.int32)
+            degree = np.empty(n, np.int32) if degree else None
+            info = np.zeros(4, np.int64)
+        with self._order(dev, labels, degree, info):
+            self._chk(self._lib.ef_gallery_cluster(self._h, mt, threshold, int(min_samples), _ptr(labels), _ptr(degree),
+                                                   _ptr(info), N.EF_MEM_DEVICE if dev else 0))
+        return labels, degree, info
+
     # ------------------------------------------------------------- top-m search
     def _topk_m(self, m):
         m = int(m)
@@ -1757,7 +1802,7 @@ class Engine:
                "ingest": N.EF_KERNEL_INGEST, "haar": N.EF_KERNEL_HAAR, "jpeg": N.EF_KERNEL_JPEG,
                "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST, "scan": N.EF_KERNEL_SCAN,
                "recon": N.EF_KERNEL_RECON, "recon_reduce": N.EF_KERNEL_RECON_REDUCE,
-               "haar_scan": N.EF_KERNEL_HAAR_SCAN}[kernel]
+               "haar_scan": N.EF_KERNEL_HAAR_SCAN, "cluster": N.EF_KERNEL_CLUSTER}[kernel]
         ms = C.c_double(0)
         n = C.c_int64(0)
         self._chk(self._lib.ef_timing_get(self._h, kid, C.byref(ms), C.byref(n)))

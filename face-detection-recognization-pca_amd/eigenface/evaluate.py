@@ -329,6 +329,15 @@ def compare_verification(pca_features, fisher_features, labels, metric="l2", fmr
     return out
 
 
+def clustering_agreement(labels_true, labels_pred):
+    """How well a clustering (``cluster_gallery``'s labels; -1 = noise, each a cluster of its own)
+    recovers known identities: the integer pair counts and pair precision, recall and F1
+    (``cluster.pair_confusion`` / ``pairwise_scores``; host arithmetic, no GPU)."""
+    from .cluster import pair_confusion, pairwise_scores
+    tp, fp, fn, tn = pair_confusion(labels_true, labels_pred)
+    return {"tp": tp, "fp": fp, "fn": fn, "tn": tn, **pairwise_scores(labels_true, labels_pred)}
+
+
 def evaluate_model(model_data, metric="cosine", device=0, keys=None):
     """Leave-one-out evaluation of a model dict holding ``face_features`` (n, k) and
     ``face_labels`` (n,) — the face_model.pkl layout (train-v4.py:210-222).  Returns

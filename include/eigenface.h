@@ -419,6 +419,63 @@ int ef_score_census(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric,
                     float lo, float hi, int32_t nbins,
                     int64_t* counts /* [2][nbins + 3] */, uint32_t flags);
 
+/* ------------------------------------------------- gallery clustering (labels for unlabelled rows)
+ * Added by symbol (EF_API_VERSION stays 7).  Groups the rows of the resident gallery by identity
+ * without labels: a self-join that links every pair of rows within a threshold and returns the
+ * connected components.  It produces what ef_gallery_labels, ef_score_census and ef_lda_* take,
+ * and the list of near-duplicate rows.  The distance GEMM is the census's; its epilogue joins the
+ * linked pairs in a bounded lock-free union-find instead of binning scores.  No n x n array of any
+ * kind is written.
+ *
+ * Linked: rows i != j with fp64 squared distance <= threshold (L2), or fp64 cosine similarity
+ *   >= threshold (cosine; a zero row scores 0 against everything), both computed from the fp32
+ *   features as stored, as ef_keys_decode shows them.  A pair whose fp32 scan score is not finite
+ *   (a NaN or +-inf component in either row, fp32 squares that overflow under L2) is never linked:
+ *   such rows are clusters of their own, or noise under a density floor.
+ * Guarantee: inside the scan's domain (ef_score_census's: fp32 max |g|^2 in [2^-80, 2^126 / 3.02],
+ *   for cosine also no non-zero row with |g|^2 < 2^-80 and no row with a non-finite norm) every
+ *   edge is decided as in fp64.  The fp32 scan score s^ decides alone when |s^ - threshold| >
+ *   delta; a pair inside the band is re-scored in fp64 by a whole wave and decided on that.  With
+ *   u = 2^-24 and kp the padded k, delta is ef_score_census's bound without its bin-index term,
+ *   taken per call at |q|, |g| <= max|g| and |s| <= 4 max|g|^2, plus the rounding of the threshold
+ *   to fp32:
+ *     L2      delta = 2 [(kp + 4) u 1.01 (3 max|g|^2) + 16 u max|g|^2] + |fp32(t) - t|
+ *     cosine  delta = 2 (kp + 12) u 1.01 + |fp32(t) - t|
+ *   Outside the domain delta is +inf: every pair with a finite scan score is decided in fp64
+ *   (correct, and slow).  The components of an exactly decided graph do not depend on the order in
+ *   which its edges arrive, and every count is an integer: the same input gives the same outputs
+ *   on every run.
+ * min_samples (DBSCAN's density floor): <= 1 gives plain connected components.  Otherwise a row is
+ *   core when degree + 1 >= min_samples; only core-core pairs are joined; a non-core row linked
+ *   to a core row takes the cluster of its lowest-index linked core row; a non-core row linked to
+ *   none is noise.
+ * Outputs (rows are local rows of this context's shard):
+ *   labels[n]  the cluster of each row, clusters numbered 0 .. by their lowest member row (under
+ *              a density floor: by their lowest core row); -1 for noise.
+ *   degree[n]  optional (NULL): the number of other rows linked to each row.
+ *   info[4]    {clusters, noise rows, linked unordered pairs, pairs settled in fp64}, all exact.
+ * Termination: every union-find walk is cut at n links and every union at 2 n + 2 attempts;
+ *   nothing waits for another workgroup.  A walk that reached its bound (never seen: the forest is
+ *   acyclic by construction) makes a host call return EF_E_NUMERIC after its synchronisation;
+ *   with EF_MEM_DEVICE it sets the bit EF_CLUSTER_UNCONVERGED of info[3].
+ * n = 0 is EF_OK with info all zero.  EF_E_STATE: no gallery; a communicator of more than one rank
+ *   attached.  EF_E_INVALID: a NaN threshold, an unknown metric, labels or info NULL, more than
+ *   2^31 - 129 rows.  With EF_MEM_DEVICE every pointer is a device pointer and the call does not
+ *   wait (and reads nothing back to size anything).  Every k of ef_search is supported.  Memory:
+ *   O(n) (six 4-byte values per row).  ef_timing_get: EF_KERNEL_CLUSTER.
+ *
+ * ef_cluster_schedule: the link pass's work items for n rows of padded length kp, on the host (no
+ *   context, no device): n_items triples {first row tile, end row tile, probe tile} of 128-row
+ *   tiles, of which up to max_items are written.  Every unordered tile pair (row tile <= probe
+ *   tile) belongs to exactly one item.  EF_E_INVALID for n < 0 or kp not a positive multiple of 16. */
+#define EF_KERNEL_CLUSTER 12 /* everything one ef_gallery_cluster queues */
+#define EF_CLUSTER_UNCONVERGED ((int64_t)1 << 62)
+int ef_gallery_cluster(ef_ctx* ctx, int32_t metric, double threshold, int32_t min_samples,
+                       int32_t* labels /* [n] */, int32_t* degree /* [n] or NULL */,
+                       int64_t* info /* [4] */, uint32_t flags);
+int ef_cluster_schedule(int64_t n, int32_t kp, int64_t* items_out /* [max_items][3] */, int32_t max_items,
+                        int32_t* n_items);
+
 /* ------------------------------------------------- Fisher discriminant (Fisherfaces)
  * Added by symbol (EF_API_VERSION stays 7).  A linear discriminant inside face space
  * (Belhumeur, Hespanha, Kriegman 1997): from features F[n][k] (EF_F32 / EF_F64; a fit's
