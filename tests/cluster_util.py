@@ -1,7 +1,8 @@
 """numpy reference of the gallery clustering (ef_gallery_cluster): fp64 pair scores from the fp32
 features, the threshold graph, components by a plain union-find, the density rule with the
 lowest-index core attachment, canonical numbering, and delta from the formula in
-include/eigenface.h (never from the kernel's output)."""
+include/eigenface.h (never from the kernel's output).  For galleries too large for an n x n
+array: an integer lattice whose exact answer comes from a dict of its occupied points."""
 import numpy as np
 
 U = 2.0 ** -24
@@ -105,8 +106,10 @@ def reference(g, metric, t, min_samples=1, scores=None, gram=False):
     return labels, degree, info
 
 
-def delta(g, metric, scores=None):
-    """The header's bound without the bin-index term, at the gallery's own maxima (q = g)."""
+def delta(g, metric, scores=None, from_norms=False):
+    """The header's bound without the bin-index term, at the gallery's own maxima (q = g).
+    ``from_norms``: |s| <= 4 max|g|^2 stands in for the largest pair score (the call's own form),
+    so that no n x n array is needed."""
     g64 = np.asarray(g, np.float32).astype(np.float64)
     kp = kp_of(g64.shape[1])
     if metric != "l2":
@@ -115,8 +118,11 @@ def delta(g, metric, scores=None):
         sq = (g64 * g64).sum(axis=1)
     sq = sq[np.isfinite(sq)]
     gm2 = float(sq.max(initial=0.0))
-    s = pair_scores(g, metric) if scores is None else scores
-    smax = float(np.abs(s[np.isfinite(s)]).max(initial=0.0))
+    if from_norms:
+        smax = 4.0 * gm2
+    else:
+        s = pair_scores(g, metric) if scores is None else scores
+        smax = float(np.abs(s[np.isfinite(s)]).max(initial=0.0))
     return 2.0 * ((kp + 4) * U * 1.01 * (2.0 * gm2 + gm2) + 4.0 * U * smax)
 
 
@@ -145,3 +151,122 @@ def blobs(n, k, ncls, seed, spread=4.0):
     centres = spread * rng.standard_normal((ncls, k))
     g = (centres[cls] + rng.standard_normal((n, k))).astype(np.float32)
     return g, cls.astype(np.int32)
+
+
+# ------------------------------------------------------------------ the lattice gallery
+def lattice(n, k, seed, ngroups=None):
+    """Integer-valued fp32 rows (n, k >= 8) whose threshold graph is known without an n x n array.
+    Coordinates 0 .. 5 hold the base-8 digits of the row's group id as 4 digit + 1, coordinates
+    6 and 7 are 0 or 1, the rest are the constant 3; the groups (n // 3 distinct random ids unless
+    ``ngroups`` says otherwise) are dealt to the rows at random, so a group's members lie in
+    tiles far apart.  Squared distances are exact integers in fp32: 0, 1, 1 or 2 inside a group,
+    at least 16 between groups."""
+    assert k >= 8
+    rng = np.random.default_rng(seed)
+    ngroups = max(1, n // 3) if ngroups is None else ngroups
+    ids = rng.choice(8 ** 6, ngroups, replace=False)[rng.integers(0, ngroups, n)]
+    g = np.full((n, k), 3.0, np.float32)
+    for c in range(6):
+        g[:, c] = 4 * ((ids >> (3 * c)) & 7) + 1
+    g[:, 6:8] = rng.integers(0, 2, (n, 2))
+    return g
+
+
+def _row_keys(p):
+    """One bytes object per row of the 2-D integer array p."""
+    p = np.ascontiguousarray(p)
+    return p.view(np.dtype((np.void, p.shape[1] * p.itemsize))).ravel().tolist()
+
+
+def lattice_cells(g):
+    """The occupied points of an integer-valued gallery: (cell of each row, rows of each cell in
+    ascending order, pairs (c, c2) of occupied cells one unit step apart, each once).  A dict
+    from point to cell; the 2 k unit neighbours of a cell are looked up in it."""
+    p = np.rint(np.asarray(g, np.float64)).astype(np.int32)
+    assert (p == g).all() and np.abs(p).max() < 2 ** 11  # integers; |g|^2 and every partial sum exact in fp32
+    index, members = {}, []
+    cell = np.empty(p.shape[0], np.int64)
+    for i, key in enumerate(_row_keys(p)):
+        c = index.setdefault(key, len(members))
+        if c == len(members):
+            members.append([])
+        members[c].append(i)
+        cell[i] = c
+    pts = p[[m[0] for m in members]]
+    steps = []
+    for j in range(p.shape[1]):  # the neighbour one step up in coordinate j; the step down is its mirror
+        up = pts.copy()
+        up[:, j] += 1
+        for c, key in enumerate(_row_keys(up)):
+            c2 = index.get(key)
+            if c2 is not None:
+                steps.append((c, c2))
+    return cell, members, np.array(steps, np.int64).reshape(-1, 2)
+
+
+def lattice_reference(g, min_samples=1, unit_steps=True):
+    """(labels int32, degree int32, info int64[3]) as ``reference`` gives them for L2 at t = 1.0 on
+    an integer-valued gallery, in O(n k): two rows link iff they are the same point or one unit
+    step apart.  ``unit_steps`` False: only rows at the same point link (the duplicates)."""
+    cell, members, steps = lattice_cells(g)
+    if not unit_steps:
+        steps = steps[:0]
+    n, m = cell.shape[0], len(members)
+    occ = np.array([len(r) for r in members], np.int64)
+    first = np.array([r[0] for r in members], np.int64)
+    around = np.zeros(m, np.int64)  # rows in the cells one step away
+    np.add.at(around, steps[:, 0], occ[steps[:, 1]])
+    np.add.at(around, steps[:, 1], occ[steps[:, 0]])
+    cdeg = occ - 1 + around  # every row of a cell has the cell's degree
+    ccore = cdeg + 1 >= min_samples if min_samples > 1 else np.ones(m, bool)
+    parent = np.arange(m)
+
+    def find(c):
+        while parent[c] != c:
+            parent[c] = parent[parent[c]]
+            c = parent[c]
+        return c
+    for a, b in steps:
+        if ccore[a] and ccore[b]:
+            ra, rb = find(a), find(b)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+    comp = np.array([find(c) for c in range(m)])
+    lowest = np.full(m, n, np.int64)  # by component: its lowest core row
+    np.minimum.at(lowest, comp[ccore], first[ccore])
+    # a non-core cell: its rows take the cluster of the lowest core row one step away (the rows
+    # at its own point are non-core like itself)
+    nearest = np.full(m, n, np.int64)
+    for a, b in ((0, 1), (1, 0)):
+        ok = ccore[steps[:, b]] & ~ccore[steps[:, a]]
+        np.minimum.at(nearest, steps[ok, a], first[steps[ok, b]])
+    croot = np.where(ccore, lowest[comp], -1)
+    att = ~ccore & (nearest < n)
+    croot[att] = lowest[comp[cell[nearest[att]]]]
+    final = croot[cell]
+    core_roots = np.unique(lowest[comp[ccore]])
+    labels = canonical(final, core_roots)
+    links = int((occ * (occ - 1) // 2).sum() + (occ[steps[:, 0]] * occ[steps[:, 1]]).sum())
+    info = np.array([core_roots.size, int((final < 0).sum()), links], np.int64)
+    return labels, cdeg[cell].astype(np.int32), info
+
+
+def lattice_unit_pairs(g):
+    """Unordered row pairs at squared distance exactly 1."""
+    _, members, steps = lattice_cells(g)
+    occ = np.array([len(r) for r in members], np.int64)
+    return int((occ[steps[:, 0]] * occ[steps[:, 1]]).sum())
+
+
+def max_cosine_between_points(g, block=1024):
+    """The largest fp64 cosine similarity of two rows that are not the same point, block by block
+    over the distinct points (never an n x n array)."""
+    pts = np.unique(np.asarray(g, np.float64), axis=0)
+    u = pts / np.sqrt((pts * pts).sum(axis=1))[:, None]
+    best = -1.0
+    for a in range(0, u.shape[0], block):
+        c = u[a:a + block] @ u[a:].T  # the upper triangle is enough
+        r = np.arange(c.shape[0])
+        c[r, r] = -1.0  # a point with itself
+        best = max(best, float(c.max()))
+    return best

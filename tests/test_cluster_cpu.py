@@ -188,3 +188,57 @@ def test_reference_density_rule():
         d2 = (x - x[r]) ** 2
         nb = np.flatnonzero((d2 <= 0.96 ** 2) & core & (np.arange(10) != r))
         assert lab[r] == lab[nb[0]]
+
+
+# ------------------------------------------------------------------ the lattice and its hash reference
+@pytest.mark.parametrize("min_samples", (1, 3, 5))
+@pytest.mark.parametrize("n,k", ((700, 16), (701, 40)))
+def test_lattice_reference_equals_the_dense_reference(n, k, min_samples):
+    g = cu.lattice(n, k, n + k)
+    s = cu.pair_scores(g, "l2")
+    v = cu.upper(s)
+    assert (s == np.rint(s)).all() and set(np.unique(v[v < 16])) == {0.0, 1.0, 2.0}
+    dense = cu.reference(g, "l2", 1.0, min_samples, s)
+    lab, deg, info = dense
+    core = deg + 1 >= min_samples
+    assert (np.bincount(lab[lab >= 0]) > 1).any()  # clusters of several rows
+    if min_samples > 1:
+        assert (~core & (lab >= 0)).any() and (lab < 0).any() and info[1] > 0  # attached rows, noise rows
+    assert cu.lattice_unit_pairs(g) == int((v == 1.0).sum())
+    for got, want in zip(cu.lattice_reference(g, min_samples), dense):
+        assert got.dtype == want.dtype
+        np.testing.assert_array_equal(got, want)
+    # the duplicates alone: the graph of score 0
+    for got, want in zip(cu.lattice_reference(g, min_samples, unit_steps=False),
+                         cu.reference(g, "l2", 0.0, min_samples, s)):
+        np.testing.assert_array_equal(got, want)
+
+
+def test_max_cosine_between_points_equals_the_dense_maximum():
+    g = cu.lattice(700, 16, 716)
+    s = cu.pair_scores(g, "cosine")
+    apart = cu.pair_scores(g, "l2") > 0
+    assert cu.max_cosine_between_points(g, block=64) == pytest.approx(s[apart].max(), abs=1e-15)
+    assert (s[~apart] >= 1 - 1e-15).all()
+
+
+# the large galleries of test_gpu_cluster.py: (n, k)
+LATTICE_SIZES = ((11530, 16), (11530, 40), (65836, 16))
+
+
+@pytest.mark.parametrize("n,k", LATTICE_SIZES)
+def test_large_lattices_reach_items_of_several_tiles(n, k):
+    """What test_gpu_cluster.py relies on at these sizes, from the planner alone."""
+    tiles = (n + 127) // 128
+    assert n % 128 != 0
+    # the link pass: an item of two or more row tiles that holds its own diagonal tile, not first
+    t0, t1, pt = ec.cluster_schedule(n, cu.kp_of(k)).T
+    assert int((t1 - t0).max()) == max(1, tiles * (tiles + 1) // 2 // 2048) >= 2
+    late_diagonal = (t1 - t0 >= 2) & (pt > t0) & (pt < t1)
+    assert late_diagonal.any() and (t0[late_diagonal] > 0).any()
+    # the count pass sweeps the full square (cluster_tiles_per_item(tiles, true) restated): the
+    # ragged last tile is a later tile of its item
+    tpc = min(tiles, max(1, tiles * tiles // 2048))
+    assert tpc >= 2 and (tiles - 1) % tpc != 0
+    # the label scan carries a running total between rounds of 256 blocks of 256 rows
+    assert ((n + 255) // 256 > 256) == (n == 65836)

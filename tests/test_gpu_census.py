@@ -206,6 +206,155 @@ def test_bracketed_counts(eng, k, n, b, metric):
             _assert_bracket(got, s, masks, lo, hi, nbins, delta)
 
 
+# ------------------------------------------- 2b. work items ("chunks") of several tiles
+# Every case above runs one gallery tile per work item, and test_one_bin_past_32_bits, which does
+# not, repeats one row and labels i % 2, so all its tiles are alike.  Here the planner gives two
+# tiles per item, the last item ends on a 5-row tile, and rows, norms and labels differ from tile
+# to tile.  The references are built over blocks of probes: no b x n array is held.
+CHUNK_N, CHUNK_B = 4229, 8192
+
+
+def _assert_chunk_plan(n, b):
+    """launch_census's plan restated: tiles per work item, and where the ragged tile falls."""
+    n_ptiles = (b + 127) // 128
+    tiles = (n + 127) // 128
+    want = max(1, (2048 + n_ptiles - 1) // n_ptiles)
+    tpc = (tiles + min(want, tiles) - 1) // min(want, tiles)
+    assert tiles > want and tpc >= 2
+    assert n % 128 != 0 and (tiles - 1) % tpc != 0  # the ragged last tile is a later tile of its item
+    return tpc
+
+
+def _assert_tiles_differ(g, glab):
+    """A value taken from the tile before or after is another value, for labels and norms alike."""
+    sq = (np.asarray(g, np.float64) ** 2).sum(1)
+    assert (glab[:-128] != glab[128:]).mean() > 0.5
+    assert (sq[:-128] != sq[128:]).mean() > 0.9
+    with np.errstate(divide="raise"):
+        assert (1 / np.sqrt(sq[:-128]) != 1 / np.sqrt(sq[128:])).mean() > 0.9
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_integer_ref(k):
+    """counts[2][nbins + 3] by np.bincount on the exact integer scores, 512 probes at a time."""
+    n, b = CHUNK_N, CHUNK_B
+    g, q, glab, plab, excl = integer_case(k, n, b)
+    top, per_block = 0, []
+    for a in range(0, b, 512):
+        s = lu.score_matrix(q[a:a + 512], g, "l2")
+        si = np.rint(s).astype(np.int64)
+        assert (s == si).all() and si.min() >= 0 and si.max() < 2 ** 23  # every fp32 partial sum is an exact integer
+        top = max(top, int(si.max()))
+        per_block.append((si, _sides(glab, plab[a:a + 512], excl[a:a + 512], n)))
+    # 2048 bins from -0.5 on, of the smallest width 2^j that holds every score: the edges are
+    # half-integers, no score lies on one, and (score + 0.5) / width is exact in fp32
+    nbins, width = 2048, 1
+    while top >= nbins * width:
+        width *= 2
+    ref = np.zeros((2, nbins + 3), np.int64)
+    for si, masks in per_block:
+        slot = si // width + 1
+        for side, m in enumerate(masks):
+            ref[side] += np.bincount(slot[m], minlength=nbins + 3)
+    ref.setflags(write=False)
+    return ref, nbins, width
+
+
+@pytest.mark.parametrize("k", (16, 40))
+def test_chunks_of_several_tiles(eng, k):
+    n, b = CHUNK_N, CHUNK_B
+    assert _assert_chunk_plan(n, b) == 2 and n - 33 * 128 == 5 and _kp(k) // 16 == (1 if k == 16 else 4)
+    g, q, glab, plab, excl = integer_case(k, n, b)
+    _assert_tiles_differ(g, glab)
+    assert (plab == ABSENT).any() and not (glab == ABSENT).any()
+    assert (excl < 0).any() and (excl >= n).any() and ((excl >= 0) & (excl < n)).any()
+    ref, nbins, width = chunk_integer_ref(k)
+    assert ref.sum() == b * n - ((excl >= 0) & (excl < n)).sum()
+    assert ((ref[:, 1:nbins + 1] > 0).sum(axis=1) > 40).all()  # both sides spread over many bins
+    rng_ = (-0.5, -0.5 + nbins * width)
+    _load(eng, g, glab)
+    got = eng.score_census(q, plab, excl, "l2", nbins, rng_)
+    assert got.dtype == np.int64 and got.shape == (2, nbins + 3)
+    np.testing.assert_array_equal(got, ref)
+    np.testing.assert_array_equal(eng.score_census(q, plab, excl, "l2", nbins, rng_), got)
+
+
+def _bracket_bounds(blocks, lo, hi, nbins, delta):
+    """_assert_bracket's reference side over blocks of (scores, (genuine mask, impostor mask)):
+    per side the number of pairs, of pairs within delta of an edge, and per edge the pairs below
+    edge - delta and below edge + delta."""
+    edges = lo + (hi - lo) * np.arange(nbins + 1) / nbins
+    assert 2 * delta < (hi - lo) / nbins  # the intervals around the edges are disjoint
+    marks = np.stack([edges - delta, edges + delta], axis=1).ravel()  # ascending
+    assert (np.diff(marks) > 0).all()
+    size, near, below = np.zeros(2, np.int64), np.zeros(2, np.int64), np.zeros((2, marks.size + 1), np.int64)
+    for s, masks in blocks:
+        for side, m in enumerate(masks):
+            v = s[m]
+            c = np.searchsorted(marks, v, side="right")  # marks at or below the score
+            size[side] += v.size
+            below[side] += np.bincount(c, minlength=marks.size + 1)
+            # |v - e| <= delta: from e - delta on (c odd) or on e + delta itself
+            near[side] += ((c % 2 == 1) | (v == marks[np.maximum(c, 1) - 1])).sum()
+    cum = np.cumsum(below, axis=1)[:, :-1]  # pairs with score < marks[i] (c <= i)
+    return size, near, cum[:, 0::2], cum[:, 1::2]
+
+
+def _assert_bracket_bounds(got, bounds, nbins):
+    size, near, lower, upper = bounds
+    for side in range(2):
+        assert got[side].sum() == size[side] and got[side, nbins + 2] == 0
+        below = np.cumsum(got[side])[:nbins + 1]  # binned below edge j: slots 0 .. j
+        bad = (below < lower[side]) | (below > upper[side])
+        assert not bad.any(), f"side {side}: edges {np.flatnonzero(bad)[:5]} outside the bracket: " \
+                              f"{below[bad][:5]} not in [{lower[side][bad][:5]}, {upper[side][bad][:5]}]"
+
+
+def test_bracket_bounds_equal_assert_brackets_own():
+    """The blockwise bounds are _assert_bracket's: equal on a case small enough for both."""
+    k, n, b, nbins = 16, 1000, 257, 64
+    g, glab = real_case(k, n)
+    s = real_scores(k, n, b, "cosine")
+    masks = _sides(glab, glab[:b], None, n)
+    lo, hi = _real_range(s, "cosine", nbins)
+    delta = 1e-3  # wide enough that pairs fall within it
+    blocks = [(s[a:a + 100], tuple(m[a:a + 100] for m in masks)) for a in range(0, b, 100)]
+    size, near, lower, upper = _bracket_bounds(blocks, lo, hi, nbins, delta)
+    edges = lo + (hi - lo) * np.arange(nbins + 1) / nbins
+    for side, m in enumerate(masks):
+        v = np.sort(s[m])
+        want_near = np.zeros(v.shape, bool)
+        for e in edges:
+            want_near |= np.abs(v - e) <= delta
+        assert size[side] == v.size and near[side] == want_near.sum() > 0
+        np.testing.assert_array_equal(lower[side], np.searchsorted(v, edges - delta, side="left"))
+        np.testing.assert_array_equal(upper[side], np.searchsorted(v, edges + delta, side="left"))
+
+
+def test_chunks_of_several_tiles_cosine(eng):
+    """The same plan on real-valued features under cosine, where the rows' 1 / |g| are read from
+    the aux slot in the epilogue: the guarantee's bracket, its bounds built block by block."""
+    k, n, b, nbins = 16, CHUNK_N, CHUNK_B, 64
+    assert _assert_chunk_plan(n, b) == 2
+    feats, labs = real_case(k, n + b)  # one set of class centres: the gallery, then the probes
+    g, glab, q, plab = feats[:n], labs[:n], feats[n:], labs[n:]
+    _assert_tiles_differ(g, glab)
+    excl = _excl(np.random.default_rng(k + n + b), n, b)
+    lo, hi = -1.0625, 1.0625
+    delta = _delta(k, q, g, None, lo, hi, "cosine")
+    blocks = ((-lu.score_matrix(q[a:a + 512], g, "cosine"), _sides(glab, plab[a:a + 512], excl[a:a + 512], n))
+              for a in range(0, b, 512))
+    bounds = _bracket_bounds(blocks, lo, hi, nbins, delta)
+    size, near = bounds[:2]
+    assert (size > 0).all() and size.sum() == b * n - ((excl >= 0) & (excl < n)).sum()
+    assert (near <= 0.02 * size).all(), near / size  # _assert_bracket's cap, before the GPU is asked
+    assert ((bounds[3] - bounds[2]).max(axis=1) > 0).all() or near.sum() == 0
+    _load(eng, g, glab)
+    got = eng.score_census(q, plab, excl, "cosine", nbins, (lo, hi))
+    _assert_bracket_bounds(got, bounds, nbins)
+    np.testing.assert_array_equal(eng.score_census(q, plab, excl, "cosine", nbins, (lo, hi)), got)
+
+
 # ------------------------------------------------ 3. contention and 64-bit accumulation
 def _one_vector(eng, k, n, b, metric, nbins, rng_, slot, excl):
     v = np.arange(1, k + 1, dtype=np.float32) % 5 - 2  # small integers: every sum is exact

@@ -368,3 +368,135 @@ def test_larger_gallery(eng):
     ref = cu.reference(g, "l2", t, 1, s)
     assert ref[2][0] == 64
     _check(_run(eng, g, "l2", t), ref)
+
+
+# ------------------------------------------------------------------ work items of several tiles
+# Below n = 11521 every link item is one row tile, and below n = 65537 the label scan is one
+# round.  The lattice of cluster_util has its exact answer from a dict of points in O(n k), so
+# the sizes past those lines need no n x n reference.
+LINE = 65536  # rows in one round of cluster_scan_kernel: 256 blocks of 256
+
+
+def _plan(n):
+    """(row tiles, tiles per link item, tiles per count item): cluster_tiles_per_item restated."""
+    tiles = (n + 127) // 128
+    return tiles, min(tiles, max(1, tiles * (tiles + 1) // 2 // 2048)), min(tiles, max(1, tiles * tiles // 2048))
+
+
+def _differs_from_tile_to_tile(x):
+    """An input condition: a per-row value taken from the tile before or after is another value."""
+    assert (x[:-128] != x[128:]).mean() > 0.9
+
+
+def _run_device(eng, t, metric, min_samples, n):
+    """The device-tensor form on the resident gallery, as host arrays."""
+    import torch
+    lab = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    deg = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+    l2, d2, info = eng.cluster_gallery(t, metric, min_samples, degree=deg, labels=lab)
+    assert l2 is lab and d2 is deg and info.is_cuda and info.dtype == torch.int64
+    return tuple(x.cpu().numpy() for x in (lab, deg, info))
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_case(n, k):
+    g = cu.lattice(n, k, n + k)
+    if n > LINE:
+        # three whole clusters of the min_samples = 4 reference go behind the line, so that
+        # their roots lie there at every min_samples
+        lab = cu.lattice_reference(g, 4)[0]
+        sizes = np.bincount(lab[lab >= 0])
+        rows = np.flatnonzero(np.isin(lab, np.flatnonzero((sizes >= 4) & (sizes <= 8))[-3:]))
+        tail = np.arange(n - rows.size, n)
+        src, dst = np.setdiff1d(rows, tail), np.setdiff1d(tail, rows)
+        g[np.concatenate([src, dst])] = g[np.concatenate([dst, src])]
+    # scores 0 and 2 are decided by the fp32 scan, score 1 = t lies inside the band
+    assert cu.delta(g, "l2", from_norms=True) < 0.5
+    _differs_from_tile_to_tile((g.astype(np.float64) ** 2).sum(axis=1))
+    _freeze(g)
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_ref(n, k, min_samples, unit_steps=True):
+    ref = cu.lattice_reference(lattice_case(n, k), min_samples, unit_steps)
+    lab, deg, info = ref
+    assert 1 < info[0] < n and info[2] > n // 8 and (np.bincount(lab[lab >= 0]) > 1).any()
+    if min_samples > 1:
+        core = deg + 1 >= min_samples
+        assert info[1] > 0 and (~core).any() and core.any()
+        assert (~core & (lab >= 0)).any() or not unit_steps  # rows attached to a core row of another point
+    _freeze(*ref)
+    return ref
+
+
+@pytest.mark.parametrize("min_samples", (1, 4))
+@pytest.mark.parametrize("k", (16, 40))
+def test_link_items_of_several_tiles(eng, k, min_samples):
+    """n = 11530: 91 row tiles with 10 rows in the last.  The link pass takes two row tiles per
+    item (the diagonal tile second in items with t0 > 0), the count pass four, its last item
+    ending on the ragged tile.  k = 16 is one slice per tile, k = 40 (kp = 64) four."""
+    n = 11530
+    assert _plan(n) == (91, 2, 4) and n - 90 * 128 == 10 and cu.kp_of(k) // 16 == (1 if k == 16 else 4)
+    g = lattice_case(n, k)
+    ref = lattice_ref(n, k, min_samples)
+    got = _run(eng, g, "l2", 1.0, min_samples)
+    _check(got, ref)
+    assert got[2][3] >= cu.lattice_unit_pairs(g)  # the pairs at t itself are settled in fp64
+    dev = _run_device(eng, 1.0, "l2", min_samples, n)
+    for x, y in zip(dev, got):
+        assert x.tobytes() == y.tobytes()
+
+
+@functools.lru_cache(maxsize=None)
+def cosine_threshold(n, k):
+    """Midway between 1 and the largest cosine of two rows that are not the same point: then
+    exactly the duplicates link."""
+    g = lattice_case(n, k)
+    top = cu.max_cosine_between_points(g)
+    half = 0.5 * (1.0 - top)
+    assert half > 4 * cu.delta(g, "cosine"), (half, cu.delta(g, "cosine"))
+    return 1.0 - half
+
+
+@pytest.mark.parametrize("min_samples", (1, 2))
+@pytest.mark.parametrize("k", (16, 40))
+def test_link_items_of_several_tiles_cosine(eng, k, min_samples):
+    """The same plan under cosine, where the rows' 1 / |g| are read from the aux slot in the
+    epilogue: only rows at the same point link."""
+    n = 11530
+    assert _plan(n) == (91, 2, 4)
+    g = lattice_case(n, k)
+    with np.errstate(divide="raise"):
+        _differs_from_tile_to_tile(1.0 / np.sqrt((g.astype(np.float64) ** 2).sum(axis=1)))
+    t = cosine_threshold(n, k)
+    ref = lattice_ref(n, k, min_samples, False)
+    got = _run(eng, g, "cosine", t, min_samples)
+    _check(got, ref)
+    if k == 16:
+        dev = _run_device(eng, t, "cosine", min_samples, n)
+        for x, y in zip(dev, got):
+            assert x.tobytes() == y.tobytes()
+
+
+@pytest.mark.parametrize("min_samples", (1, 4))
+def test_label_scan_carries_past_256_blocks(eng, min_samples):
+    """n = 65836: 258 blocks of 256 rows, so cluster_scan_kernel runs a second round on the
+    running total of the first; 515 row tiles, 64 per link item and 129 per count item."""
+    n, k = 65836, 16
+    assert (n + 255) // 256 == 258 and _plan(n) == (515, 64, 129)
+    g = lattice_case(n, k)
+    ref = lattice_ref(n, k, min_samples)
+    lab, deg, info = ref
+    core = deg + 1 >= min_samples
+    roots = np.full(info[0], n, np.int64)  # by cluster: its lowest core row
+    np.minimum.at(roots, lab[core], np.flatnonzero(core))
+    assert (np.diff(roots) > 0).all()  # numbered in the order of their roots
+    assert 3 <= (roots >= LINE).sum() < info[0]  # roots whose number needs the carry
+    behind = lab[LINE:]
+    assert (roots[behind[behind >= 0]] < LINE).any() and (roots[behind[behind >= 0]] >= LINE).any()
+    if min_samples > 1:
+        assert (lab[:LINE] < 0).any() and (behind < 0).any()  # noise on both sides
+    got = _run(eng, g, "l2", 1.0, min_samples)
+    _check(got, ref)
+    assert got[2][3] >= cu.lattice_unit_pairs(g)
