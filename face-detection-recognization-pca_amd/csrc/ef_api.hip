@@ -472,7 +472,7 @@ int Results::fetch(ef_ctx* c) const {
 
 // b probe features Q[b][k of the gallery] (host, or device with dev) into ctx->q_pad, padded
 // to bpad rows of the gallery's kp
-static int stage_queries(ef_ctx* c, const float* Q, int64_t b, bool dev, int64_t bpad) {
+int stage_queries(ef_ctx* c, const float* Q, int64_t b, bool dev, int64_t bpad) {
   const Gallery& g = c->gal;
   EF_TRY(ensure(c, c->q_pad, (size_t)bpad * g.kp * sizeof(float)));
   if (!dev) {

@@ -41,7 +41,7 @@ inline int proj_pad(int kp) { return kp <= 64 ? 64 : (kp + 127) / 128 * 128; }
 constexpr int kSearchProbeTile = 256;   // probes per search workgroup (4 waves x 64)
 constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
-constexpr int kTimers = 13;             // EF_KERNEL_* ids (include/eigenface.h)
+constexpr int kTimers = 14;             // EF_KERNEL_* ids (include/eigenface.h)
 constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
 // What gallery_aux_kernel reports of a gallery's rows (ef_search_common.hpp scan_regular)
 constexpr unsigned kRowNotFinite = 1;   // a row whose fp32 ||g||^2 is +inf or NaN
@@ -480,6 +480,7 @@ struct ef_ctx {
   ef::DevBuf label_ws;  // per-call scratch of ef_search_labelled: int[2][bpad], then the host call's staging
                         // (ef_score_census: int[2][bpad], float[bpad] probe norms, the staging, the counts)
   ef::DevBuf cluster_ws;  // per-call scratch of ef_gallery_cluster (ef_cluster.hip): O(n)
+  ef::DevBuf range_ws;    // per-call scratch of ef_search_range (ef_range.hip): O(b chunks), then a host call's staging
   ef::GalleryDerived der;  // the split and prefix copies and the prefix guard (search_copies)
   int64_t opt_search_prefix = 1;
   int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32
@@ -580,6 +581,9 @@ SearchPlan search_plan(int64_t bpad, int64_t n, int kp, bool s3, int tile_rows =
 // rows per tile of the prefix scan at prefix length k1 (split: the split-bf16 scan)
 int prefix_tile_rows(int k1, bool split);
 std::vector<SearchPiece> search_pieces(int64_t b, int kp);
+// b probe features Q[b][k of the gallery] (host, or device with dev) into ctx->q_pad, padded to
+// bpad rows of the gallery's kp
+int stage_queries(ef_ctx* c, const float* Q, int64_t b, bool dev, int64_t bpad);
 // Top-1 search of one piece.  sp: the scan's variant (0 fp32; 1 split 16x16x32; 2 split 32x32x16;
 // 3 single-bf16 screen, wide k only — split_variant above) with the copies that match it.  The
 // sequence: the probes' copy into sp.Q3 (variant != 0 at kp > 128), then the timed main scan,

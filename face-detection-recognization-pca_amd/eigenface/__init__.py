@@ -18,6 +18,7 @@ from .evaluate import (VerificationRates, auc, compare_verification, d_prime, pa
 from .fisher import Fisherfaces  # noqa: F401
 from .cluster import (ClusterResult, cluster_faces, cluster_gallery, cluster_schedule, pair_confusion,  # noqa: F401
                       pairwise_scores)
+from .neighbors import (RangeResult, label_votes, merge_range, radius_neighbors, search_range_plan)  # noqa: F401
 from .pca import (  # noqa: F401
     EigenfacePCA,
     get_engine,
@@ -47,4 +48,5 @@ __all__ = [
     "score_census", "VerificationRates", "verification_rates", "pair_equal_error", "tar_at_fmr", "auc", "d_prime",
     "compare_verification",
     "ClusterResult", "cluster_gallery", "cluster_faces", "cluster_schedule", "pair_confusion", "pairwise_scores",
+    "RangeResult", "radius_neighbors", "merge_range", "label_votes", "search_range_plan",
 ]

@@ -29,6 +29,7 @@ EF_KERNEL_SCAN = 8
 EF_KERNEL_RECON, EF_KERNEL_RECON_REDUCE = 9, 10
 EF_KERNEL_HAAR_SCAN = 11
 EF_KERNEL_CLUSTER = 12
+EF_KERNEL_RANGE = 13
 EF_CLUSTER_UNCONVERGED = 1 << 62  # ef_gallery_cluster: bit of info[3] on a device call
 EF_HAAR_GROUP_MAX = 16384  # rectangles per grouping; the ceiling of a Haar scan plan's max_candidates
 EF_HAAR_SCAN_OVERFLOW, EF_HAAR_SCAN_UNCONVERGED = 0x1, 0x2  # ef_haar_scan_head.status bits
@@ -160,6 +161,9 @@ _SIGS = {
     # gallery clustering: added the same way
     "ef_gallery_cluster": ([vp, i32, C.c_double, i32, vp, vp, vp, u32], C.c_int),
     "ef_cluster_schedule": ([i64, i32, vp, i32, C.POINTER(i32)], C.c_int),
+    # range search: added the same way
+    "ef_search_range": ([vp, vp, i64, i32, C.c_double, vp, vp, vp, vp, i64, vp, u32], C.c_int),
+    "ef_search_range_plan": ([i64, i64, i32, C.POINTER(i64), C.POINTER(i64)], C.c_int),
     # model bank: added after API v7 without a version bump, so bound (and checked) by symbol
     "ef_bank_clear": ([vp], C.c_int),
     "ef_bank_add": ([vp, vp, vp, i64, i32, vp, i64, u32, C.POINTER(i32)], C.c_int),

@@ -1071,6 +1071,91 @@ class Engine:
                                                    _ptr(info), N.EF_MEM_DEVICE if dev else 0))
         return labels, degree, info
 
+    # ------------------------------------------------------------- range search
+    def _range_call(self, q, qp, b, dev, mt, threshold, ex, exp, cap, rows, scores):
+        """One ef_search_range on prepared probes: (lims, info); rows / scores of ``cap`` entries are
+        the caller's (None with cap 0: the count-only form)."""
+        device = q.device if dev else None
+        lims = _empty(b + 1, np.int64, device)
+        info = _empty(4, np.int64, device)
+        with self._order(dev, q, ex, lims, rows, scores, info):
+            self._chk(self._lib.ef_search_range(self._h, qp, b, mt, threshold, exp, _ptr(lims), _ptr(rows),
+                                                _ptr(scores), cap, _ptr(info), N.EF_MEM_DEVICE if dev else 0))
+        return lims, info
+
+    def _range_args(self, Q, threshold, metric, exclude_rows):
+        mt = _metric(metric)
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("threshold must not be NaN")
+        if self.gallery_k is None:
+            raise RuntimeError("no gallery: call set_gallery first")
+        q, qp, _, b, dev = self._probes(Q, pixels=False)
+        ex, exp = _per_probe(exclude_rows, np.int64, "exclude_rows", q, dev)
+        return mt, threshold, q, qp, b, dev, ex, exp
+
+    def search_range(self, Q, threshold, metric="l2", exclude_rows=None, max_results=None, out=None):
+        """ef_search_range: for each probe ALL resident rows within ``threshold`` (fp64 squared
+        distance <= threshold for l2, fp64 cosine similarity >= threshold for cosine, every
+        membership decided as in fp64), as a ``RangeResult``: ``lims`` int64 (b + 1,), ``rows`` int64
+        global row indices ascending inside each probe's segment, ``scores`` float32, ``info`` int64
+        (4,) = (hits, pairs settled in fp64, hits not written, 0).  The pair of probe p with the row
+        of global index ``exclude_rows[p]`` is left out (negative: nothing).
+
+        Host arrays in, numpy arrays out; device tensors in, device tensors out, stream-ordered as
+        score_census.  ``max_results`` is the capacity of rows / scores (``out``: the caller's
+        (rows, scores) device tensors, whose length is then the capacity): one call that never
+        waits on the device route; a probe's segment is written only when it fits whole
+        (``lims[p + 1] <= capacity``), and ``complete`` of a device result is None until the caller
+        reads ``lims[-1]``.  With ``max_results`` None the capacity starts at 16 hits per probe and
+        at least 65 536 (a policy, not a measurement); when ``lims[-1]`` exceeds it the call is made
+        once more with exactly ``lims[-1]``.  Reading ``lims[-1]`` is one host wait on the device
+        route, the only one."""
+        from .neighbors import RangeResult
+        mt, threshold, q, qp, b, dev, ex, exp = self._range_args(Q, threshold, metric, exclude_rows)
+        device = q.device if dev else None
+        if out is not None:
+            if not dev:
+                raise ValueError("out is for device input; host input returns new arrays")
+            import torch
+            rows, scores = out
+            cap = int(rows.shape[0])
+            self._dev_out(rows, (cap,), torch.int64, "out[0] (rows)")
+            self._dev_out(scores, (cap,), torch.float32, "out[1] (scores)")
+        else:
+            cap = max(16 * b, 65536) if max_results is None else int(max_results)
+            if cap < 0:
+                raise ValueError("max_results must not be negative")
+            rows, scores = _empty(cap, np.int64, device), _empty(cap, np.float32, device)
+        lims, info = self._range_call(q, qp, b, dev, mt, threshold, ex, exp, cap, rows, scores)
+        if max_results is None and out is None:
+            total = int(lims[-1])  # the documented wait of the device route
+            if total > cap:
+                cap = total
+                rows, scores = _empty(cap, np.int64, device), _empty(cap, np.float32, device)
+                lims, info = self._range_call(q, qp, b, dev, mt, threshold, ex, exp, cap, rows, scores)
+            rows, scores = rows[:total], scores[:total]
+        elif not dev:
+            written = int(info[0] - info[2]) if cap > 0 else 0
+            rows, scores = rows[:written], scores[:written]
+        return RangeResult(lims, rows, scores, info, "l2" if mt == N.EF_METRIC_L2 else "cosine", cap)
+
+    def search_range_counts(self, Q, threshold, metric="l2", exclude_rows=None):
+        """The count-only form of search_range (one pass of the kernel, nothing but ``lims`` and
+        ``info`` written): ``(counts int64 (b,), info int64 (4,))`` with counts = the hits of each
+        probe and info[0] their total.  Host arrays in, numpy out; device tensors in, device tensors
+        out without a host wait."""
+        mt, threshold, q, qp, b, dev, ex, exp = self._range_args(Q, threshold, metric, exclude_rows)
+        lims, info = self._range_call(q, qp, b, dev, mt, threshold, ex, exp, 0, None, None)
+        return lims[1:] - lims[:-1], info
+
+    def recognize_range(self, P, threshold, metric="l2", exclude_rows=None, max_results=None, out=None):
+        """Projection of the pixels P (b, d) with the resident model, then search_range on the
+        features.  A device input stays on the device."""
+        if self.model_k is None or self.gallery_k is None:
+            raise RuntimeError("recognize needs a model and a gallery")
+        return self.search_range(self.project(P), threshold, metric, exclude_rows, max_results, out)
+
     # ------------------------------------------------------------- top-m search
     def _topk_m(self, m):
         m = int(m)
@@ -1802,7 +1887,7 @@ class Engine:
                "ingest": N.EF_KERNEL_INGEST, "haar": N.EF_KERNEL_HAAR, "jpeg": N.EF_KERNEL_JPEG,
                "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST, "scan": N.EF_KERNEL_SCAN,
                "recon": N.EF_KERNEL_RECON, "recon_reduce": N.EF_KERNEL_RECON_REDUCE,
-               "haar_scan": N.EF_KERNEL_HAAR_SCAN, "cluster": N.EF_KERNEL_CLUSTER}[kernel]
+               "haar_scan": N.EF_KERNEL_HAAR_SCAN, "cluster": N.EF_KERNEL_CLUSTER, "range": N.EF_KERNEL_RANGE}[kernel]
         ms = C.c_double(0)
         n = C.c_int64(0)
         self._chk(self._lib.ef_timing_get(self._h, kid, C.byref(ms), C.byref(n)))

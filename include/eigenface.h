@@ -476,6 +476,73 @@ int ef_gallery_cluster(ef_ctx* ctx, int32_t metric, double threshold, int32_t mi
 int ef_cluster_schedule(int64_t n, int32_t kp, int64_t* items_out /* [max_items][3] */, int32_t max_items,
                         int32_t* n_items);
 
+/* ------------------------------------------------- range search (every row within a threshold)
+ * Added by symbol (EF_API_VERSION stays 7).  For each probe, ALL rows of the resident gallery
+ * within a threshold (scikit-learn's radius_neighbors, faiss's range_search), as a CSR list.  The
+ * distance GEMM is the census's over the census's work items; its epilogue decides membership as
+ * ef_gallery_cluster decides a link, with a probe in place of the second row.  Two passes of one
+ * kernel: the first counts, a scan turns the counts into offsets, the second writes.  No b x n
+ * array of any kind is written.
+ *
+ * A hit: a pair (probe p, resident row r) with fp64 squared distance <= threshold (L2), or fp64
+ *   cosine similarity >= threshold (cosine; a zero row or a zero probe scores 0), both computed
+ *   from the fp32 features as stored.  Never a hit: a pair whose fp32 scan score is not finite (a
+ *   NaN or +-inf component on either side, fp32 squares that overflow under L2); the pair of p
+ *   with the row whose global index is exclude_rows[p] (a negative entry, one outside the shard or
+ *   a NULL array excludes nothing: ef_score_census's rule).
+ * Guarantee: inside the scan's domain (fp32 max |g|^2 in [2^-80, 2^126] together with
+ *   2.02 |q| max|g|; for cosine also no non-zero row with |g|^2 < 2^-80, no row with a non-finite
+ *   norm, and a probe that is zero or has |q|^2 >= 2^-80) every membership is decided as in fp64.
+ *   The fp32 scan score s^ decides alone when |s^ - fp32(t)| > delta_p; a pair inside the band is
+ *   re-scored in fp64 by a whole wave and decided on that.  delta_p is taken per probe (a lane of
+ *   the kernel owns its probe), from ef_score_census's bound without its bin-index term, with
+ *   |s| <= (|q| + max|g|)^2, plus the rounding of the threshold to fp32.  With u = 2^-24, kp the
+ *   padded k, |q| the probe's Euclidean norm and max|g| the gallery's largest:
+ *     L2      delta_p = 2 [(kp + 4) u 1.01 (2 |q| max|g| + max|g|^2) + 4 u (|q| + max|g|)^2]
+ *                       + |fp32(t) - t|
+ *     cosine  delta_p = 2 (kp + 12) u 1.01 + |fp32(t) - t|
+ *   (the kernel widens it by 0.1 % for its own roundings of |q| and max|g|).  Outside the domain
+ *   delta_p is +inf: every pair with a finite scan score is decided in fp64 (correct, and slow).
+ * Outputs:
+ *   lims[b + 1]  probe p's hits are entries lims[p] .. lims[p + 1] - 1 of rows / scores;
+ *                lims[0] = 0 and lims[b] is the exact total.  Always written in full, whatever cap.
+ *   rows[cap]    GLOBAL row indices (local row + the gallery's global offset), ascending inside
+ *                each segment.
+ *   scores[cap]  scores[i] belongs to rows[i]: s^ for a pair the scan decided alone, (float) of
+ *                the fp64 score for a pair settled in the band.  Every reported score is within
+ *                delta_p of the pair's fp64 score and on the accepting side of fp32(t).
+ *   info[4]      {total hits, pairs settled in fp64 (by the counting pass), hits not written for
+ *                lack of capacity, 0}, all exact.
+ * Capacity: a segment is written only when it fits whole, lims[p + 1] <= cap (these segments are a
+ *   prefix of the probes); nothing is ever written at or past rows[cap] / scores[cap].  rows == NULL
+ *   or cap == 0 is the count-only form: one pass, only lims and info are written (info[2] is then
+ *   the total).  Overflow is no error: compare lims[b] with cap and call again.
+ * Determinism: every position is a function of exactly decided memberships and every count is an
+ *   integer sum, so the output is byte-identical on every run and between the host and the
+ *   EF_MEM_DEVICE form.
+ * b = 0 is EF_OK (lims[0] = 0); an empty gallery is EF_OK with lims and info all zero.
+ *   EF_E_STATE: no gallery; a communicator of more than one rank attached (search each shard on a
+ *   context of its own; the segments of shards in ascending offset order concatenate).
+ *   EF_E_INVALID: a NaN threshold, an unknown metric, lims or info NULL, cap < 0, rows without
+ *   scores, more than 2^31 - 129 rows.  With EF_MEM_DEVICE every pointer is a device pointer, the
+ *   call is stream-ordered and it never waits or reads anything back to size anything.  Every k of
+ *   ef_search is supported.  Memory beside the padded probes: O(b chunks) (4 bytes per probe and
+ *   gallery chunk; a host call also stages its outputs).  ef_timing_get: EF_KERNEL_RANGE.
+ *
+ * ef_search_range_plan: the work items of a call with b probes, n rows and padded length kp, on
+ *   the host (no context, no device): the gallery's 128-row tiles are cut into n_chunks chunks of
+ *   tiles_per_item tiles (the last chunk may be shorter); a work item is one chunk against one tile
+ *   of 128 probes (b padded to a multiple of 256).  Both are 0 for b = 0 or n = 0.  EF_E_INVALID for
+ *   b < 0, n < 0 or beyond 2^31 - 129, kp not a positive multiple of 16, or a NULL output. */
+#define EF_KERNEL_RANGE 13 /* everything one ef_search_range queues */
+int ef_search_range(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric, double threshold,
+                    const int64_t* exclude_rows /* [b] or NULL */,
+                    int64_t* lims /* [b + 1] */,
+                    int64_t* rows /* [cap] or NULL */,
+                    float* scores /* [cap] or NULL */,
+                    int64_t cap, int64_t* info /* [4] */, uint32_t flags);
+int ef_search_range_plan(int64_t b, int64_t n, int32_t kp, int64_t* n_chunks, int64_t* tiles_per_item);
+
 /* ------------------------------------------------- Fisher discriminant (Fisherfaces)
  * Added by symbol (EF_API_VERSION stays 7).  A linear discriminant inside face space
  * (Belhumeur, Hespanha, Kriegman 1997): from features F[n][k] (EF_F32 / EF_F64; a fit's
