@@ -948,6 +948,7 @@ int ef_gallery_set(ef_ctx* c, const float* G, int64_t n, int32_t k, int64_t offs
   (void)hipSetDevice(c->device);
   c->der.reset();  // the copies and the guard's history belong to the gallery they were made from
   c->has_labels = false;  // and so do the row labels (ef_gallery_labels)
+  c->rank_map_valid = false;  // and their dense class map (ef_search_rank)
   release(c->glabels);
   DevBuf staging;
   EF_TRY(gallery_load(c, c->gal, G, n, k, flags, staging, &c->gmax2_host, &c->gal_rows_host));
@@ -962,6 +963,7 @@ int ef_gallery_labels(ef_ctx* c, const int32_t* labels, int64_t n, uint32_t flag
   if (!labels) {  // drop them, once no queued search reads them any more
     EF_HIP(c, hipStreamSynchronize(c->stream), "sync");
     c->has_labels = false;
+    c->rank_map_valid = false;
     release(c->glabels);
     return EF_OK;
   }
@@ -978,6 +980,7 @@ int ef_gallery_labels(ef_ctx* c, const int32_t* labels, int64_t n, uint32_t flag
   EF_HIP(c, hipStreamSynchronize(c->stream), "copy labels");  // also: nothing queued reads the old ones
   c->glabels = std::move(nb);
   c->has_labels = true;
+  c->rank_map_valid = false;  // ef_search_rank rebuilds its class map from the new labels
   return EF_OK;
 }
 
@@ -1313,6 +1316,10 @@ int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
       if (value < 16 || value > 4096) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_TOPK_CAND must be 16 .. 4096");
       c->opt_search_topk_cand = value;
       return EF_OK;
+    case EF_OPT_RANK_BITMAP_BYTES:
+      if (value < 1) return set_err(c, EF_E_INVALID, "EF_OPT_RANK_BITMAP_BYTES must be >= 1");
+      c->opt_rank_bitmap_bytes = value;
+      return EF_OK;
     case EF_OPT_HOST_THREADS:
       if (value < 0 || value > 256) return set_err(c, EF_E_INVALID, "EF_OPT_HOST_THREADS must be 0..256");
       g_host_threads.store((int)value, std::memory_order_relaxed);
@@ -1339,6 +1346,7 @@ int ef_get_option(const ef_ctx* c, int32_t option, int64_t* value) {
     case EF_OPT_SEARCH_TOPK_CAND: *value = c->opt_search_topk_cand; return EF_OK;
     case EF_OPT_SEARCH_PREFIX_SPLIT: *value = c->opt_search_prefix_split; return EF_OK;
     case EF_OPT_PROJECT_SPLIT_BF16: *value = c->opt_project_split_bf16; return EF_OK;
+    case EF_OPT_RANK_BITMAP_BYTES: *value = c->opt_rank_bitmap_bytes; return EF_OK;
     default: return EF_E_INVALID;
   }
 }

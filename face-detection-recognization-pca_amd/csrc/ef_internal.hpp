@@ -41,7 +41,7 @@ inline int proj_pad(int kp) { return kp <= 64 ? 64 : (kp + 127) / 128 * 128; }
 constexpr int kSearchProbeTile = 256;   // probes per search workgroup (4 waves x 64)
 constexpr int kProjRowTile = 128;       // probes per projection workgroup
 constexpr int kJacobiMax = 88;          // largest (even) order the LDS Jacobi handles
-constexpr int kTimers = 14;             // EF_KERNEL_* ids (include/eigenface.h)
+constexpr int kTimers = 15;             // EF_KERNEL_* ids (include/eigenface.h)
 constexpr int kCandMax = 32;            // fp64 re-rank candidates kept per ambiguous probe (top-1 search)
 // What gallery_aux_kernel reports of a gallery's rows (ef_search_common.hpp scan_regular)
 constexpr unsigned kRowNotFinite = 1;   // a row whose fp32 ||g||^2 is +inf or NaN
@@ -481,6 +481,15 @@ struct ef_ctx {
                         // (ef_score_census: int[2][bpad], float[bpad] probe norms, the staging, the counts)
   ef::DevBuf cluster_ws;  // per-call scratch of ef_gallery_cluster (ef_cluster.hip): O(n)
   ef::DevBuf range_ws;    // per-call scratch of ef_search_range (ef_range.hip): O(b chunks), then a host call's staging
+  // ef_search_rank (ef_rank.hip): the dense class map of the row labels, built by the first rank
+  // call after ef_gallery_labels and dropped with the labels or the gallery; the per-call scratch
+  // (O(b), a host call's staging, and the bitmap up to opt_rank_bitmap_bytes)
+  bool rank_map_valid = false;
+  int64_t rank_classes = 0;
+  ef::DevBuf rank_cls;   // int32[round_up(gal.n, 128)] class of each row, -1 past the end
+  ef::DevBuf rank_uniq;  // int32[rank_classes] the distinct labels, ascending
+  ef::DevBuf rank_ws;
+  int64_t opt_rank_bitmap_bytes = (int64_t)256 << 20;
   ef::GalleryDerived der;  // the split and prefix copies and the prefix guard (search_copies)
   int64_t opt_search_prefix = 1;
   int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32

@@ -15,6 +15,8 @@ from .evaluate import (OpenSetRates, compare_subspaces, equal_error_threshold, e
                        leave_one_out, open_set_rates)
 from .evaluate import (VerificationRates, auc, compare_verification, d_prime, pair_equal_error,  # noqa: F401
                        score_census, tar_at_fmr, verification_rates)
+from .evaluate import (cmc_curve, identification_ranks, mean_reciprocal_rank, search_rank_plan,  # noqa: F401
+                       summarize_identification)
 from .fisher import Fisherfaces  # noqa: F401
 from .cluster import (ClusterResult, cluster_faces, cluster_gallery, cluster_schedule, pair_confusion,  # noqa: F401
                       pairwise_scores)
@@ -49,4 +51,5 @@ __all__ = [
     "compare_verification",
     "ClusterResult", "cluster_gallery", "cluster_faces", "cluster_schedule", "pair_confusion", "pairwise_scores",
     "RangeResult", "radius_neighbors", "merge_range", "label_votes", "search_range_plan",
+    "cmc_curve", "mean_reciprocal_rank", "identification_ranks", "summarize_identification", "search_rank_plan",
 ]

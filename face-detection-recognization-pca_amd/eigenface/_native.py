@@ -30,6 +30,8 @@ EF_KERNEL_RECON, EF_KERNEL_RECON_REDUCE = 9, 10
 EF_KERNEL_HAAR_SCAN = 11
 EF_KERNEL_CLUSTER = 12
 EF_KERNEL_RANGE = 13
+EF_KERNEL_RANK = 14
+EF_RANK_GENUINE_GIVEN = 0x1000  # ef_search_rank: genuine[b] is an input
 EF_CLUSTER_UNCONVERGED = 1 << 62  # ef_gallery_cluster: bit of info[3] on a device call
 EF_HAAR_GROUP_MAX = 16384  # rectangles per grouping; the ceiling of a Haar scan plan's max_candidates
 EF_HAAR_SCAN_OVERFLOW, EF_HAAR_SCAN_UNCONVERGED = 0x1, 0x2  # ef_haar_scan_head.status bits
@@ -48,6 +50,7 @@ EF_OPT_SEARCH_PREFIX = 11
 EF_OPT_SEARCH_TOPK_CAND = 12
 EF_OPT_SEARCH_PREFIX_SPLIT = 13
 EF_OPT_PROJECT_SPLIT_BF16 = 14
+EF_OPT_RANK_BITMAP_BYTES = 15
 EF_TOPK_MAX = 64  # most ranks of a top-m search
 EF_LABEL_SAME, EF_LABEL_OTHER, EF_LABEL_ANY = 0, 1, 2  # ef_search_labelled relations
 EF_CENSUS_MAX_BINS = 2048  # most bins of ef_score_census
@@ -164,6 +167,9 @@ _SIGS = {
     # range search: added the same way
     "ef_search_range": ([vp, vp, i64, i32, C.c_double, vp, vp, vp, vp, i64, vp, u32], C.c_int),
     "ef_search_range_plan": ([i64, i64, i32, C.POINTER(i64), C.POINTER(i64)], C.c_int),
+    # identification rank: added the same way
+    "ef_search_rank": ([vp, vp, i64, i32, vp, vp, vp, vp, vp, u32], C.c_int),
+    "ef_search_rank_plan": ([i64, i64, i64, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)], C.c_int),
     # model bank: added after API v7 without a version bump, so bound (and checked) by symbol
     "ef_bank_clear": ([vp], C.c_int),
     "ef_bank_add": ([vp, vp, vp, i64, i32, vp, i64, u32, C.POINTER(i32)], C.c_int),

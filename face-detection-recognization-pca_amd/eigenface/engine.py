@@ -96,7 +96,7 @@ _OPTIONS = {"fit_max_iters": N.EF_OPT_FIT_MAX_ITERS, "fit_fp32_coarse": N.EF_OPT
             "fit_chebyshev": N.EF_OPT_FIT_CHEBYSHEV, "host_threads": N.EF_OPT_HOST_THREADS,
             "search_prefix": N.EF_OPT_SEARCH_PREFIX, "search_topk_cand": N.EF_OPT_SEARCH_TOPK_CAND,
             "search_prefix_split": N.EF_OPT_SEARCH_PREFIX_SPLIT,
-            "project_split_bf16": N.EF_OPT_PROJECT_SPLIT_BF16}
+            "project_split_bf16": N.EF_OPT_PROJECT_SPLIT_BF16, "rank_bitmap_bytes": N.EF_OPT_RANK_BITMAP_BYTES}
 
 
 def host_cpu_share():
@@ -309,8 +309,8 @@ class Engine:
         """Context tunable (include/eigenface.h EF_OPT_*): "fit_max_iters",
         "fit_fp32_coarse", "cov_slab_bytes", "tm_int64_sums", "haar_ordered", "jpeg_chunk_bits",
         "search_split_bf16", "jpeg_part_files", "fit_chebyshev", "host_threads" (process-wide),
-        "search_prefix", "search_topk_cand", "search_prefix_split", "project_split_bf16" or the
-        code."""
+        "search_prefix", "search_topk_cand", "search_prefix_split", "project_split_bf16", "rank_bitmap_bytes" or
+        the code."""
         self._chk(self._lib.ef_set_option(self._h, _option(option), int(value)))
 
     def get_option(self, option):
@@ -1156,6 +1156,67 @@ class Engine:
             raise RuntimeError("recognize needs a model and a gallery")
         return self.search_range(self.project(P), threshold, metric, exclude_rows, max_results, out)
 
+    # ------------------------------------------------------- identification rank
+    def search_rank(self, Q, probe_labels, exclude_rows=None, metric="l2", genuine=None, out=None):
+        """ef_search_rank: for each probe the number of OTHER identities with a resident row that
+        beats the probe's genuine row (the nearest row of its own label, ``exclude_rows[p]`` left
+        out), every comparison decided as in fp64 with the first-index rule on ties.  The
+        identification rank is ``better + 1``; ``better`` is -1 for a probe without a genuine row
+        (see ``evaluate.cmc_curve``).  The gallery needs labels (set_gallery_labels).
+
+        Returns ``(better int32 (b,), genuine records (b,), info int64 (4,))`` with info = (pairs
+        settled in fp64, pieces, distinct labels, 0); the records are those of
+        ``search_labelled_matches(.., "same")``.  With ``genuine`` given (records merged over
+        shards with merge_matches / merge_matches_host) they are taken as the genuine rows instead
+        of searched for: over a gallery sharded by identity the shards' ``better`` add up.
+
+        Host arrays in, numpy arrays out; device tensors in, device tensors out, stream-ordered as
+        search_range (``out``: the caller's int32 tensor for ``better``).  The first call after
+        set_gallery_labels builds the class map on the host and waits."""
+        mt = _metric(metric)
+        if self.gallery_k is None:
+            raise RuntimeError("no gallery: call set_gallery first")
+        if probe_labels is None:
+            raise ValueError("probe_labels are required")
+        q, qp, _, b, dev = self._probes(Q, pixels=False)
+        pl, plp = _per_probe(probe_labels, np.int32, "probe_labels", q, dev)
+        ex, exp = _per_probe(exclude_rows, np.int64, "exclude_rows", q, dev)
+        device = q.device if dev else None
+        flags = N.EF_MEM_DEVICE if dev else 0
+        if genuine is None:
+            gen, gp = self._result(q, dev, None, (b,), True, "genuine")
+        else:
+            flags |= N.EF_RANK_GENUINE_GIVEN
+            if dev:
+                import torch
+                if not _is_dev(genuine):
+                    raise TypeError("genuine must be a device tensor for device probes")
+                gen = self._dev_out(genuine, (b, 3), torch.int64, "genuine")
+                gp = gen.data_ptr()
+            else:
+                gen = np.ascontiguousarray(genuine, dtype=N.MATCH_DTYPE)
+                if gen.shape != (b,):
+                    raise ValueError(f"genuine must be ({b},) match records, got {gen.shape}")
+                gp = gen.ctypes.data
+        if out is not None:
+            if not dev:
+                raise ValueError("out is for device input; host input returns new arrays")
+            import torch
+            better = self._dev_out(out, (b,), torch.int32, "out")
+        else:
+            better = _empty(b, np.int32, device)
+        info = _empty(4, np.int64, device)
+        with self._order(dev, q, pl, ex, gen, better, info):
+            self._chk(self._lib.ef_search_rank(self._h, qp, b, mt, plp, exp, gp, _ptr(better), _ptr(info), flags))
+        return better, gen, info
+
+    def recognize_rank(self, P, probe_labels, exclude_rows=None, metric="l2", genuine=None, out=None):
+        """Projection of the pixels P (b, d) with the resident model, then search_rank on the
+        features.  A device input stays on the device."""
+        if self.model_k is None or self.gallery_k is None:
+            raise RuntimeError("recognize needs a model and a gallery")
+        return self.search_rank(self.project(P), probe_labels, exclude_rows, metric, genuine, out)
+
     # ------------------------------------------------------------- top-m search
     def _topk_m(self, m):
         m = int(m)
@@ -1887,7 +1948,8 @@ class Engine:
                "ingest": N.EF_KERNEL_INGEST, "haar": N.EF_KERNEL_HAAR, "jpeg": N.EF_KERNEL_JPEG,
                "syrk": N.EF_KERNEL_SYRK, "jpeg_host": N.EF_KERNEL_JPEG_HOST, "scan": N.EF_KERNEL_SCAN,
                "recon": N.EF_KERNEL_RECON, "recon_reduce": N.EF_KERNEL_RECON_REDUCE,
-               "haar_scan": N.EF_KERNEL_HAAR_SCAN, "cluster": N.EF_KERNEL_CLUSTER, "range": N.EF_KERNEL_RANGE}[kernel]
+               "haar_scan": N.EF_KERNEL_HAAR_SCAN, "cluster": N.EF_KERNEL_CLUSTER, "range": N.EF_KERNEL_RANGE,
+               "rank": N.EF_KERNEL_RANK}[kernel]
         ms = C.c_double(0)
         n = C.c_int64(0)
         self._chk(self._lib.ef_timing_get(self._h, kid, C.byref(ms), C.byref(n)))

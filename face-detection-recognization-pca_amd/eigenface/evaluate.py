@@ -355,3 +355,99 @@ def evaluate_model(model_data, metric="cosine", device=0, keys=None):
     if gk.shape != (feats.shape[0],):
         raise ValueError(f"keys must hold one entry per gallery row ({feats.shape[0]}), got {gk.shape}")
     return summarize(gk, ik, metric)
+
+
+# ------------------------------------------------------------------- identification rank
+# Engine.search_rank (ef_search_rank) gives, per probe, ``better``: the number of other identities
+# that come before the probe's own, -1 for a probe without a genuine row.  The rank is better + 1;
+# everything below is host arithmetic on that array.
+
+def _better(better):
+    b = np.asarray(better)
+    if b.ndim != 1 or not np.issubdtype(b.dtype, np.integer):
+        raise ValueError(f"better must be a 1-D integer array, got {b.dtype} {b.shape}")
+    if (b < -1).any():
+        raise ValueError("better must be -1 (no genuine row) or a count")
+    return b.astype(np.int64)
+
+
+def cmc_curve(better, max_rank=None):
+    """The cumulative match characteristic: ``(ranks 1 .. R, share of the probes with a genuine
+    row whose rank better + 1 is <= r)``.  R defaults to the largest rank present (1 when there is
+    none).  Probes without a genuine row (-1) are in no numerator and no denominator; the shares are
+    NaN when no probe has one."""
+    b = _better(better)
+    ranks = b[b >= 0] + 1
+    if max_rank is None:
+        max_rank = int(ranks.max()) if ranks.size else 1
+    R = int(max_rank)
+    if R < 1:
+        raise ValueError(f"max_rank must be >= 1, got {max_rank}")
+    r = np.arange(1, R + 1)
+    if ranks.size == 0:
+        return r, np.full(R, np.nan)
+    hist = np.bincount(np.minimum(ranks, R + 1), minlength=R + 2)[1:R + 1]
+    return r, np.cumsum(hist) / ranks.size
+
+
+def mean_reciprocal_rank(better):
+    """Mean of 1 / rank over the probes with a genuine row; NaN when there is none."""
+    b = _better(better)
+    ranks = b[b >= 0] + 1
+    return float(np.mean(1.0 / ranks)) if ranks.size else float("nan")
+
+
+def summarize_identification(better, ranks=(1, 5, 10, 20)):
+    """Rank-r identification rates at ``ranks``, the mean reciprocal rank, the median and the
+    largest rank, and the probe counts: ``{"n", "n_genuine", "rank": {r: rate}, "mrr",
+    "median_rank", "max_rank"}`` (NaN / None where no probe has a genuine row)."""
+    b = _better(better)
+    rk = b[b >= 0] + 1
+    out = {"n": int(b.size), "n_genuine": int(rk.size), "rank": {}, "mrr": mean_reciprocal_rank(b),
+           "median_rank": float(np.median(rk)) if rk.size else float("nan"),
+           "max_rank": int(rk.max()) if rk.size else None}
+    for r in ranks:
+        if int(r) < 1:
+            raise ValueError(f"ranks must be >= 1, got {r}")
+        out["rank"][int(r)] = float((rk <= int(r)).mean()) if rk.size else float("nan")
+    return out
+
+
+def identification_ranks(G, labels, metric="cosine", device=0, batch=4096, engine=None):
+    """The leave-one-out form of ``Engine.search_rank``: every row of the labelled gallery ``G``
+    (n, k) against all the others (``exclude_rows = arange``), in batches, as ``leave_one_out``
+    runs the labelled search.  Returns ``better`` int32 (n,): feed it to ``cmc_curve`` /
+    ``summarize_identification``."""
+    from .engine import Engine
+    metric = _metric_name(metric)
+    g = np.ascontiguousarray(G, dtype=np.float32)
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    if g.ndim != 2 or lab.shape != (g.shape[0],):
+        raise ValueError(f"G must be (n, k) and labels (n,), got {g.shape} and {lab.shape}")
+    n = g.shape[0]
+    own = engine is None
+    e = Engine(device) if own else engine
+    try:
+        e.set_gallery(g)
+        e.set_gallery_labels(lab)
+        better = np.empty(n, np.int32)
+        rows = np.arange(n, dtype=np.int64)
+        for a in range(0, n, int(batch)):
+            s = slice(a, min(n, a + int(batch)))
+            better[s] = e.search_rank(g[s], lab[s], rows[s], metric)[0]
+    finally:
+        if own:
+            e.close()
+    return better
+
+
+def search_rank_plan(b, n, n_classes, bitmap_bytes=256 << 20):
+    """ef_search_rank_plan (host only): ``(words_per_probe, probes_per_piece, n_pieces)`` of a rank
+    search with b probes over n rows of n_classes identities under a bitmap budget."""
+    import ctypes as C
+    w, p, m = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    rc = N.lib().ef_search_rank_plan(int(b), int(n), int(n_classes), int(bitmap_bytes), C.byref(w), C.byref(p),
+                                     C.byref(m))
+    if rc != N.EF_OK:
+        raise N.EigenfaceError(rc, "ef_search_rank_plan: bad arguments")
+    return int(w.value), int(p.value), int(m.value)

@@ -543,6 +543,73 @@ int ef_search_range(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric, doub
                     int64_t cap, int64_t* info /* [4] */, uint32_t flags);
 int ef_search_range_plan(int64_t b, int64_t n, int32_t kp, int64_t* n_chunks, int64_t* tiles_per_item);
 
+/* ------------------------------------------------- identification rank (CMC curves)
+ * Added by symbol (EF_API_VERSION stays 7).  For each probe, the number of OTHER identities that
+ * come before the probe's own: better[p], the identification rank less one.  A cumulative match
+ * characteristic is the distribution of better + 1.  The rank of an identity counts identities,
+ * not rows, so no top-m list answers it on a gallery with many rows per person.  The scan is
+ * the range search's counting pass with one threshold per probe (the score of the probe's genuine
+ * row) and one bit per (probe, identity) in place of the count.  No b x n array is written.
+ *
+ * Definition, for probe p with label probe_labels[p] on a gallery with labels (ef_gallery_labels):
+ *   A row qualifies unless its global index is exclude_rows[p] (ef_search_labelled's rule); a pair
+ *   whose fp32 scan score is not finite qualifies for nothing (ef_search_range's rule).
+ *   The genuine row is the one ef_search_labelled(.., EF_LABEL_SAME, ..) returns, row_gen its global
+ *   index, and tau_p its fp64 score (squared L2 distance, or the negated cosine similarity, as
+ *   ef_match.score carries it), recomputed by this call from the stored fp32 features, so that
+ *   bit-identical rows score bit-identically.
+ *   A qualifying row r with a label other than the probe's BEATS the genuine row when its fp64 score
+ *   s(p, r) < tau_p, or s(p, r) == tau_p and its global index is below row_gen (the first-index rule
+ *   of the whole search family).
+ *   better[p] = the number of distinct labels with at least one beating row; rank = better[p] + 1.
+ *   better[p] = -1 when the probe has no genuine row (no qualifying row of its label, a label no
+ *   row carries, a NaN or +-inf component in the probe), or when tau_p is not finite (fp32 squares
+ *   that overflow under L2): no finite score is comparable with it, in any form of the call.
+ * Guarantee: inside the scan's domain (ef_search_range's, evaluated per probe) every "beats" is
+ *   decided as in fp64.  The fp32 scan score decides alone when it is further than delta_p from
+ *   fp32(tau_p); the pairs inside the band are settled by a whole wave on the fp64 score.  delta_p
+ *   is ef_search_range's formula with |fp32(tau_p) - tau_p| as the threshold's rounding term.
+ *   Outside the domain delta_p is +inf: every pair with a finite scan score is settled in fp64
+ *   (correct, and slow).  All accumulation is a bitwise OR and a popcount: the output is
+ *   byte-identical on every run and between the host and the EF_MEM_DEVICE form, and it does not
+ *   depend on EF_OPT_RANK_BITMAP_BYTES.
+ * Outputs:
+ *   better[b]   as defined.
+ *   genuine[b]  optional: the records of the labelled SAME scan, unchanged.
+ *   info[4]     {pairs settled in fp64 (whatever their label), pieces, distinct labels C, 0}.
+ * EF_RANK_GENUINE_GIVEN: genuine[b] is an INPUT, e.g. the records of several shards merged with
+ *   ef_matches_merge.  tau_p is recomputed when the record's row lies in this shard, else the
+ *   record's score is taken as given; a record with EF_KEY_NONE, or a tau_p that is not finite,
+ *   gives -1.  With a gallery sharded by identity (no identity on two shards) every identity is
+ *   counted on exactly one shard, so the shards' better[p] add up exactly to the single-gallery
+ *   answer (pass global exclude_rows to every shard; a probe is -1 on every shard or on none).
+ * The dense class map (label -> 0 .. C - 1) is built on the host by the first call after
+ *   ef_gallery_labels (4 n bytes down, sorted, 4 n bytes up) and cached until the labels or the
+ *   gallery change: THAT call waits for the stream, even with EF_MEM_DEVICE.  Apart from it, with
+ *   EF_MEM_DEVICE every pointer is a device pointer and the call does not wait.
+ * Memory beside the labelled scan's workspace: O(b), and the bitmap: ceil(C / 32) words per
+ *   probe.  The probes run in pieces of whole 256-probe blocks so that a piece's bitmap stays
+ *   within EF_OPT_RANK_BITMAP_BYTES (256 MiB by default; at least one block per piece).
+ * b = 0 is EF_OK; an empty gallery is EF_OK with better all -1 and info all zero.
+ *   EF_E_STATE: no gallery; no gallery labels; a communicator of more than one rank attached.
+ *   EF_E_INVALID: probe_labels, better or info NULL; an unknown metric; EF_RANK_GENUINE_GIVEN
+ *   without genuine; more than 2^31 - 129 rows.  Every k of ef_search is supported.
+ *   ef_timing_get: EF_KERNEL_RANK.
+ *
+ * ef_search_rank_plan: the bitmap's shape for b probes, n rows, n_classes labels and a budget, on
+ *   the host (no context, no device): words_per_probe = max(1, ceil(n_classes / 32)),
+ *   probes_per_piece = 256 max(1, floor(bitmap_bytes / (1024 words_per_probe))), at most b padded
+ *   to 256 (and at least 256), n_pieces = ceil(padded b / probes_per_piece), 0 for b = 0 or
+ *   n = 0.  EF_E_INVALID for a negative argument or a NULL output. */
+#define EF_KERNEL_RANK 14 /* everything one ef_search_rank queues (the labelled scan included) */
+#define EF_RANK_GENUINE_GIVEN 0x1000u /* ef_search_rank: genuine[b] is an input */
+int ef_search_rank(ef_ctx* ctx, const float* Q, int64_t b, int32_t metric,
+                   const int32_t* probe_labels /* [b] */, const int64_t* exclude_rows /* [b] or NULL */,
+                   ef_match* genuine /* [b]: out (may be NULL), or in with EF_RANK_GENUINE_GIVEN */,
+                   int32_t* better /* [b] */, int64_t* info /* [4] */, uint32_t flags);
+int ef_search_rank_plan(int64_t b, int64_t n, int64_t n_classes, int64_t bitmap_bytes,
+                        int64_t* words_per_probe, int64_t* probes_per_piece, int64_t* n_pieces);
+
 /* ------------------------------------------------- Fisher discriminant (Fisherfaces)
  * Added by symbol (EF_API_VERSION stays 7).  A linear discriminant inside face space
  * (Belhumeur, Hespanha, Kriegman 1997): from features F[n][k] (EF_F32 / EF_F64; a fit's
@@ -794,6 +861,11 @@ int ef_comm_info(const ef_ctx* ctx, int32_t* nranks, int32_t* rank);
                                       0's in their last bits (as between two batch sizes) and
                                       repeat bit for bit from call to call.  0: always the fp32
                                       kernel */
+#define EF_OPT_RANK_BITMAP_BYTES 15 /* diagnostic (added by symbol): device budget of ef_search_rank's
+                                      (probe, identity) bitmap [256 MiB]; the probes run in pieces
+                                      of whole 256-probe blocks that fit it, a value below one
+                                      block's need means one block per piece.  The result does not
+                                      depend on it.  >= 1 */
 int ef_set_option(ef_ctx* ctx, int32_t option, int64_t value);
 int ef_get_option(const ef_ctx* ctx, int32_t option, int64_t* value);
 
