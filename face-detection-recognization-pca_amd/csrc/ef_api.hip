@@ -184,8 +184,13 @@ static int prefix_k1(ef_ctx* c, int metric, int variant) {
     (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure of a later launch
     if (q == hipSuccess) {
       d.ev_pending = false;
-      const int64_t fb_tiles = round_up(*static_cast<const int*>(c->prefix_host.p), kSearchProbeTile) / kSearchProbeTile;
+      const int* host = static_cast<const int*>(c->prefix_host.p);
+      const int64_t fb_tiles = round_up(host[0], kSearchProbeTile) / kSearchProbeTile;
       if (2 * fb_tiles > d.ev_tiles) d.skip_left = kPrefixGuardSkips;
+      // the screen's own guard: it left more than half of the probe tiles' probes to the split
+      // stage, which then costs most of a split scan on top of the screen
+      const int64_t sc_tiles = d.ev_screen ? round_up(host[2], kSearchProbeTile) / kSearchProbeTile : 0;
+      if (2 * sc_tiles > d.ev_tiles) d.screen_skip_left = kPrefixGuardSkips;
     }
   }
   if (d.skip_left > 0) {
@@ -198,10 +203,11 @@ static int prefix_k1(ef_ctx* c, int metric, int variant) {
 
 // The derived copies a search of (variant, k1) reads, built on the first search that needs
 // them and kept until GalleryDerived::reset(): G3 in the variant's layout with the scratch Q3
-// of the probes' copy (wide k), and the prefix copy (G1, gnorm1) in the arithmetic of split1.
+// of the probes' copy (wide k), the prefix copy (G1, gnorm1) in the arithmetic of split1, and
+// beside it the screen's single-bf16 copy with its start values (G1h; screen).
 // The only place that builds them and the only one that fills a SplitScan, so no launcher is
 // handed a variant whose copy was not built.
-static int search_copies(ef_ctx* c, int variant, int k1, bool split1, int64_t bpad_max, SplitScan* sp) {
+static int search_copies(ef_ctx* c, int variant, int k1, bool split1, bool screen, int64_t bpad_max, SplitScan* sp) {
   const Gallery& g = c->gal;
   GalleryDerived& d = c->der;
   const float* G = static_cast<const float*>(g.G.p);
@@ -234,6 +240,14 @@ static int search_copies(ef_ctx* c, int variant, int k1, bool split1, int64_t bp
            "prefix gallery");
     d.g1_k1 = k1;
     d.g1_split = split1;
+    d.g1h_k1 = 0;  // gnorm1's second half was rewritten
+  }
+  if (screen && d.g1h_k1 != k1) {
+    d.g1h_k1 = 0;
+    EF_TRY(ensure(c, d.G1h, (size_t)g.n * k1 * 2));
+    EF_HIP(c, launch_prefix_screen_gallery(c->stream, G, g.n, g.kp, k1, d.G1h.p, static_cast<float*>(d.gnorm1.p)),
+           "prefix screen gallery");
+    d.g1h_k1 = k1;
   }
   return EF_OK;
 }
@@ -253,6 +267,7 @@ static int search_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long*
   const Gallery& g = c->gal;
   c->stats_probes = b;
   c->stats_prefix = c->stats_skipped = false;
+  c->stats_screen = c->stats_screen_skipped = false;
   if (g.n == 0) {
     EF_HIP(c, launch_keys_none(c->stream, keys_dev, b, match_dev), "keys");
     return EF_OK;
@@ -262,12 +277,19 @@ static int search_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long*
   const int variant = split_variant(c->opt_search_split_bf16, g.kp, false);
   const int k1 = prefix_k1(c, metric, variant);
   const bool split1 = c->opt_search_prefix_split != 0;  // the prefix scan's arithmetic
+  // the screen engages where prefix64_kernel does, unless its guard keeps this search off it
+  bool screen = k1 > 0 && k1 <= 32 && split1 && c->opt_search_prefix_screen != 0;
+  if (screen && c->der.screen_skip_left > 0) {
+    --c->der.screen_skip_left;
+    c->stats_screen_skipped = true;
+    screen = false;
+  }
   const SearchSchedule sc = search_schedule(b, g.n, g.kp, variant, k1, split1, 0, 0);
   EF_TRY(ensure(c, c->search_ws, sc.ws_bytes));
   Carve cv{c->search_ws.p};
   SearchWs ws = carve_search_ws(cv, sc.parts, (size_t)sc.bpad_max);
   SplitScan sp;
-  EF_TRY(search_copies(c, variant, k1, split1, sc.bpad_max, &sp));
+  EF_TRY(search_copies(c, variant, k1, split1, screen, sc.bpad_max, &sp));
   PrefixWs pw{};
   if (k1 > 0) {
     if (!c->prefix_host.p) EF_HIP(c, pinned_alloc(c->prefix_host, 16), "pinned counters");
@@ -275,7 +297,8 @@ static int search_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long*
     EF_TRY(ensure(c, c->prefix_ws, sc.prefix_bytes));
     Carve cvp{c->prefix_ws.p};
     pw = carve_prefix_ws(cvp, (size_t)sc.bpad_max, k1, g.kp);
-    EF_HIP(c, hipMemsetAsync(ws.amb_count + 2, 0, sizeof(int), c->stream), "zero counters");
+    // [2] the search's total of probes sent to the full-k run; the screen's [3], [4] beside it
+    EF_HIP(c, hipMemsetAsync(ws.amb_count + 2, 0, (screen ? 3 : 1) * sizeof(int), c->stream), "zero counters");
   }
   const float* G = static_cast<const float*>(g.G.p);
   const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? g.gnorm2.p : g.ginv.p);
@@ -285,11 +308,14 @@ static int search_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long*
     const float* q = static_cast<const float*>(c->q_pad.p) + p.off * g.kp;
     ws.match = match_dev ? match_dev + p.off : nullptr;
     tiles += p.bpad / kSearchProbeTile;
+    if (screen && i > 0)  // the piece's own count of probes the screen leaves
+      EF_HIP(c, hipMemsetAsync(ws.amb_count + kScreenCount, 0, sizeof(int), c->stream), "zero counters");
     if (k1 > 0)
       EF_HIP(c,
              launch_search_prefix(c->stream, g.kp, k1, sc.plans[i], sc.plans1[i], q, p.bpad, p.b, G, aux,
                                   static_cast<const float*>(c->der.G1.p), static_cast<const float*>(c->der.gnorm1.p),
-                                  split1, g.n, c->g_offset, scan_gmax2(c, metric), ws, pw, keys_dev + p.off, c),
+                                  split1, screen ? static_cast<const float*>(c->der.G1h.p) : nullptr, g.n, c->g_offset,
+                                  scan_gmax2(c, metric), ws, pw, keys_dev + p.off, c),
              "prefix search");
     else
       EF_HIP(c,
@@ -299,12 +325,16 @@ static int search_run(ef_ctx* c, int64_t bpad, int64_t b, int metric, long long*
   }
   if (k1 > 0) {
     // the counters follow the search to the host; nobody waits for them here
-    EF_HIP(c, hipMemcpyAsync(c->prefix_host.p, ws.amb_count + 2, sizeof(int), hipMemcpyDeviceToHost, c->stream),
+    EF_HIP(c,
+           hipMemcpyAsync(c->prefix_host.p, ws.amb_count + 2, (screen ? 3 : 1) * sizeof(int), hipMemcpyDeviceToHost,
+                          c->stream),
            "D2H prefix counters");
     EF_HIP(c, hipEventRecord(c->prefix_ev, c->stream), "event record");
     c->der.ev_pending = true;
     c->der.ev_tiles = tiles;
+    c->der.ev_screen = screen;
     c->stats_prefix = true;
+    c->stats_screen = screen;
   }
   return EF_OK;
 }
@@ -1156,7 +1186,7 @@ static int search_topk_run(ef_ctx* c, int64_t bpad, int64_t b, int m, int metric
   const SearchWs ws = carve_search_ws(cv, sc.parts, (size_t)sc.bpad_max);
   const TopkWs tw = carve_topk_ws(cv, (size_t)sc.bpad_max, (size_t)cap);
   SplitScan sp;
-  EF_TRY(search_copies(c, variant, 0, false, sc.bpad_max, &sp));
+  EF_TRY(search_copies(c, variant, 0, false, false, sc.bpad_max, &sp));
   const float* aux = static_cast<const float*>(metric == EF_METRIC_L2 ? g.gnorm2.p : g.ginv.p);
   for (size_t i = 0; i < sc.pieces.size(); ++i) {
     const SearchPiece& p = sc.pieces[i];
@@ -1308,6 +1338,11 @@ int ef_set_option(ef_ctx* c, int32_t option, int64_t value) {
       c->opt_search_prefix_split = value;
       c->der.reset();  // a clean guard; the compact copy is rebuilt in the new arithmetic's layout
       return EF_OK;
+    case EF_OPT_SEARCH_PREFIX_SCREEN:
+      if (value != 0 && value != 1) return set_err(c, EF_E_INVALID, "EF_OPT_SEARCH_PREFIX_SCREEN must be 0 or 1");
+      c->opt_search_prefix_screen = value;
+      c->der.reset();  // clean guards
+      return EF_OK;
     case EF_OPT_PROJECT_SPLIT_BF16:
       if (value != 0 && value != 1) return set_err(c, EF_E_INVALID, "EF_OPT_PROJECT_SPLIT_BF16 must be 0 or 1");
       c->opt_project_split_bf16 = value;  // read by the next projection; the pieces stay with the model
@@ -1346,6 +1381,7 @@ int ef_get_option(const ef_ctx* c, int32_t option, int64_t* value) {
     case EF_OPT_SEARCH_TOPK_CAND: *value = c->opt_search_topk_cand; return EF_OK;
     case EF_OPT_SEARCH_PREFIX_SPLIT: *value = c->opt_search_prefix_split; return EF_OK;
     case EF_OPT_PROJECT_SPLIT_BF16: *value = c->opt_project_split_bf16; return EF_OK;
+    case EF_OPT_SEARCH_PREFIX_SCREEN: *value = c->opt_search_prefix_screen; return EF_OK;
     case EF_OPT_RANK_BITMAP_BYTES: *value = c->opt_rank_bitmap_bytes; return EF_OK;
     default: return EF_E_INVALID;
   }
@@ -1377,6 +1413,17 @@ int ef_search_stats(ef_ctx* c, int64_t out[4]) {
   out[1] = c->stats_prefix ? c->stats_probes - fb : 0;
   out[2] = fb;
   out[3] = c->stats_skipped ? 1 : 0;
+  return EF_OK;
+}
+
+int ef_prefix_screen_stats(ef_ctx* c, int64_t out[3]) {
+  if (!c || !out) return EF_E_INVALID;
+  (void)hipSetDevice(c->device);
+  EF_HIP(c, hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+  const int64_t left = c->stats_screen ? (int64_t) static_cast<const int*>(c->prefix_host.p)[2] : 0;
+  out[0] = c->stats_screen ? c->stats_probes : 0;
+  out[1] = c->stats_screen ? c->stats_probes - left : 0;
+  out[2] = c->stats_screen_skipped ? 1 : 0;
   return EF_OK;
 }
 

@@ -80,9 +80,13 @@ struct SearchPlan {
 // Scratch of one prefix search (EF_OPT_SEARCH_PREFIX; device pointers).  The counters of the
 // path live beside SearchWs::amb_count: amb_count[1] = probes of this piece sent to the
 // full-k scan (the device count of the second run), amb_count[2] = their total over the
-// search's pieces.
+// search's pieces.  The cascade (EF_OPT_SEARCH_PREFIX_SCREEN) adds amb_count[kScreenCount] = probes
+// of this piece the screen left unproven (the device count of the split stage) and
+// amb_count[kScreenTotal] = their total over the pieces.
+constexpr int kScreenCount = 3, kScreenTotal = 4;
 struct PrefixWs {
-  float* q1;         // [bpad][K1] the probes' first K1 components (the search_kernel forms; prefix64_kernel reads qpad)
+  float* q1;         // [bpad][K1] the probes' first K1 components (the search_kernel forms; prefix64_kernel reads qpad,
+                     // and the cascade, which runs only where it does, keeps the screen's list of bpad ints here)
   float* qpad2;      // [bpad][KP] the unproven probes' rows, in list order
   int* list;         // [bpad] probe of each unproven slot
   long long* keys2;  // [bpad] keys of the second run, by slot
@@ -214,7 +218,7 @@ struct Carve {
 // parts: the largest nchunks x bpad of the call's pieces; bpad: its largest piece (the
 // braces evaluate left to right, in member order; match stays null)
 inline SearchWs carve_search_ws(Carve& cv, size_t parts, size_t bpad) {
-  return SearchWs{cv.take<long long>(parts), cv.take<float>(parts), cv.take<int>(4), cv.take<int>(bpad),
+  return SearchWs{cv.take<long long>(parts), cv.take<float>(parts), cv.take<int>(8), cv.take<int>(bpad),
                   cv.take<float>(bpad), cv.take<int>(bpad * kCandMax), cv.take<int>(bpad), nullptr, kCandMax};
 }
 // Scratch of one top-m search beside its SearchWs (ef_search_topk.hip; device pointers).  The
@@ -337,14 +341,20 @@ struct GalleryDerived {
   DevBuf gnorm1;  // float[2][n]: fp32 ||g[:K1]||^2, then the aux kernel's unused 1/||.|| output
   int g1_k1 = 0;  // 0: no copy
   bool g1_split = false;  // only the copy the chosen arithmetic reads is kept
+  // the screen (EF_OPT_SEARCH_PREFIX_SCREEN): single-bf16 copy of the same prefix; its start
+  // values take gnorm1's second half, so it is rebuilt whenever G1 is
+  DevBuf G1h;      // bf16[n][g1h_k1]
+  int g1h_k1 = 0;  // 0: no copy
   // the guard: counters of the last prefix search arrive in pinned memory behind ev
   bool ev_pending = false;
   int64_t ev_tiles = 0;  // probe tiles of the search ev belongs to
   int skip_left = 0;     // searches the guard still keeps off the prefix scan
+  bool ev_screen = false;    // the search ev belongs to ran the screen
+  int screen_skip_left = 0;  // searches the screen's guard still sends straight to the split stage
   void reset() {
-    g3_layout = g1_k1 = 0;
-    ev_pending = false;
-    skip_left = 0;
+    g3_layout = g1_k1 = g1h_k1 = 0;
+    ev_pending = ev_screen = false;
+    skip_left = screen_skip_left = 0;
   }
 };
 
@@ -493,13 +503,16 @@ struct ef_ctx {
   ef::GalleryDerived der;  // the split and prefix copies and the prefix guard (search_copies)
   int64_t opt_search_prefix = 1;
   int64_t opt_search_prefix_split = 1;  // the prefix scan's arithmetic: 1 split bf16, 0 fp32
+  int64_t opt_search_prefix_screen = 1;  // 1: a single-bf16 screen ahead of the split scan at K1 <= 32
   ef::DevBuf prefix_ws;  // per-call scratch of the prefix path (ef::PrefixWs carve-out)
   // counters of the last prefix search, copied to pinned host memory behind the search
-  // ([0] probes sent to the full-k scan); the next search reads them once prefix_ev has passed
+  // ([0] probes sent to the full-k scan, [2] probes the screen left unproven); the next search
+  // reads them once prefix_ev has passed
   ef::PinnedBuf prefix_host;  // int[4]
   // what ef_search_stats reports: {probes, used the prefix scan, guard skipped}
   int64_t stats_probes = 0;
   bool stats_prefix = false, stats_skipped = false;
+  bool stats_screen = false, stats_screen_skipped = false;  // ef_prefix_screen_stats
 
   // per-call scratch (grown on demand, never shrunk)
   ef::DevBuf q_pad;     // float[bpad][kp]
@@ -607,15 +620,23 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SplitScan& sp,
 // launch_search on the unproven probes.  Same keys / match records as launch_search.
 // split (EF_OPT_SEARCH_PREFIX_SPLIT): G1 holds split-bf16 rows and the scan runs the split
 // chain; pl1 is planned with prefix_tile_rows(k1, split).
+// G1h (EF_OPT_SEARCH_PREFIX_SCREEN; split and k1 <= 32 only, else null): the single-bf16 copy
+// of the prefix, its start values at gnorm1 + n.  The scan then runs as a cascade: the screen
+// over G1h, the split scan for the probes the screen could not prove, the full-k pipeline for
+// the rest.  The caller zeroes ws.amb_count[kScreenCount] ahead of every piece.
 hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan& pl, const SearchPlan& pl1,
                                 const float* qpad, int64_t bpad,
                                 int64_t b, const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
-                                bool split, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
-                                const PrefixWs& pw, long long* keys, ef_ctx* c);
+                                bool split, const float* G1h, int64_t n, int64_t g_offset, float gmax2,
+                                const SearchWs& ws, const PrefixWs& pw, long long* keys, ef_ctx* c);
 // G1[n][k1] <- G[n][kp][:k1], gnorm1[n] = ||G1 row||^2 in fp32 (gnorm1 holds 2 n floats);
 // split: G1's rows are then rewritten as split-bf16 rows (launch_split_rows, same bytes)
 hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, bool split, float* G1,
                                  float* gnorm1);
+// G1h[n][k1] <- bf16(G[n][kp][:k1]) and the screen's start values gnorm1[n + r] from gnorm1[r]
+// (after launch_prefix_gallery, whose aux kernel writes that half too)
+hipError_t launch_prefix_screen_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, void* G1h,
+                                        float* gnorm1);
 hipError_t launch_split_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);
 // single-bf16 copy for the bf16 screen (EF_OPT_SEARCH_SPLIT_BF16 = 3), kp % 64 == 0
 hipError_t launch_hi_rows(hipStream_t s, const float* G, int64_t n, int kp, void* out);

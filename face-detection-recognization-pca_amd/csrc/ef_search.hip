@@ -50,7 +50,10 @@
 // (EF_OPT_SEARCH_PREFIX_SPLIT; prefix64_kernel at K1 <= 32, search_kernel<K1, .., S3> at 64) or
 // in fp32 (search_kernel<K1>), gives a lower bound of every distance;
 // reduce_prefix_kernel proves the winner from it where it can, and only the unproven probes
-// go through passes 1-3 at full k (launch_search_prefix).
+// go through passes 1-3 at full k (launch_search_prefix).  At K1 <= 32 the split
+// scan is the middle of a cascade (EF_OPT_SEARCH_PREFIX_SCREEN): a single-bf16 screen with a
+// bound per row and per probe goes first (prefix64x_kernel, reduce_prefix_x_kernel) and the
+// split scan runs for the probes it cannot prove alone.
 //
 // Top-m search (ef_search_topk.hip) launches pass 1 and the COLLECT pass of
 // these kernels through launch_search_scan, with its own threshold and resolution kernels.
@@ -1007,6 +1010,292 @@ __global__ __launch_bounds__(512, 4) void prefix64_kernel(
   }
 }
 
+// The cascade's other two forms of the scan (EF_OPT_SEARCH_PREFIX_SCREEN; search_prefix_t), one
+// kernel template of their own: prefix64_kernel above stays as it is, text and name, for the
+// launch sequence of option 0.  What differs from it is marked HI1 / CNT; the rest is its code
+// with the row length in LDS (RF floats) in place of K1.
+//
+// Screen (HI1, not CNT): one product per fragment, hi(g).hi(-2 q), over the single-bf16 copy of
+// the prefix (G1 = G1h: n rows of K1 bf16 values, round to nearest even as bf16_bits; 64- or
+// 32-byte rows, so four or eight rows span the 64 banks: SS = 2 or 3, and the lane groups of
+// ds_read_b128 again meet each bank range in distinct (r >> SS) & (CPR - 1)).  A chain starts from
+// the row's value of gnorm1 = gstart, a rounded-down ||g[:K1]||^2 (1 - es - cg) (prefix_hi_kernel),
+// and so ends at a lower bound L(g) of the row's prefix score plus the probe's share of the bound
+// (reduce_prefix_x_kernel, S3 = 2).  Rows are ranked by L: the record is (min L, its first row, second
+// smallest L).  Half the tile bytes, DMAs and A reads of the split form, a third of its MFMAs;
+// 108 VGPRs at K1 = 32, 96 at 16, no scratch.
+//
+// Split scan of the listed probes (CNT, not HI1): prefix64_kernel's arithmetic for the probes
+// list[0 .. cnt), cnt = ws.amb_count[kScreenCount] on the device, read from qpad through the
+// list; slot s of the records belongs to probe list[s].  The grid is sized for bpad; a workgroup
+// whose probe tile starts at or past cnt returns at once.
+template <int KP, int K1, int PB, bool HI1, bool CNT>
+__global__ __launch_bounds__(512, 4) void prefix64x_kernel(
+    const float* __restrict__ qpad, const float* __restrict__ G1, const float* __restrict__ gnorm1, int64_t n,
+    int n_ptiles, int tiles_per_chunk, int64_t bpad, SearchWs ws, const int* __restrict__ list) {
+  static_assert((K1 == 16 || K1 == 32) && K1 < KP, "the prefix lengths that take 256-row tiles");
+  constexpr int NW = 8, TGT = kPrefixSplitTile;
+  constexpr int RB = 4 / PB;  // row blocks run at once: RB x PB = 4 accumulator chains
+  constexpr int KH = K1 / 2, NF = KH / 8;  // k per lane half, 8-element fragments of it
+  constexpr int CPR = HI1 ? K1 / 8 : K1 / 4;  // 16-B chunks per row (HI1: K1 bf16 values)
+  constexpr int RF = CPR * 4;                 // a row's length in floats
+  constexpr int SS = CPR == 8 ? 1 : CPR == 4 ? 2 : 3;  // swizzle: chunk ^ ((row >> SS) & (CPR - 1))
+  constexpr int RP = 64 / CPR;             // rows per 1-KiB DMA piece
+  constexpr int NI = TGT / RP, PPW = NI / NW;
+  constexpr int TGS = TGT * RF;            // floats per tile buffer
+  static_assert(PPW * NW == NI && RP % (1 << SS) == 0, "whole pieces per wave, swizzle splits per piece");
+  __shared__ __attribute__((aligned(16))) float smem[2 * TGS + 2 * TGT];
+  float* const sAux0 = smem + 2 * TGS;
+
+  const int lin = xcd_lin();  // the probe tiles of one chunk co-resident on an XCD
+  const int gc = lin / n_ptiles, pt = lin - gc * n_ptiles;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // The lane id is re-derived where it is needed (two VALU instructions) instead of living in
+  // VGPRs through the sweep with what is computed from it: 64 accumulators, 32 probe registers
+  // and 16 of A fragments leave 16 for everything else
+  auto lane_id = [] {
+    unsigned l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return (int)l;
+  };
+
+  int64_t t0, t1;
+  chunk_range<TGT>(n, gc, tiles_per_chunk, t0, t1);
+  // this lane's probe slots: block 0 at s0, block 1 at s0 + 32; a wave's 64 slots lie on one
+  // side of bpad (a multiple of 256)
+  const int64_t w0 = (int64_t)pt * (NW * 32 * PB) + wave * (32 * PB);
+  // CNT: slot s holds probe list[s] for s < cnt, the device count; workgroups and waves wholly
+  // past it have nothing to do, and the slots past it inside a live wave are swept as zeros
+  int cnt = 0;
+  if constexpr (CNT) {
+    cnt = ws.amb_count[kScreenCount];
+    if ((int64_t)pt * (NW * 32 * PB) >= cnt) return;
+  }
+  const bool live = CNT ? w0 < cnt : w0 < bpad;  // wave-uniform
+
+  if (t0 >= t1) {  // empty chunk: publish "no candidate" so the reducer can skip it
+    const int lane = lane_id();
+    const int64_t s0 = w0 + lane;
+    if (live && lane < 32) {
+#pragma unroll
+      for (int pb = 0; pb < PB; ++pb) top2_store_empty(ws, (int64_t)gc * bpad, s0 + 32 * pb);
+    }
+    return;
+  }
+
+  // LDS-DMA of tile t into buffer buf: wave w fills pieces [w PPW, (w + 1) PPW), a piece is RP
+  // whole rows, lane-linear.  The swizzle is applied on the source address and splits into a
+  // lane constant and a wave-uniform part: ((j RP + lrow) >> SS) = (j RP >> SS) + (lrow >> SS),
+  // a sum without carries.  Rows past n (tail tile) re-read the last row, masked below.
+  const unsigned lds_base = lds_addr(smem);
+  auto issue_tile = [&](int64_t t, int buf) {
+    const int nrem = (int)((n - t * TGT) < TGT ? (n - t * TGT) : TGT);
+    const int lane = lane_id();
+    const int lr = lane / CPR;                                // this lane's (row, chunk) inside a piece
+    const int lx = (lane % CPR) ^ ((lr >> SS) & (CPR - 1));  // chunk, with the lane's swizzle part
+    if (nrem == TGT) {
+      const unsigned long long gb = uniform_ptr(G1 + t * TGT * RF);
+      const unsigned lro = (unsigned)(lr * RF * 4);
+#pragma unroll
+      for (int jj = 0; jj < PPW; ++jj) {
+        const int j = wave * PPW + jj;
+        const int sj = ((j * RP) >> SS) & (CPR - 1);
+        glds16s(lro + ((unsigned)(lx ^ sj) << 4), gb + (unsigned long long)(j * RP * RF * 4),
+                lds_base + (unsigned)((buf * TGS + j * 256) * 4));
+      }
+      if (wave < TGT / 64)  // one 64-row piece of the norms per wave
+        glds4s((unsigned)lane * 4u, uniform_ptr(gnorm1 + t * TGT + wave * 64),
+               lds_base + (unsigned)((2 * TGS + buf * TGT + wave * 64) * 4));
+    } else {
+      const float* gbase = G1 + t * TGT * RF;  // wave-uniform
+#pragma unroll
+      for (int jj = 0; jj < PPW; ++jj) {
+        const int j = wave * PPW + jj;
+        const int sj = ((j * RP) >> SS) & (CPR - 1);
+        int row = j * RP + lr;
+        row = row < nrem ? row : nrem - 1;
+        glds16(gbase + row * RF + ((lx ^ sj) << 2), lds_base + (unsigned)((buf * TGS + j * 256) * 4));
+      }
+      if (wave < TGT / 64) {
+        const int row = wave * 64 + lane < nrem ? wave * 64 + lane : nrem - 1;
+        glds4(gnorm1 + t * TGT + row, lds_base + (unsigned)((2 * TGS + buf * TGT + wave * 64) * 4));
+      }
+    }
+  };
+
+  issue_tile(t0, 0);
+
+  // Probe fragments (B operands): lane holds probes c32 and 32 + c32 of the wave, k in
+  // [h KH, h KH + KH) of the row's first K1 columns, scaled by -2 (exact) and split, so that a
+  // chain started from ||g||^2 ends at the L2 prefix score
+  bf16x8 qh[PB][NF], ql[PB][HI1 ? 1 : NF];  // HI1: the hi fragments alone
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb) {
+    const int lane = lane_id();
+    bool have = live;
+    const float4* q0;
+    if constexpr (CNT) {
+      const int64_t slot = w0 + (lane & 31) + 32 * pb;
+      have = live && slot < cnt;
+      q0 = reinterpret_cast<const float4*>(qpad + (int64_t)(have ? list[slot] : 0) * KP + (lane >> 5) * KH);
+    } else {
+      q0 = reinterpret_cast<const float4*>(qpad + (live ? w0 + (lane & 31) + 32 * pb : 0) * KP + (lane >> 5) * KH);
+    }
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      const float4 a = have ? q0[2 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 b = have ? q0[2 * i + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float t[8] = {-2.f * a.x, -2.f * a.y, -2.f * a.z, -2.f * a.w, -2.f * b.x, -2.f * b.y, -2.f * b.z, -2.f * b.w};
+      if constexpr (HI1) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qh[pb][i][j] = (short)bf16_bits(t[j]);
+      } else {
+        split8(t, qh[pb][i], ql[pb][i]);
+      }
+    }
+  }
+  // consumed here so that the waits for these loads stand before the loop (search_kernel)
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      if constexpr (HI1) asm volatile("" ::"v"(qh[pb][i]));
+      else asm volatile("" ::"v"(qh[pb][i]), "v"(ql[pb][i]));
+    }
+
+  const float INF = __builtin_inff();
+  float b1[PB], b2[PB];
+  int i1[PB];
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb) b1[pb] = b2[pb] = INF, i1[pb] = INT_MAX;
+
+  // Arg-best epilogue of one finished block of scores v (register r <-> row rowbase + (r & 3) +
+  // 8 (r >> 2) + 4 h, increasing with r), merged into probe block pb's running record.  The
+  // screen is search_kernel's: a block whose minimum is not below the lane's runner-up changes
+  // nothing, and when that holds for every lane the block is skipped on a uniform branch.  A
+  // block that passes is walked in row order, and only the registers in which some lane has a
+  // score below its runner-up are merged (a uniform branch each; a score that is not below b2
+  // leaves b1, b2 and i1 as they are): with b1 <= b2 the new runner-up is the median of (b1,
+  // score, b2), and strict '<' keeps the lowest row on ties.  The chunk sweeps are short enough
+  // that about half the blocks pass the screen for one or two lanes, and search_kernel's
+  // branch-free top-2 of all 16 registers (64 VALU instructions) was most of this scan's
+  // non-MFMA work.  The record is the same: minimum, its first row, second smallest of the
+  // multiset.
+  auto consume = [&](const f32x16& v, int rowbase, int pb, int h) {
+    float mn = v[0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mn = fminf(mn, v[r]);
+    if (!__any(mn < b2[pb])) return;  // exact skip: the block changes nothing
+    const int row0 = rowbase + 4 * h;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      // expected not taken: the merges then lie out of line and a walk falls through 16 compares
+      if (__builtin_expect(!__any(v[r] < b2[pb]), 1)) continue;
+      const bool lt = v[r] < b1[pb];
+      b2[pb] = __builtin_amdgcn_fmed3f(b1[pb], v[r], b2[pb]);
+      i1[pb] = lt ? row0 + (r & 3) + 8 * (r >> 2) : i1[pb];
+      b1[pb] = lt ? v[r] : b1[pb];
+    }
+  };
+
+  dma_wait_all();
+  __syncthreads();  // tile t0 landed
+
+  for (int64_t t = t0; t < t1; ++t) {
+    const int buf = (int)((t - t0) & 1);
+    if (t + 1 < t1) issue_tile(t + 1, buf ^ 1);  // lands under this tile's MFMAs
+    const float* tileA = sAux0 + buf * TGT;
+    const bool tail = (t + 1) * TGT > n;
+    const int tbase = (int)(t * TGT);
+    const int lane = lane_id();
+    const int h = lane >> 5, c32 = lane & 31;
+    const int swz = (c32 >> SS) & (CPR - 1);  // rows c32 and 32 bi + c32 share it
+    const float* arow = smem + buf * TGS + c32 * RF;
+#pragma unroll
+    for (int g0 = 0; g0 < TGT / 32; g0 += RB) {  // row blocks g0 .. g0 + RB - 1 against every probe block
+      f32x16 acc[RB][PB];
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb) {
+        f32x16 a;  // ||g||^2 of the block's rows, in the register <-> row map
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 x = *reinterpret_cast<const float4*>(tileA + 32 * (g0 + rb) + 8 * q + 4 * h);
+          a[4 * q] = x.x;
+          a[4 * q + 1] = x.y;
+          a[4 * q + 2] = x.z;
+          a[4 * q + 3] = x.w;
+        }
+#pragma unroll
+        for (int pb = 0; pb < PB; ++pb) acc[rb][pb] = a;
+      }
+      if constexpr (HI1) {
+        // one product per fragment: chunk i of this lane half's k range, every fragment of the
+        // group read ahead of its MFMAs (8 NF registers where the split form holds 16)
+        bf16x8 a1[RB][NF];
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+          for (int rb = 0; rb < RB; ++rb)
+            a1[rb][i] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + rb) * 32 * RF + ((h * (CPR / 2) + i) ^ swz) * 4));
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            acc[c / PB][c % PB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[c / PB][i], qh[c % PB][i], acc[c / PB][c % PB], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // fragment i: chunks 2i (hi) and 2i + 1 (lo) of this lane half's k range
+#pragma unroll
+      for (int i = 0; i < (HI1 ? 0 : NF); ++i) {
+        const int c0 = h * (CPR / 2) + 2 * i;
+        const int ch = c0 ^ swz, cl = (c0 + 1) ^ swz;
+        bf16x8 ah[RB], al[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+          ah[rb] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + rb) * 32 * RF + ch * 4));
+          al[rb] = as_bf16x8(*reinterpret_cast<const float4*>(arow + (g0 + rb) * 32 * RF + cl * 4));
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[c / PB][c % PB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c / PB], qh[c % PB][i], acc[c / PB][c % PB], 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[c / PB][c % PB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[c / PB], ql[c % PB][i], acc[c / PB][c % PB], 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[c / PB][c % PB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[c / PB], qh[c % PB][i], acc[c / PB][c % PB], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);  // bound the A prefetch depth
+      }
+      if (tail) {  // uniform: only the last tile has rows past n
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (tbase + 32 * (g0 + rb) + (r & 3) + 8 * (r >> 2) + 4 * h >= n) {
+#pragma unroll
+              for (int pb = 0; pb < PB; ++pb) acc[rb][pb][r] = INF;
+            }
+      }
+#pragma unroll
+      for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) consume(acc[rb][pb], tbase + 32 * (g0 + rb), pb, h);  // in row order (tie rule)
+    }
+    dma_wait_all();
+    __syncthreads();  // tile t+1 landed; everyone is done reading buffer buf
+  }
+
+#pragma unroll
+  for (int pb = 0; pb < PB; ++pb) {  // merge the two lane halves (same probe, disjoint rows)
+    const float ob1 = __shfl_xor(b1[pb], 32);
+    const int oi1 = __shfl_xor(i1[pb], 32);
+    const float ob2 = __shfl_xor(b2[pb], 32);
+    top2_merge(b1[pb], b2[pb], i1[pb], ob1, ob2, oi1);
+    const int lane = lane_id();
+    if (live && lane < 32) top2_store(ws, (int64_t)gc * bpad, w0 + lane + 32 * pb, b1[pb], b2[pb], i1[pb]);
+  }
+}
+
 // One wave per probe: winner over chunks, global runner-up, fp64 re-score, ambiguity test.
 // KP = 0: row length kp_rt at run time (k > 512).
 // S3: the scan's arithmetic — 0 fp32, 1 split bf16 (hi + lo), 2 single bf16 (the screen of
@@ -1256,6 +1545,129 @@ __global__ __launch_bounds__(256) void reduce_prefix_kernel(const float* __restr
   }
 }
 
+// The cascade's reduces (EF_OPT_SEARCH_PREFIX_SCREEN), a kernel template of their own:
+// reduce_prefix_kernel above stays as it is, text and name, for option 0.  The code is its code
+// with the slot p of the records apart from the probe pr.
+//
+// S3 = 2 (the first stage of the cascade): the scan was
+// prefix64x_kernel<.., HI1>, one bf16 product per element.  With q^ = bf16(q), g^ = bf16(g) rounded
+// to nearest, |x - x^| <= 2^-8 |x|, so per element
+//   |2 q_i g_i - 2 q^_i g^_i| <= es 2 |q_i| |g_i| <= es (q_i^2 + g_i^2),  es = 2.01 2^-8
+// (bf16(-2 q) = -2 q^ exactly), and over the K1 elements, with g1 = ||g[:K1]||^2,
+//   |S~1(g) - S1(g)| <= es (q1 + g1),  S~1(g) = g1 - 2 q^.g^ in exact arithmetic.
+// The row's share es g1 is a constant of the row and the probe's share es q1 one of the probe,
+// so neither needs the largest norm of the gallery (scan_delta<L2, 2>'s 2 es ||q|| gm proves
+// nothing as soon as one row is long).  The fp32 terms of scan_delta<L2, 2> at chain length K1
+// split the same way: every partial sum of a row's chain is at most g1 + 2.02 ||q[:K1]||
+// ||g[:K1]|| <= 1.01 q1 + 2.01 g1 in magnitude, so K1 + 4 adds and the final rounding (K1 + 6
+// roundings at 2u each, 1 % for the products of rounded operands) cost at most
+// cf (1.01 q1 + 2.01 g1), cf = (K1 + 6) 2u 1.01, and the fp32 norm itself K1 u g1.  With the
+// project's safety factor 2 on these (none on es, a rounding theorem):
+//   cg = 2 (2.01 cf + K1 u),  cq = 2 (1.01 cf)        (prefix_screen_cg / _cq),
+// and a chain started from gstart(g) <= g1 (1 - es - cg) (rounded down, prefix_hi_kernel) ends at
+//   L(g) <= S1(g) + (es + cq) q1   for every row g.
+// Rows are ranked by L, not by the score: w = arg-min L (lowest row on ties), r2L = min of L over
+// every other row.  Then for every g != w
+//   D(g) >= q1 + S1(g) >= q1 (1 - es - cq) + L(g) >= q1 (1 - es - cq) + r2L,
+// and the test  q1 (1 - es - cq) + r2L - uf > Dw + tol  proves D(g) > Dw + tol for all of them:
+// w is the unique arg-min outside the tie window, as above.  If w is not the nearest row, or
+// another row lies within tol of it, that row t has D(t) <= Dw + tol and L(t) >= r2L, and the
+// test fails.  uf = (4 K1 + 8) 2^-126 (1 + 2.02 ||q|| + gm) covers operands, products and sums
+// that underflow (2^-126 each, times the other operand), which the relative terms do not; the
+// gate scan_regular and the negated gmax2 are the split form's.  The test's own fp64 rounding
+// is below 1e-13 (q1 + |r2L| + Dw) as above, against cq q1 + cg g1 >= 1e-5 (q1 + g1) of slack
+// whose safety factor's half is unused.  Unproven probes are appended to `list` with the count
+// at ws.amb_count[kScreenCount].
+//
+// LST (the cascade's second stage; S3 = 1): slot p < ws.amb_count[kScreenCount] of the records
+// belongs to probe src[p] (prefix64x_kernel<.., CNT>).  Its key and record go to the probe's own
+// place and an unproven probe is listed by its own index, so nothing is scattered back; thread
+// 0 adds the piece's screen count to the search's total (ws.amb_count[kScreenTotal]).
+__host__ __device__ inline double prefix_screen_cf(int k1) { return (k1 + 6) * 2.0 * 5.9604644775390625e-08 * 1.01; }
+__host__ __device__ inline double prefix_screen_cg(int k1) {
+  return 2.0 * (2.01 * prefix_screen_cf(k1) + k1 * 5.9604644775390625e-08);
+}
+__host__ __device__ inline double prefix_screen_cq(int k1) { return 2.0 * 1.01 * prefix_screen_cf(k1); }
+constexpr double kScreenEs = 2.01 * 0.00390625;  // 2.01 2^-8
+
+template <int KP, int K1, int S3, bool LST>
+__global__ __launch_bounds__(256) void reduce_prefix_x_kernel(const float* __restrict__ qpad, int64_t b, int64_t bpad,
+                                                              int nchunks, const float* __restrict__ G,
+                                                              int64_t g_offset, float gmax2, SearchWs ws,
+                                                              long long* __restrict__ keys, int* __restrict__ list,
+                                                              const int* __restrict__ src) {
+  const int lane = threadIdx.x & 63;
+  const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // the records' slot
+  int* const unproven = ws.amb_count + (S3 == 2 ? kScreenCount : 1);
+  int64_t pr = p;  // the probe
+  if constexpr (LST) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) ws.amb_count[kScreenTotal] += ws.amb_count[kScreenCount];
+    if (p >= ws.amb_count[kScreenCount]) return;
+    pr = src[p];
+  } else {
+    if (p >= b) return;
+  }
+  long long kmin = LLONG_MAX;
+  for (int c = lane; c < nchunks; c += 64) {
+    const long long k = ws.part_key[(int64_t)c * bpad + p];
+    kmin = k < kmin ? k : kmin;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long o = __shfl_xor(kmin, off);
+    kmin = o < kmin ? o : kmin;
+  }
+  if (kmin == LLONG_MAX) {  // no row scored (cannot happen with n > 0): the full-k run decides
+    if (lane == 0) list[atomicAdd(unproven, 1)] = (int)pr;
+    return;
+  }
+  float r2 = __builtin_inff();
+  for (int c = lane; c < nchunks; c += 64) {
+    const long long k = ws.part_key[(int64_t)c * bpad + p];
+    r2 = fminf(r2, ws.part_b2[(int64_t)c * bpad + p]);
+    if (k != kmin && k != LLONG_MAX) r2 = fminf(r2, key_value(k));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) r2 = fminf(r2, __shfl_xor(r2, off));
+
+  const float b1 = key_value(kmin);
+  const unsigned row = (unsigned)(kmin & 0xffffffffll);
+  const float* q = qpad + pr * KP;
+  const double dw = score64<KP, EF_METRIC_L2>(q, G + (int64_t)row * KP, lane);
+  double qq64 = 0.0, q1 = 0.0;
+  for (int c = lane; c < KP; c += 64) {
+    const double t = (double)q[c] * (double)q[c];
+    qq64 += t;
+    if (c < K1) q1 += t;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    qq64 += __shfl_xor(qq64, off);
+    q1 += __shfl_xor(q1, off);
+  }
+  // the probe's side of the bound: what is taken off q1 + r2
+  double off1;
+  if constexpr (S3 == 2) {
+    const double uf = (4 * K1 + 8) * 1.1754943508222875e-38 * (1.0 + 2.02 * sqrt(qq64) + sqrt(fabs((double)gmax2)));
+    off1 = (kScreenEs + prefix_screen_cq(K1)) * q1 + uf;
+  } else {
+    off1 = (double)((S3 ? 2.f : 1.f) * scan_delta<EF_METRIC_L2, S3>(K1, sqrtf((float)qq64), gmax2, b1));
+  }
+  const double scale = qq64 + (double)gmax2;
+  const double tol = 1e-12 * (fabs(dw) + scale);
+  // outside the bound's domain (scan_regular: a negated gmax2 among them) nothing is proven here
+  const bool regular = scan_regular<EF_METRIC_L2>((float)qq64, gmax2);
+  if (lane == 0) {
+    if (regular && q1 + (double)r2 - off1 > dw + tol) {
+      const long long key = pack_key((float)dw, (unsigned)(row + g_offset));
+      keys[pr] = key;
+      if (ws.match) ws.match[pr] = ef_match{dw, scale, key};
+    } else {
+      list[atomicAdd(unproven, 1)] = (int)pr;
+    }
+  }
+}
+
 // dst[rows][c4_dst] <- the first c4_dst 16-B chunks of src[rows][c4_src] (the prefix copies of
 // the gallery and of the probes).
 __global__ void prefix_cols_kernel(const float4* __restrict__ src, int64_t rows, int c4_src, int c4_dst,
@@ -1367,6 +1779,24 @@ __global__ void hi_rows_kernel(const float* __restrict__ G, int64_t blocks, uint
     out[8 * i + c] = make_uint4(bf16_bits(a.x) | bf16_bits(a.y) << 16, bf16_bits(a.z) | bf16_bits(a.w) << 16,
                                 bf16_bits(b.x) | bf16_bits(b.y) << 16, bf16_bits(b.z) | bf16_bits(b.w) << 16);
   }
+}
+
+// The screen's copy of the prefix (EF_OPT_SEARCH_PREFIX_SCREEN): out[n][c8] 16-B chunks, chunk c
+// of row r = bf16(G[r][8 c .. 8 c + 7]), and the chains' start values gstart[r] = gnorm1[r] fac
+// rounded down, fac = 1 - es - cg (reduce_prefix_x_kernel): fac's own rounding and the two
+// products' are 3 2^-24 at the most, the factor 1 - 2^-22 takes them off again.
+__global__ void prefix_hi_kernel(const float* __restrict__ G, int64_t n, int kp, int c8,
+                                 const float* __restrict__ gnorm1, float fac, uint4* __restrict__ out,
+                                 float* __restrict__ gstart) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * c8) return;
+  const int64_t r = i / c8;
+  const int c = (int)(i - r * c8);
+  const float4* x = reinterpret_cast<const float4*>(G + r * kp + 8 * c);
+  const float4 a = x[0], b = x[1];
+  out[i] = make_uint4(bf16_bits(a.x) | bf16_bits(a.y) << 16, bf16_bits(a.z) | bf16_bits(a.w) << 16,
+                      bf16_bits(b.x) | bf16_bits(b.y) << 16, bf16_bits(b.z) | bf16_bits(b.w) << 16);
+  if (c == 0) gstart[r] = gnorm1[r] * fac * 0.99999976158142089844f;
 }
 
 // max ||g||^2 (one atomic per block; non-negative floats order as their bit patterns)
@@ -1593,6 +2023,25 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SplitScan& sp,
 #undef EF_SEARCH_CASE
 }
 
+// Step 3 of the prefix search below: the probes of pw.list (count at ws.amb_count[1]) through
+// top1_t's cnt form, their keys and records scattered back.
+template <int KP>
+static hipError_t prefix_second_run(hipStream_t s, const SearchPlan& pl, const float* qpad, int64_t bpad, int64_t b,
+                                    const float* G, const float* gnorm2, int64_t n, int64_t g_offset, float gmax2,
+                                    const SearchWs& ws, const PrefixWs& pw, long long* keys) {
+  hipLaunchKernelGGL(prefix_gather_kernel, dim3((unsigned)((bpad * (KP / 4) + 255) / 256)), dim3(256), 0, s,
+                     reinterpret_cast<const float4*>(qpad), pw.list, ws.amb_count + 1, bpad, KP / 4,
+                     reinterpret_cast<float4*>(pw.qpad2));
+  SearchWs w2 = ws;
+  w2.match = ws.match ? pw.match2 : nullptr;
+  const hipError_t e = top1_t<KP, EF_METRIC_L2>(s, 0, true, pl, pw.qpad2, pw.qpad2, G, bpad, b, G, gnorm2, n, g_offset,
+                                                gmax2, w2, pw.keys2, nullptr, KP);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(prefix_scatter_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, s, pw.list, ws.amb_count,
+                     pw.keys2, w2.match, keys, ws.match);
+  return hipGetLastError();
+}
+
 // Prefix search.  pl1 = search_plan(bpad, n, K1, false, prefix_tile_rows(K1, S3)) plans the
 // prefix scan, pl the second run (the plain plan of KP).
 //   1. Q1 <- the probes' first K1 columns; search_kernel<K1> over (Q1, G1, gnorm1): the
@@ -1607,54 +2056,72 @@ hipError_t launch_search(hipStream_t s, int kp, int metric, const SplitScan& sp,
 //      in its cnt form (untimed, the device count in place of b, no memset of its own); the grids
 //      are sized for bpad and the work past the count returns at once, so the host never
 //      learns the count.  Their keys / records are scattered back by the list.
+// G1h (EF_OPT_SEARCH_PREFIX_SCREEN; S3 and K1 <= 32 only): the cascade.  Step 1 becomes three:
+//   1a. prefix64x_kernel<.., HI1> over (G1h, gstart): the timed main launch, one bf16 product per
+//       element; reduce_prefix_x_kernel<.., 2> proves what its per-row bound can and lists the
+//       rest in a list of its own (in pw.q1, which this form does not use; count at
+//       ws.amb_count[kScreenCount]).
+//   1b. prefix64x_kernel<.., CNT>: step 1's split scan for the listed probes alone, read through the
+//       list, the count on the device and the grid sized for bpad.
+//   1c. reduce_prefix_x_kernel<.., 1, LST>: step 2 for them; keys and records go to the probes' own
+//       places, and pw.list receives the probes neither stage proved, by their own index.
+// Step 3 is unchanged.  The caller zeroes ws.amb_count[kScreenCount] ahead of every piece.
 template <int KP, int K1, bool S3>
 static hipError_t search_prefix_t(hipStream_t s, const SearchPlan& pl, const SearchPlan& pl1, const float* qpad, int64_t bpad, int64_t b,
                                   const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
-                                  int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws, const PrefixWs& pw,
-                                  long long* keys, ef_ctx* c) {
+                                  const float* G1h, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
+                                  const PrefixWs& pw, long long* keys, ef_ctx* c) {
   constexpr int M = EF_METRIC_L2;
   const dim3 block(512), pgrid((unsigned)((b + 3) / 4)), sgrid((unsigned)(pl1.nchunks * pl1.n_ptiles));
   constexpr bool W64 = S3 && K1 <= 32;  // prefix64_kernel reads the probes' rows in place
+  if (G1h && !W64) return hipErrorInvalidValue;
   if constexpr (!W64)
     hipLaunchKernelGGL(prefix_cols_kernel, dim3((unsigned)((bpad * (K1 / 4) + 255) / 256)), dim3(256), 0, s,
                        reinterpret_cast<const float4*>(qpad), bpad, KP / 4, K1 / 4, reinterpret_cast<float4*>(pw.q1));
   TimerEvt tev;
   timer_begin(c, EF_KERNEL_SEARCH, &tev);
-  if constexpr (W64)
-    hipLaunchKernelGGL((prefix64_kernel<KP, K1, kPrefixSplitProbes / 256>), sgrid, block, 0, s, qpad, G1, gnorm1, n, pl1.n_ptiles,
-                       pl1.tiles_per_chunk, bpad, ws);
-  else
+  if constexpr (W64) {
+    if (G1h)
+      hipLaunchKernelGGL((prefix64x_kernel<KP, K1, kPrefixSplitProbes / 256, true, false>), sgrid, block, 0, s, qpad, G1h, gnorm1 + n,
+                         n, pl1.n_ptiles, pl1.tiles_per_chunk, bpad, ws, nullptr);
+    else
+      hipLaunchKernelGGL((prefix64_kernel<KP, K1, kPrefixSplitProbes / 256>), sgrid, block, 0, s, qpad, G1, gnorm1, n, pl1.n_ptiles,
+                         pl1.tiles_per_chunk, bpad, ws);
+  } else {
     hipLaunchKernelGGL((search_kernel<K1, M, false, S3, false, (K1 <= 32 ? kPrefixTile : TG)>), sgrid, block, 0, s,
                        pw.q1, G1, gnorm1, n, pl1.n_ptiles, pl1.tiles_per_chunk, bpad, ws);
+  }
   timer_end(c, &tev);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(ws.amb_count, 0, 2 * sizeof(int), s);  // [0] queued for fp64, [1] unproven
   if (e != hipSuccess) return e;
+  if constexpr (W64) {
+    if (G1h) {
+      int* const list1 = reinterpret_cast<int*>(pw.q1);  // no Q1 copy in this form: the screen's list
+      hipLaunchKernelGGL((reduce_prefix_x_kernel<KP, K1, 2, false>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl1.nchunks, G,
+                         g_offset, gmax2, ws, keys, list1, nullptr);
+      hipLaunchKernelGGL((prefix64x_kernel<KP, K1, kPrefixSplitProbes / 256, false, true>), sgrid, block, 0, s, qpad, G1, gnorm1, n,
+                         pl1.n_ptiles, pl1.tiles_per_chunk, bpad, ws, list1);
+      hipLaunchKernelGGL((reduce_prefix_x_kernel<KP, K1, 1, true>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl1.nchunks, G,
+                         g_offset, gmax2, ws, keys, pw.list, list1);
+      return prefix_second_run<KP>(s, pl, qpad, bpad, b, G, gnorm2, n, g_offset, gmax2, ws, pw, keys);
+    }
+  }
   hipLaunchKernelGGL((reduce_prefix_kernel<KP, K1, S3 ? 1 : 0>), pgrid, dim3(256), 0, s, qpad, b, bpad, pl1.nchunks, G, g_offset,
                      gmax2, ws, keys, pw.list);
-  hipLaunchKernelGGL(prefix_gather_kernel, dim3((unsigned)((bpad * (KP / 4) + 255) / 256)), dim3(256), 0, s,
-                     reinterpret_cast<const float4*>(qpad), pw.list, ws.amb_count + 1, bpad, KP / 4,
-                     reinterpret_cast<float4*>(pw.qpad2));
-  SearchWs w2 = ws;
-  w2.match = ws.match ? pw.match2 : nullptr;
-  e = top1_t<KP, M>(s, 0, true, pl, pw.qpad2, pw.qpad2, G, bpad, b, G, gnorm2, n, g_offset, gmax2, w2, pw.keys2,
-                    nullptr, KP);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(prefix_scatter_kernel, dim3((unsigned)((b + 255) / 256)), dim3(256), 0, s, pw.list, ws.amb_count,
-                     pw.keys2, w2.match, keys, ws.match);
-  return hipGetLastError();
+  return prefix_second_run<KP>(s, pl, qpad, bpad, b, G, gnorm2, n, g_offset, gmax2, ws, pw, keys);
 }
 
 hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan& pl, const SearchPlan& pl1,
                                 const float* qpad, int64_t bpad,
                                 int64_t b, const float* G, const float* gnorm2, const float* G1, const float* gnorm1,
-                                bool split, int64_t n, int64_t g_offset, float gmax2, const SearchWs& ws,
-                                const PrefixWs& pw, long long* keys, ef_ctx* c) {
+                                bool split, const float* G1h, int64_t n, int64_t g_offset, float gmax2,
+                                const SearchWs& ws, const PrefixWs& pw, long long* keys, ef_ctx* c) {
 #define EF_PREFIX_CASE(KPV, K1V)                                                                                  \
   if (kp == KPV && k1 == K1V)                                                                                     \
-    return split ? search_prefix_t<KPV, K1V, true>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, n, g_offset, gmax2, ws, pw, keys, c) \
-                 : search_prefix_t<KPV, K1V, false>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, n, g_offset, gmax2, ws, pw, keys, c);
+    return split ? search_prefix_t<KPV, K1V, true>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, G1h, n, g_offset, gmax2, ws, pw, keys, c) \
+                 : search_prefix_t<KPV, K1V, false>(s, pl, pl1, qpad, bpad, b, G, gnorm2, G1, gnorm1, G1h, n, g_offset, gmax2, ws, pw, keys, c);
   EF_PREFIX_CASE(128, 64)
   EF_PREFIX_CASE(128, 32)
   EF_PREFIX_CASE(128, 16)
@@ -1663,6 +2130,13 @@ hipError_t launch_search_prefix(hipStream_t s, int kp, int k1, const SearchPlan&
   EF_PREFIX_CASE(32, 16)
 #undef EF_PREFIX_CASE
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_prefix_screen_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, void* G1h, float* gnorm1) {
+  const float fac = (float)(1.0 - kScreenEs - prefix_screen_cg(k1));
+  hipLaunchKernelGGL(prefix_hi_kernel, dim3((unsigned)((n * (k1 / 8) + 255) / 256)), dim3(256), 0, s, G, n, kp, k1 / 8,
+                     gnorm1, fac, static_cast<uint4*>(G1h), gnorm1 + n);
+  return hipGetLastError();
 }
 
 hipError_t launch_prefix_gallery(hipStream_t s, const float* G, int64_t n, int kp, int k1, bool split, float* G1,

@@ -51,6 +51,7 @@ EF_OPT_SEARCH_TOPK_CAND = 12
 EF_OPT_SEARCH_PREFIX_SPLIT = 13
 EF_OPT_PROJECT_SPLIT_BF16 = 14
 EF_OPT_RANK_BITMAP_BYTES = 15
+EF_OPT_SEARCH_PREFIX_SCREEN = 16
 EF_TOPK_MAX = 64  # most ranks of a top-m search
 EF_LABEL_SAME, EF_LABEL_OTHER, EF_LABEL_ANY = 0, 1, 2  # ef_search_labelled relations
 EF_CENSUS_MAX_BINS = 2048  # most bins of ef_score_census
@@ -151,6 +152,7 @@ _SIGS = {
     "ef_timing_get": ([vp, i32, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
     "ef_timing_reset": ([vp], C.c_int),
     "ef_search_stats": ([vp, C.POINTER(i64)], C.c_int),
+    "ef_prefix_screen_stats": ([vp, C.POINTER(i64)], C.c_int),  # added by symbol
     "ef_search_topk": ([vp, vp, i64, i32, i32, vp, u32], C.c_int),
     "ef_recognize_topk": ([vp, vp, i32, i64, i32, i32, vp, vp, u32], C.c_int),
     "ef_search_topk_matches": ([vp, vp, i64, i32, i32, vp, u32], C.c_int),

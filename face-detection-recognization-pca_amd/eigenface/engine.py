@@ -96,6 +96,7 @@ _OPTIONS = {"fit_max_iters": N.EF_OPT_FIT_MAX_ITERS, "fit_fp32_coarse": N.EF_OPT
             "fit_chebyshev": N.EF_OPT_FIT_CHEBYSHEV, "host_threads": N.EF_OPT_HOST_THREADS,
             "search_prefix": N.EF_OPT_SEARCH_PREFIX, "search_topk_cand": N.EF_OPT_SEARCH_TOPK_CAND,
             "search_prefix_split": N.EF_OPT_SEARCH_PREFIX_SPLIT,
+            "search_prefix_screen": N.EF_OPT_SEARCH_PREFIX_SCREEN,
             "project_split_bf16": N.EF_OPT_PROJECT_SPLIT_BF16, "rank_bitmap_bytes": N.EF_OPT_RANK_BITMAP_BYTES}
 
 
@@ -323,6 +324,13 @@ class Engine:
         most recent search (ef_search_stats); synchronises the stream."""
         out = (C.c_int64 * 4)()
         self._chk(self._lib.ef_search_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def search_screen_stats(self):
+        """(probes screened, proven by the screen, screen's guard skipped it) of the most recent
+        search (ef_prefix_screen_stats); synchronises the stream."""
+        out = (C.c_int64 * 3)()
+        self._chk(self._lib.ef_prefix_screen_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     # --------------------------------------------------------------- multi-GPU

@@ -861,6 +861,15 @@ int ef_comm_info(const ef_ctx* ctx, int32_t* nranks, int32_t* rank);
                                       0's in their last bits (as between two batch sizes) and
                                       repeat bit for bit from call to call.  0: always the fp32
                                       kernel */
+#define EF_OPT_SEARCH_PREFIX_SCREEN 16 /* the EF_OPT_SEARCH_PREFIX scan as a cascade (added by symbol,
+                                      EF_API_VERSION stays 7).  1 [default]: where the split-bf16
+                                      prefix scan runs at K1 <= 32, a single-bf16 screen (one bf16
+                                      product per element over a bf16 copy of the prefix, n x K1 x
+                                      2 B) goes first and proves a probe's winner with a bound
+                                      taken per row and per probe, es (||q[:K1]||^2 + ||g[:K1]||^2),
+                                      es = 2.01 2^-8; the split scan runs for the probes it cannot
+                                      prove alone, the full-k scan for the rest.  Results are those
+                                      of 0.  0: the split scan for every probe */
 #define EF_OPT_RANK_BITMAP_BYTES 15 /* diagnostic (added by symbol): device budget of ef_search_rank's
                                       (probe, identity) bitmap [256 MiB]; the probes run in pieces
                                       of whole 256-probe blocks that fit it, a value below one
@@ -1119,6 +1128,13 @@ int ef_timing_reset(ef_ctx* ctx);
  * the prefix scan}.  A search the prefix scan does not apply to reports {probes, 0, 0, 0}.
  * Synchronises the context's stream. */
 int ef_search_stats(ef_ctx* ctx, int64_t out[4]);
+
+/* Added by symbol (EF_API_VERSION stays 7).  The screen's counters of the most recent search
+ * (EF_OPT_SEARCH_PREFIX_SCREEN): out = {probes screened, proven by the screen, 1 if the screen's
+ * guard sent the search straight to the split scan}.  A search without the screen reports
+ * {0, 0, 0 or 1}.  ef_search_stats counts a probe as proven whichever prefix stage proved it.
+ * Python: Engine.search_screen_stats().  Synchronises the context's stream. */
+int ef_prefix_screen_stats(ef_ctx* ctx, int64_t out[3]);
 
 #ifdef __cplusplus
 }
